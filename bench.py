@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
-"""DHGR frames transcoded per second on MI355X (BASELINE.json metric) + make_data_tables wall-clock.
+"""DHGR frames transcoded per second on MI355X (BASELINE.json metric); with --full also make_data_tables wall-clock and more.
 
-    python bench.py --gpus N --steps K --warmup W [--mode DHGR|HGR] [--palette NTSC|IIGS] [--streams S] [--emit]
+    python bench.py --gpus N --steps K --warmup W [--mode DHGR|HGR] [--palette NTSC|IIGS] [--streams S] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: setup, W warm-up steps, the K timed steps, the outputs
+(--dump-outputs DIR: the last timed step's opcode rows of a fixed, seeded sample of the streams and its segments, as
+DIR/<name>.npy in float32 / float64, 64 MB at most; the inputs are the same from run to run), the JSON line.  Everything
+else -- the events leg and the roofline objects, the CPU baselines, the extra legs below -- runs with --full only.
 
 Workload (BASELINE.json configs[3]; configs[2] with --mode HGR; configs[4] with --palette IIGS
 under torchrun on 8 GPUs): synthetic 560x192 (280x192) S-iid clips, driver =
@@ -13,12 +18,12 @@ of every clip; the defaults (20 steps x 50 frames) make each clip 1000 frames lo
 
 Inputs (targets, tables, stream state) are resident in HBM before the timed region.  The timed
 region is exactly K steps, bracketed by barrier + torch.cuda.synchronize() on both sides; the
-reported time is the MAX over ranks.  Between the W warm-up steps and the timed region runs an
+reported time is the MAX over ranks.  With --full, between the W warm-up steps and the timed region runs an
 untimed EVENTS leg (min(K, 3) of the same steps) in which the library records a HIP event pair
 around every kernel launch on the launch stream: the per-kernel launch durations of the roofline
 objects come from it, and the timed region runs without any event recording.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   roofline            greedy_wave_kernel (dominant): algorithmic bytes per launch (534 B per opcode,
                       SURVEY.md 8d) / mean launch duration from the events leg, against the 8 TB/s
                       HBM peak.  `traffic`, `issue` and roofline_prologue's counter_* figures are
@@ -118,10 +123,17 @@ def parse_args(argv=None):
                          "(with --repeat N, every drawn frame is shown N times): the work list runs dry, the re-queued bag "
                          "and the out-of-work padding are what gets timed")
     ap.add_argument("--repeat", type=int, default=1, help="with --static: show every drawn frame this many times")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip make_data_tables / single-stream (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the events leg and the roofline objects, the CPU baselines and "
+                         "the extra legs.  Without it a run sets up, warms up, times --steps steps, writes --dump-outputs and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64; "
+                         "the opcode rows of a fixed, seeded sample of the streams, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra legs (profiling runs)")
     ap.add_argument("--extras", default="all",
-                    help="comma list of the extra legs to run beside the timed region (default all): single_stream, emit, "
+                    help="with --full: comma list of the extra legs to run beside the timed region (default all): single_stream, emit, "
                          "make_data_tables, ingest, dropin, hgr, img, fourth_offset, joint -- for iterating on one of them")
     ap.add_argument("--cpu-frames", type=int, default=600, help="frames of stream 0 the CPU baseline encodes")
     ap.add_argument("--cpu-frames-all", type=int, default=60, help="frames per stream of the all-cores CPU baseline")
@@ -143,7 +155,7 @@ def parse_args(argv=None):
                     help="A/B: launch the streams in index order instead of longest first (IIV_OPT_STREAM_ORDER 0; same bytes)")
     ap.add_argument("--lds-pad", type=int, default=-1, help="tuning: extra LDS bytes per greedy wave (caps streams per CU)")
     ap.add_argument("--emit", action="store_true",
-                    help="(default unless --no-extras) also time encode -> .a2m byte emission -> pinned host "
+                    help="(default with --full unless --no-extras) also time encode -> .a2m byte emission -> pinned host "
                          "memory, end to end; kept as a flag for older command lines")
     ap.add_argument("--no-emit", action="store_true", help="skip the end-to-end emission leg")
     ap.add_argument("--dist-backend", choices=["gloo", "nccl"], default=os.environ.get("IIV_BENCH_DIST_BACKEND", "gloo"),
@@ -416,7 +428,18 @@ class GpuBackend:
         the timed region and the clip count does not depend on --warmup.  (S-coh / S-static clips do not wrap: they are
         as long as warm-up + timed region -- a wrap would put one complete redraw into the timed region; see main().)"""
         self.last_ops, segs = self.batch.encode_frames(self.fm, self.fa, self.args.frames_per_step, self.ops_buf, loop=True)
+        self.last_segs = segs
         return segs
+
+    def outputs(self):
+        """What the caller of the last step received (StreamBatch.encode_frames: the (S, n, 6) opcode rows and the segments),
+        for --dump-outputs: the rows of the streams dump_sample() picks, as float32."""
+        import numpy as np
+        rows = self.last_ops
+        idx = dump_sample(self.S, rows.shape[1] * rows.shape[2] * 4)
+        ops = rows.index_select(0, self.torch.from_numpy(idx).to(rows.device)).cpu().numpy()
+        return {"opcodes": ops.astype(np.float32), "opcode_streams": idx.astype(np.float64),
+                "segments": np.asarray(self.last_segs, dtype=np.float64).reshape(-1, 4)}
 
     def first_ops(self, segs):
         """The opcodes of the step just run for the clips the oracle re-encodes afterwards -- the first, the middle and the
@@ -446,6 +469,34 @@ class GpuBackend:
 
     def uses_wave_kernel(self):
         return self.args.greedy != "workgroup" and not self.args.joint
+
+
+DUMP_MAX_BYTES = 64 << 20    # --dump-outputs: all files together
+DUMP_MAX_STREAMS = 64        # opcode rows of at most this many streams (64 x 50 frames x 490 opcodes x 6 x 4 B = 37.6 MB)
+DUMP_SEED = 20240229
+
+
+def dump_sample(S, bytes_per_stream):
+    """The streams --dump-outputs writes: a fixed, seeded choice out of S (sorted), as many as fit the size limit."""
+    import numpy as np
+    k = int(max(1, min(S, DUMP_MAX_STREAMS, (DUMP_MAX_BYTES * 3 // 4) // max(int(bytes_per_stream), 1))))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(S, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(be, out_dir):
+    """Write be.outputs() -- what the last timed step computed -- as out_dir/<name>.npy; returns the names."""
+    import numpy as np
+    arrays = be.outputs()
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise SystemExit("bench.py: output %s is %s, not float32 / float64" % (name, a.dtype))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: the outputs are %d bytes, more than %d" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 class _QuietStdout:
@@ -514,7 +565,7 @@ def _run(args, backend_cls, quiet):
     # S-iid and S-img frames are to each other anyway; for S-coh / S-static that wrap would put one complete redraw into the
     # timed region, so those clips are as long as warm-up + timed region and never wrap.
     wraps = not (args.coherent or args.static)
-    n_frames = args.steps * F if wraps else (args.steps + args.warmup + events_leg_steps(args.steps)) * F
+    n_frames = args.steps * F if wraps else (args.steps + args.warmup + (events_leg_steps(args.steps) if args.full else 0)) * F
     S = args.streams
     if S <= 0:
         per_clip = n_frames * 8192 * (2 if dhgr else 1) + 300 * 1024 + F * OPS_PER_FRAME * 6   # frames + stream state (292 KB) + opcodes
@@ -537,8 +588,9 @@ def _run(args, backend_cls, quiet):
         if use_dist:
             dist.barrier()
 
-    leg = timed_leg(be, args.steps, args.warmup, barrier)
+    leg = timed_leg(be, args.steps, args.warmup, barrier, events=args.full)
     first_ops, op_count, seg_count, prof = leg["first_ops"], leg["op_count"], leg["seg_count"], leg["prof"]
+    dumped = dump_outputs(be, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
     rank_elapsed = all_ranks(leg["elapsed"], cdev, world, use_dist)   # (one float per rank: what the line's per-rank rates come from)
     seed_lo = all_ranks(float(seeds[0][0]), cdev, world, use_dist)     # first / last stream seed of every rank: disjoint ranges
     seed_hi = all_ranks(float(seeds[-1][0]), cdev, world, use_dist)
@@ -602,9 +654,12 @@ def _run(args, backend_cls, quiet):
         "diff_weights": "table-gather" if args.dw_table or args.dw == "table" else args.dw,
         "table_build_s": t_tab,
         "build_id": be.build_id() if hasattr(be, "build_id") else None,   # iiv_version(): what committed counter runs must carry to be quoted
+        "full": bool(args.full),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "names": dumped, "of": "the last timed step, rank 0"}
 
-    if rank == 0:
+    if rank == 0 and args.full:
         ev = leg["events"]
         out.update(_roofline_objects(be, args, prof, ev["op_count"], ev["seg_count"], S, ev["elapsed"],
                                      live_ceiling=be.is_gpu and not args.no_extras))
@@ -650,6 +705,7 @@ def _run(args, backend_cls, quiet):
                 if want("joint"):
                     out["joint"] = _hgr_leg(be, args, local_rank, world, steps=2, warmup=1, mode="DHGR", joint=True, streams=min(be.S, 3072))
 
+    if rank == 0:
         quiet.restore()
         print(json.dumps(out))
         sys.stdout.flush()
@@ -664,18 +720,23 @@ def events_leg_steps(steps):
     return min(int(steps), 3)
 
 
-def timed_leg(be, steps, warmup, barrier=lambda: None):
+def timed_leg(be, steps, warmup, barrier=lambda: None, events=True):
     """W untimed warm-up steps, an untimed EVENTS leg, then exactly K steps bracketed by barrier + synchronize on both sides.
     The events leg (events_leg_steps(K) steps of the same work) is where the library records a HIP event pair around every
     kernel launch on the launch stream (iiv_encoder_profile): the kernels' average launch durations -- roofline.achieved,
     avg_launch_ms, kernel_time_share -- come from it, and the timed region that `value` is computed from runs with no
-    event recording at all (round 5 recorded them inside it)."""
+    event recording at all (round 5 recorded them inside it).  events=False (a run without --full): no events leg, the
+    timed region follows the warm-up."""
     first_ops = None   # stream 0's opcodes of the first step, checked against the oracle by _cpu_baseline
     for i in range(warmup):
         segs0 = be.step()
         if i == 0:
             first_ops = be.first_ops(segs0)
     be.check()
+    if not events:
+        leg = _timed_region(be, steps, barrier)
+        leg.update({"prof": None, "first_ops": first_ops, "events": None})
+        return leg
     # ---- the events leg
     be.profile(True)
     barrier()
@@ -693,7 +754,14 @@ def timed_leg(be, steps, warmup, barrier=lambda: None):
     prof = be.profile_read()
     be.profile(False)
     be.check()
-    # ---- the timed region
+    leg = _timed_region(be, steps, barrier)
+    leg.update({"prof": prof, "first_ops": first_ops,
+                "events": {"steps": events_leg_steps(steps), "elapsed": e1 - e0, "op_count": ev_ops, "seg_count": ev_segs}})
+    return leg
+
+
+def _timed_region(be, steps, barrier):
+    """Exactly `steps` steps between barrier + synchronize on both sides."""
     barrier()
     be.synchronize()
     t0 = time.perf_counter()
@@ -706,8 +774,7 @@ def timed_leg(be, steps, warmup, barrier=lambda: None):
     barrier()
     t1 = time.perf_counter()
     be.check()
-    return {"elapsed": t1 - t0, "prof": prof, "op_count": op_count, "seg_count": seg_count, "first_ops": first_ops,
-            "events": {"steps": events_leg_steps(steps), "elapsed": e1 - e0, "op_count": ev_ops, "seg_count": ev_segs}}
+    return {"elapsed": t1 - t0, "op_count": op_count, "seg_count": seg_count}
 
 
 def _gather_ceiling_live(S, mode="DHGR", shared=False):

@@ -49,7 +49,15 @@ class CpuStandIn:
 
     def step(self):
         self.log["steps"] += 1
-        return self.clock.segments(self.args.frames_per_step)
+        self.last_segs = self.clock.segments(self.args.frames_per_step)
+        return self.last_segs
+
+    def outputs(self):
+        """what --dump-outputs writes: the last step's segments and the streams bench.dump_sample picks"""
+        import numpy as np
+        import bench
+        idx = bench.dump_sample(self.S, 6 * 4 * sum(s[3] for s in self.last_segs))
+        return {"opcode_streams": idx.astype(np.float64), "segments": np.asarray(self.last_segs, dtype=np.float64).reshape(-1, 4)}
 
     def first_ops(self, segs):
         return {0: torch.zeros((sum(s[3] for s in segs), 6), dtype=torch.uint8)}

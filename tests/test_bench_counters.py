@@ -32,7 +32,7 @@ def _line(tmp_path, monkeypatch, doc):
         monkeypatch.delenv(k, raising=False)
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        out = bench.main(["--backend", "bench_standin:CpuStandIn", "--steps", "2", "--warmup", "1", "--frames-per-step", "4", "--streams", "64"])
+        out = bench.main(["--full", "--backend", "bench_standin:CpuStandIn", "--steps", "2", "--warmup", "1", "--frames-per-step", "4", "--streams", "64"])
     return out
 
 

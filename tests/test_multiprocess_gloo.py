@@ -102,7 +102,7 @@ def test_bench_main_runs_in_two_ranks(tmp_path, monkeypatch):
     monkeypatch.setenv("IIV_BENCH_SYSFS", str(tmp_path))   # (the spawned ranks inherit it)
     for var in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
         monkeypatch.delenv(var, raising=False)
-    argv = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--frames-per-step", "4", "--config", "5"]
+    argv = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--frames-per-step", "4", "--config", "5", "--full"]
     (r0, v0, cfg0, log0, line0), (r1, v1, cfg1, log1, line1) = _spawn(_bench_worker, 2, (argv,))
     # every rank pinned itself to the CPUs of its GPU's NUMA node before anything else, and the line says so
     if len(os.sched_getaffinity(0)) >= 8:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B: run bench.py against several builds of the library (IIV_LIB override) on one box.
 #   tools/ab_libs.sh "bench args" lib1.so lib2.so ...
-args="$1"; shift
+args="--full $1"; shift   # (the roofline objects are read below)
 for lib in "$@"; do
   IIV_LIB=$PWD/$lib python bench.py --no-cpu-baseline $args 2>/tmp/ab_libs.err | tail -1 | python -c "
 import sys, json

@@ -71,7 +71,7 @@ def main():
     tmp = "/tmp/iiv_prof"
     subprocess.run(["rm", "-rf", tmp])
     os.makedirs(tmp)
-    bench = ["python3", os.path.join(ROOT, "bench.py")] + bench_args
+    bench = ["python3", os.path.join(ROOT, "bench.py"), "--full"] + bench_args   # (the line's roofline is read below)
     r = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp + "/stats", "--"] + bench,
                        cwd="/tmp", stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, check=False)
     bench_line = next((l for l in reversed(r.stdout.splitlines()) if l.startswith("{")), "")
