@@ -49,6 +49,7 @@ SYMBOLS = [
     "iiv_build_narrow_store_table",
     "iiv_check_diff_weight_pieces",
     "iiv_emit_stream", "iiv_emit_chunk", "iiv_frames_to_memory_maps",
+    "iiv_audio_tick_count", "iiv_audio_ticks", "iiv_audio_resample", "iiv_audio_normalization",
 ]
 
 
@@ -161,11 +162,20 @@ def lib():
     L.iiv_emit_chunk.argtypes = [i32, i32, C.c_long, C.c_long, vp, sz, vp, sz, i32, vp, C.c_uint16, vp, sz,
                                  C.POINTER(sz), C.POINTER(sz), vp, vp]
     L.iiv_frames_to_memory_maps.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp]
+    if hasattr(L, "iiv_audio_ticks") or "IIV_LIB" not in os.environ:
+        lg = C.c_long
+        L.iiv_audio_tick_count.restype = lg
+        L.iiv_audio_tick_count.argtypes = [lg, i32, i32, lg]
+        L.iiv_audio_ticks.argtypes = [i32, vp, sz, vp, vp, vp, i32, lg, vp, vp, sz, vp, vp]
+        L.iiv_audio_resample.argtypes = [i32, vp, sz, vp, vp, vp, i32, vp, sz, vp, vp]
+        L.iiv_audio_normalization.argtypes = [i32, vp, sz, vp, vp, vp, i32, vp, vp]
     if hasattr(L, "iiv_encoder_launch_forms") or "IIV_LIB" not in os.environ:
         L.iiv_encoder_launch_forms.argtypes = [vp, C.POINTER(C.c_int64)]
     for name in SYMBOLS:
         if "IIV_LIB" in os.environ and name in ("iiv_encoder_launch_forms", "iiv_check_diff_weight_pieces", "iiv_encoder_info", "iiv_encoder_get_video_brief_async",
-                                                 "iiv_encoder_live_queue", "iiv_encode_live", "iiv_encoder_set_state_async") and not hasattr(L, name):
+                                                 "iiv_encoder_live_queue", "iiv_encode_live", "iiv_encoder_set_state_async",
+                                                 "iiv_audio_tick_count", "iiv_audio_ticks", "iiv_audio_resample",
+                                                 "iiv_audio_normalization") and not hasattr(L, name):
             continue   # (an older build under IIV_LIB: tools/ab_libs.sh)
         getattr(L, name)  # AttributeError if the library lacks a declared symbol
     _lib = L
@@ -739,3 +749,89 @@ def frames_to_memory_maps(mode, palette_rgb, rgb, dither=0, out=None):
             aux = None
     check(lib().iiv_frames_to_memory_maps(mode, hptr(pal), n, dptr(rgb), int(dither), dptr(main), dptr(aux), stream_ptr()))
     return main, aux
+
+
+# ---- f4: the audio track ------------------------------------------------------------
+
+AUDIO_BITRATE = 14700          # audio.Audio(bitrate=14700) (audio.py:35)
+AUDIO_BLOCK_FRAMES = 128 * 1024  # audio.py:98 f.read_data(128 * 1024): frames per decode block
+
+
+def audio_tick_count(n_frames, rate, bitrate=AUDIO_BITRATE, block_frames=AUDIO_BLOCK_FRAMES):
+    """Ticks (= opcodes) of one stream of n_frames frames at `rate` Hz.  Host only."""
+    n = lib().iiv_audio_tick_count(int(n_frames), int(rate), int(bitrate), int(block_frames))
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def _audio_streams(pcm, n_frames, channels, rate):
+    """pcm: CUDA int16 (S, stride) (each row interleaved frames); per-stream frame counts / channels / rates (scalars
+    broadcast) -> the host arrays of the C ABI."""
+    torch = _torch()
+    if not (pcm.is_cuda and pcm.dtype == torch.int16 and pcm.dim() == 2 and pcm.stride(1) == 1):
+        raise ValueError("pcm must be a CUDA int16 tensor (n_streams, samples) with contiguous rows")
+    S = int(pcm.shape[0])
+    nf = np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, dtype=np.int64), (S,)), dtype=C.c_long)
+    ch = np.ascontiguousarray(np.broadcast_to(np.asarray(channels, dtype=np.int32), (S,)), dtype=np.int32)
+    rt = np.ascontiguousarray(np.broadcast_to(np.asarray(rate, dtype=np.int32), (S,)), dtype=np.int32)
+    if S and int((nf.astype(np.int64) * ch).max()) > int(pcm.shape[1]):   # (the C side can only check the row stride)
+        raise ValueError("pcm rows hold %d samples; a stream needs n_frames * channels = %d" % (
+            int(pcm.shape[1]), int((nf.astype(np.int64) * ch).max())))
+    return S, nf, ch, rt
+
+
+AUDIO_PREFIX_BYTES = 10 * 1024 * 1024   # audio.py:63 _normalization(read_bytes=1024 * 1024 * 10)
+AUDIO_RAW_BLOCK_FRAMES = 1024           # audioread's wave backend: read_data() reads 1024 frames a block (DESIGN.md 10, A2)
+
+
+def audio_prefix_frames(n_frames, channels):
+    """The frames Audio._normalization decodes (audio.py:62-66: reads until more than 10 MiB are held); the rule
+    iiv_audio_normalization applies."""
+    blocks = AUDIO_PREFIX_BYTES // (AUDIO_RAW_BLOCK_FRAMES * 2 * int(channels)) + 1
+    return min(int(n_frames), blocks * AUDIO_RAW_BLOCK_FRAMES)
+
+
+def audio_ticks(pcm, n_frames, channels, rate, normalization, bitrate=AUDIO_BITRATE, block_frames=AUDIO_BLOCK_FRAMES,
+                out=None):
+    """Speaker duty cycles (4..66, even) of S streams: pcm CUDA int16 (S, >= n_frames * channels) -> (CUDA uint8
+    (S, max tick count) -- bytes past a stream's own count are left as they were --, int64 numpy tick counts).
+    normalization: per stream (or one value).  out: a CUDA uint8 (S, >= max count) tensor with contiguous rows to write into.
+    Asynchronous on torch's current stream."""
+    torch = _torch()
+    S, nf, ch, rt = _audio_streams(pcm, n_frames, channels, rate)
+    nm = np.ascontiguousarray(np.broadcast_to(np.asarray(normalization, dtype=np.float64), (S,)))
+    counts = np.array([audio_tick_count(nf[s], rt[s], bitrate, block_frames) for s in range(S)], dtype=C.c_long)
+    width = int(counts.max()) if S else 0
+    if out is None:
+        out = torch.zeros((S, max(width, 1)), dtype=torch.uint8, device="cuda")
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == S and out.shape[1] >= width
+              and out.stride(1) == 1):
+        raise ValueError("out must be a CUDA uint8 tensor (n_streams, >= %d) with contiguous rows" % width)
+    got = np.zeros(S, dtype=C.c_long)
+    check(lib().iiv_audio_ticks(S, dptr(pcm), int(pcm.stride(0)), hptr(nf), hptr(ch), hptr(rt), int(bitrate),
+                                int(block_frames), hptr(nm), dptr(out), int(out.stride(0)), hptr(got), stream_ptr()))
+    return out, got.astype(np.int64)
+
+
+def audio_resample(pcm, n_frames, channels, rate, bitrate=AUDIO_BITRATE):
+    """audio.Audio._decode of each whole stream as one block -> (CUDA float32 (S, max length), int64 numpy lengths)."""
+    torch = _torch()
+    S, nf, ch, rt = _audio_streams(pcm, n_frames, channels, rate)
+    lens = np.array([audio_tick_count(nf[s], rt[s], bitrate, max(int(nf[s]), 1)) for s in range(S)], dtype=C.c_long)
+    out = torch.zeros((S, max(int(lens.max()) if S else 0, 1)), dtype=torch.float32, device="cuda")
+    got = np.zeros(S, dtype=C.c_long)
+    check(lib().iiv_audio_resample(S, dptr(pcm), int(pcm.stride(0)), hptr(nf), hptr(ch), hptr(rt), int(bitrate),
+                                   dptr(out), int(out.stride(0)), hptr(got), stream_ptr()))
+    return out, got.astype(np.int64)
+
+
+def audio_normalization(pcm, n_frames, channels, rate, bitrate=AUDIO_BITRATE):
+    """audio.Audio._normalization of S streams on the device -> float64 numpy (S,) (inf for a silent prefix).
+    Synchronises."""
+    _torch()
+    S, nf, ch, rt = _audio_streams(pcm, n_frames, channels, rate)
+    out = np.zeros(S, dtype=np.float64)
+    check(lib().iiv_audio_normalization(S, dptr(pcm), int(pcm.stride(0)), hptr(nf), hptr(ch), hptr(rt), int(bitrate),
+                                        hptr(out), stream_ptr()))
+    return out

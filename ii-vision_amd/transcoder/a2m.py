@@ -2,8 +2,9 @@
 
 Mirrors what movie.Movie.emit_stream / done (transcoder/movie.py:113-161) produce
 through opcodes.py / machine.py for one stream, for any number of streams at once
-(iiv_emit_stream, csrc/iiv_a2m.hip).  Audio is out of scope here: the caller supplies
-the speaker duty cycle ("tick", 4..66 even, movie.py:104-107) of every opcode.
+(iiv_emit_stream, csrc/iiv_a2m.hip).  The caller supplies the speaker duty cycle ("tick",
+4..66 even, movie.py:104-107) of every opcode: audio.ArrayAudio.ticks() computes them from the
+clip's PCM on the device (csrc/iiv_audio.hip), or a constant stands in for a silent movie.
 """
 
 import numpy as np

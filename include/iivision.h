@@ -502,6 +502,49 @@ int iiv_emit_chunk(int mode, int n_streams, long first_op, long n_ops, const uin
                    uint16_t ack_addr, uint8_t *d_out, size_t out_stride, size_t *first_byte, size_t *n_bytes,
                    int *d_err, void *stream);
 
+
+/* ==== f4: the audio track ===================================================
+ * audio.Audio (transcoder/audio.py:9-107) and the tick of movie.Movie.encode (movie.py:67-111): interleaved int16 PCM
+ * -> one speaker duty cycle per player opcode.  Per stream: frames are cut into decode blocks of block_frames frames
+ * (audio.py:98 read_data(128 * 1024); the last block is short), each block is averaged over its channels
+ * (audio.py:51-55, librosa.to_mono) and resampled on its own from rate to bitrate (audio.py:56-58: librosa.resample,
+ * res_type='scipy', scale=True: scipy.signal.resample to ceil(n * bitrate / rate) samples, divided by
+ * sqrt(bitrate / rate); rate == bitrate: untouched), then a /= 16384, a *= normalization, au = clip(int(a * 16), -15, 16)
+ * (audio.py:100-105), tick = 2 au + 34 (movie.py:104-107).  Opcode k of a movie carries tick k.  The arithmetic is fp32
+ * FFTs on the device (csrc/iiv_audio.hip).
+ * d_pcm: stream s at d_pcm + s * pcm_stride (int16 elements), n_frames[s] frames of channels[s] interleaved samples at
+ * rate[s] Hz -- host arrays of n_streams entries.  Streams are independent; at most 65535 per call.
+ * Transforms run on at most 2^24 points: a call whose decode block (or, for iiv_audio_resample / _normalization, whole
+ * stream / prefix), before or after resampling, is not a power of two and longer than 2^23 points is refused with
+ * IIV_ERR_INVALID before anything is launched (e.g. the normalisation of 8 kHz mono longer than about 570 s).
+ * Device memory is allocated stream-ordered per call and freed behind the call's work; nothing is kept between calls. */
+
+/* The tick count of one stream (the sum of the blocks' ceil(n * bitrate / rate), each product in float64 as librosa
+ * computes it).  Host only, no device; a negative error code for bad arguments. */
+long iiv_audio_tick_count(long n_frames, int rate, int bitrate, long block_frames);
+
+/* Audio.audio_stream (audio.py:93-107) for n_streams streams: d_ticks [n_streams][ticks_stride] uint8 receives tick k
+ * of stream s at d_ticks + s * ticks_stride + k for k < n_ticks[s] (host, filled before the call returns; may be NULL);
+ * bytes past a stream's tick count are not written.  normalization: host, per stream (Audio.normalization, e.g. from
+ * iiv_audio_normalization); IIV_ERR_INVALID if one is zero or not finite (16384 / 0 for a silent prefix: the reference
+ * turns the resulting NaN into an undefined int).  Asynchronous on `stream`. */
+int iiv_audio_ticks(int n_streams, const int16_t *d_pcm, size_t pcm_stride, const long *n_frames, const int *channels,
+                    const int *rate, int bitrate, long block_frames, const double *normalization, uint8_t *d_ticks,
+                    size_t ticks_stride, long *n_ticks, void *stream);
+
+/* Audio._decode of each whole stream as ONE block (audio.py:47-60): d_out [n_streams][out_stride] float32, sample k of
+ * stream s at d_out + s * out_stride + k for k < n_out[s] (host, may be NULL).  What iiv_audio_normalization
+ * measures, exposed for tests and tools.  Asynchronous on `stream`. */
+int iiv_audio_resample(int n_streams, const int16_t *d_pcm, size_t pcm_stride, const long *n_frames, const int *channels,
+                       const int *rate, int bitrate, float *d_out, size_t out_stride, long *n_out, void *stream);
+
+/* Audio._normalization (audio.py:60-78) per stream: the prefix audioread's default read_data() blocks (1024 frames)
+ * deliver until more than 10 MiB are held, decoded as one block, norm = max(|percentile(a, [0.5, 99.5])|) (linear
+ * interpolation, order statistics selected on the device) -> normalization[s] = 16384 / norm (host; inf for a silent
+ * prefix).  Synchronises. */
+int iiv_audio_normalization(int n_streams, const int16_t *d_pcm, size_t pcm_stride, const long *n_frames, const int *channels,
+                            const int *rate, int bitrate, double *normalization, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,11 +1,14 @@
 """End to end on one GPU, everything on the device: RGB frames -> memory maps (f3, csrc/iiv_ingest.hip) ->
 Movie-paced encode (the hot path + f1: prologue / greedy kernels driven by stream_batch.MovieClock) -> player byte
 stream (f2, csrc/iiv_a2m.hip) -> an .a2m file.  What the reference's `main.py in.mp4 out.a2m` does between its decoder
-and its output file (transcoder/main.py, movie.py:56-161), minus audio: every opcode carries the same speaker duty
+and its output file (transcoder/main.py, movie.py:56-161).  The speaker duty cycle of every opcode comes from the clip's
+audio (`--audio clip.wav`, or `--pcm pcm.npy --rate R`: csrc/iiv_audio.hip, transcoder/audio.py), and the movie ends where
+the audio or the frames run out, whichever is first (movie.py:67-74); without audio every opcode carries the same duty
 cycle (`--tick`, 4..66 even: movie.py:104-107).
 
     python tools/transcode_clip.py --frames clip.npy --out clip.a2m --dbg /path/to/player/iivision.dbg
     python tools/transcode_clip.py --synthetic 90 --out /tmp/bars.a2m            # a moving test card
+    python tools/transcode_clip.py --frames clip.npy --audio clip.wav --out clip.a2m
 
 --frames: uint8 array (n, 192, 280, 3), i.e. what the reference's FileFrameGrabber holds after its resize
 (frame_grabber.py:75).  --dbg: the player's cc65 debug file, from which the opcode entry points are read exactly as
@@ -41,7 +44,12 @@ def main():
     ap.add_argument("--palette", choices=["NTSC", "IIGS"], default="NTSC")
     ap.add_argument("--dither", default="diffusion", help='"diffusion" (Floyd-Steinberg) or the amplitude 0..255 of the ordered dither')
     ap.add_argument("--dbg", help="player/iivision.dbg (opcode entry points)")
-    ap.add_argument("--tick", type=int, default=34, help="speaker duty cycle of every opcode (4..66, even)")
+    ap.add_argument("--tick", type=int, default=34, help="without audio: speaker duty cycle of every opcode (4..66, even)")
+    ap.add_argument("--audio", help="16-bit PCM .wav: the clip's audio track")
+    ap.add_argument("--pcm", help="instead of --audio: .npy int16 (n_frames, channels) or (n_frames,), at --rate Hz")
+    ap.add_argument("--rate", type=int, help="sample rate of --pcm")
+    ap.add_argument("--normalization", type=float, default=None,
+                    help="Audio(normalization=); default: computed from the audio's first 10 MiB (audio.py:60-78)")
     ap.add_argument("--fourth", action="store_true", help="IIV_OPT_FOURTH_OFFSET (not the reference's stream)")
     ap.add_argument("--joint", action="store_true", help="IIV_CONTENT_JOINT (not the reference's stream)")
     ap.add_argument("--seed", type=int, default=1, help="random.seed / np.random.seed of the encoder's two nonce streams")
@@ -50,10 +58,15 @@ def main():
         ap.error("--tick: 4..66, even")
     if bool(a.frames) == bool(a.synthetic):
         ap.error("one of --frames / --synthetic")
+    if a.audio and a.pcm:
+        ap.error("one of --audio / --pcm")
+    if bool(a.pcm) != bool(a.rate):
+        ap.error("--pcm needs --rate (and --rate goes with --pcm)")
 
     import torch
     import _iiv_native as native
     import a2m
+    import audio
     import frame_grabber
     import palette
     import stream_batch
@@ -74,14 +87,27 @@ def main():
     batch = stream_batch.StreamBatch(mode, table, store, 1, seeds=[(a.seed, a.seed)], dm=dm, joint_content=a.joint, fourth_offset=a.fourth,
                                      input_frame_rate=grab.input_frame_rate)
     n = int(main_maps.shape[0])
-    ops, segs = batch.encode_frames(main_maps[None], aux_maps[None] if aux_maps is not None else None, n)
+    au = None
+    if a.audio or a.pcm:
+        if a.audio:
+            au = audio.Audio(a.audio, normalization=a.normalization)._array
+        else:
+            au = audio.ArrayAudio(np.load(a.pcm), a.rate, normalization=a.normalization)
+        audio_ticks = au.ticks()                                   # (1, n_ticks) on the device
+        max_ticks = au.tick_count()
+    else:
+        max_ticks = None
+    ops, segs = batch.encode_frames(main_maps[None], aux_maps[None] if aux_maps is not None else None, n, max_ticks=max_ticks)
     batch.enc.check()
     if a.dbg:
         addr = a2m.OpcodeAddresses.from_debug_file(a.dbg)
     else:
         print("no --dbg: placeholder opcode addresses -- the stream has the right layout but is NOT playable", file=sys.stderr)
         addr = a2m.OpcodeAddresses(0x8000 + 16 * np.arange(1024, dtype=np.uint16).reshape(32, 32), 0xc000, 0xc100)
-    ticks = torch.full((1, ops.shape[1]), a.tick, dtype=torch.uint8, device="cuda")
+    if au is None:
+        ticks = torch.full((1, ops.shape[1]), a.tick, dtype=torch.uint8, device="cuda")
+    else:
+        ticks = audio_ticks[:, :ops.shape[1]]                      # opcode k carries tick k (movie.py:67-111)
     stream = a2m.emit_stream(mode, ops, ticks, addr)
     data = stream[0].cpu().numpy().tobytes()
     torch.cuda.synchronize()
@@ -90,6 +116,10 @@ def main():
         f.write(data)
     n_ops = int(ops.shape[1])
     distinct = np.mean([len(set(r[2:6])) for r in ops[0].cpu().numpy().tolist()])
+    if au is not None:
+        print("audio: %d ticks at %d Hz from %d frames at %d Hz (%d channels, normalization %.6g); the movie ends with the %s" % (
+            max_ticks, au.bitrate, au.n_frames, au.rate, au.channels, au.normalization[0],
+            "audio" if n_ops >= max_ticks else "frames"))
     print("%d frames (%s, %s palette, dither %s) -> %d opcodes (%.2f distinct offsets each), %d generators -> %d bytes in %s" % (
         n, a.mode, a.palette, a.dither, n_ops, distinct, len(stream_batch.merge_generators(segs)), len(data), a.out))
     print("tables + ingest %.2f s, encode + emit %.3f s = %.0f frames/s for this one clip (many clips at once: bench.py)" % (
