@@ -1,0 +1,347 @@
+// iiv_resize.hip -- source frames -> 280x192 (any H x W up to 1024) on gfx950, byte-exact with Pillow's
+// Image.resize(..., LANCZOS): the step the reference applies to every decoded frame (frame_grabber.py:75,100).
+//
+// The contract (include/iivision.h: iiv_resize_coeffs / iiv_resize_frames):
+//   * per axis, float64 Lanczos-3 weights per output sample, normalised and rounded to 22-bit fixed point -- computed
+//     HERE ON THE HOST with libm sin, as Pillow computes them (a device sin may differ in the last ulp and flip a rounding);
+//   * a pass is out = clamp((2^21 + sum(pixel * k)) >> 22, 0, 255) in int32, each channel on its own -- integer
+//     multiply-adds only, so the order of the sum is free;
+//   * the horizontal pass first (vertical first when h > 100 w), the first pass's uint8 result feeding the second; an axis
+//     whose size does not change gets no pass.
+//
+// Form: two kernels, the first pass's uint8 result in a stream-ordered HBM scratch of frames_per_chunk frames, sized so a
+// chunk's intermediate (at most W / w of its source) stays in the Infinity Cache between the two launches.  Source
+// bytes cross HBM once.
+//   * resize_h_kernel: a workgroup per R source rows, one thread per output column.  The rows are read with aligned
+//     dword loads and a funnel shift (any byte stride), unpacked to one dword per pixel in LDS; each tap is then one
+//     coalesced coefficient load (the table is stored tap-major), R LDS reads and 3 R 24-bit multiply-adds.
+//   * resize_v_kernel: a workgroup per output row, one thread per four bytes of the row (the vertical pass does not care
+//     which byte is which channel); the row's coefficients are wave-uniform (scalar loads).
+// Coefficient tables are made once per (device, in, out) and kept for the life of the process.
+#include "iiv_host.h"
+
+#include <math.h>
+#include <map>
+#include <mutex>
+#include <tuple>
+#include <vector>
+
+namespace iiv {
+namespace {
+
+constexpr int kPrecisionBits = 22;
+constexpr int kMaxIn = 8192, kMaxOut = 1024;
+constexpr size_t kChunkMidBytes = 32u << 20;   // intermediate per chunk of frames (the Infinity Cache holds 256 MiB)
+
+double sinc(double x)
+{
+    if (x == 0.0) return 1.0;
+    x = x * M_PI;
+    return sin(x) / x;
+}
+
+double lanczos(double x) { return (-3.0 <= x && x < 3.0) ? sinc(x) * sinc(x / 3.0) : 0.0; }
+
+int ksize_of(int in_size, int out_size)
+{
+    double filterscale = (double)in_size / out_size;
+    if (filterscale < 1.0) filterscale = 1.0;
+    return (int)ceil(3.0 * filterscale) * 2 + 1;
+}
+
+// Pillow's precompute_coeffs + normalize_coeffs_8bpc (box = the whole axis): bounds [out][2] = (xmin, count), coeffs
+// [out][ksize], zero past count
+void make_coeffs(int in_size, int out_size, int ksize, int32_t *bounds, int32_t *coeffs)
+{
+    const double scale = (double)in_size / out_size;
+    const double filterscale = scale < 1.0 ? 1.0 : scale;
+    const double support = 3.0 * filterscale;
+    const double ss = 1.0 / filterscale;
+    std::vector<double> w((size_t)ksize);
+    for (int xx = 0; xx < out_size; xx++) {
+        const double center = (xx + 0.5) * scale;
+        int xmin = (int)(center - support + 0.5);
+        if (xmin < 0) xmin = 0;
+        int xmax = (int)(center + support + 0.5);
+        if (xmax > in_size) xmax = in_size;
+        xmax -= xmin;
+        double ww = 0.0;
+        for (int x = 0; x < xmax; x++) {
+            w[x] = lanczos((x + xmin - center + 0.5) * ss);
+            ww += w[x];
+        }
+        int32_t *k = coeffs + (size_t)xx * ksize;
+        for (int x = 0; x < ksize; x++) {
+            double v = x < xmax ? (ww != 0.0 ? w[x] / ww : w[x]) : 0.0;
+            k[x] = v < 0 ? (int32_t)(v * (1 << kPrecisionBits) - 0.5) : (int32_t)(v * (1 << kPrecisionBits) + 0.5);
+        }
+        bounds[2 * xx] = xmin;
+        bounds[2 * xx + 1] = xmax;
+    }
+}
+
+// one axis's tables on one device: bounds (xmin, count) per output sample, the coefficients out-major ([out][ksize]: the
+// vertical pass reads one row's taps) and tap-major ([ksize][out]: the horizontal pass's lanes read consecutive outputs)
+struct Table {
+    int ksize = 0;
+    int2 *bounds = nullptr;
+    int32_t *k_rows = nullptr, *k_taps = nullptr;
+};
+
+int get_table(int in_size, int out_size, const Table **out)
+{
+    static std::mutex mu;
+    static std::map<std::tuple<int, int, int>, Table> cache;
+    int dev = 0;
+    IIV_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    auto key = std::make_tuple(dev, in_size, out_size);
+    auto it = cache.find(key);
+    if (it != cache.end()) {
+        *out = &it->second;
+        return IIV_OK;
+    }
+    // first use of this size pair on this device: made on the host and uploaded synchronously
+    Table t;
+    t.ksize = ksize_of(in_size, out_size);
+    const size_t nk = (size_t)out_size * t.ksize;
+    std::vector<int32_t> b(2 * (size_t)out_size), k(nk), kt(nk);
+    make_coeffs(in_size, out_size, t.ksize, b.data(), k.data());
+    for (int o = 0; o < out_size; o++)
+        for (int j = 0; j < t.ksize; j++) kt[(size_t)j * out_size + o] = k[(size_t)o * t.ksize + j];
+    void *mem = nullptr;
+    const size_t bytes = b.size() * 4 + 2 * nk * 4;
+    IIV_HIP(hipMalloc(&mem, bytes));
+    t.bounds = (int2 *)mem;
+    t.k_rows = (int32_t *)((char *)mem + b.size() * 4);
+    t.k_taps = t.k_rows + nk;
+    int rc = hip_check(hipMemcpy(t.bounds, b.data(), b.size() * 4, hipMemcpyHostToDevice), "hipMemcpy(resize bounds)");
+    if (!rc) rc = hip_check(hipMemcpy(t.k_rows, k.data(), nk * 4, hipMemcpyHostToDevice), "hipMemcpy(resize coefficients)");
+    if (!rc) rc = hip_check(hipMemcpy(t.k_taps, kt.data(), nk * 4, hipMemcpyHostToDevice), "hipMemcpy(resize coefficients)");
+    if (rc) {
+        (void)hipFree(mem);
+        return rc;
+    }
+    *out = &(cache[key] = t);
+    return IIV_OK;
+}
+
+__device__ inline uint32_t clamp_shift(int32_t acc)
+{
+    acc >>= kPrecisionBits;
+    return (uint32_t)(acc < 0 ? 0 : (acc > 255 ? 255 : acc));
+}
+
+// the dword holding byte p and the next one, shifted so that byte p is byte 0 (p any address; `end` one past the last
+// byte that may be read).  Aligned dwords never cross a page, so the first load is safe whenever byte p is.
+__device__ inline uint32_t load_unaligned(const uint8_t *p, const uint8_t *end)
+{
+    const uintptr_t a = (uintptr_t)p & ~(uintptr_t)3;
+    const uint32_t s = (uint32_t)((uintptr_t)p & 3);
+    const uint32_t d0 = *(const uint32_t *)a;
+    const uint32_t d1 = (s && (const uint8_t *)(a + 4) < end) ? *(const uint32_t *)(a + 4) : 0u;
+    return __builtin_amdgcn_alignbyte(d1, d0, s);
+}
+
+// Horizontal pass: src rows (rows per frame, w pixels, byte strides) -> dst rows of W pixels (byte strides).  Workgroup =
+// R consecutive rows of one frame; threads = W rounded up to waves, one output pixel each.  LDS: R rows of w_pad dwords.
+template <int R>
+__global__ __launch_bounds__(1024) void resize_h_kernel(const uint8_t *__restrict__ src, size_t src_fs, size_t src_rs, int rows,
+                                                        int w, int W, const int2 *__restrict__ bounds,
+                                                        const int32_t *__restrict__ k_taps, uint8_t *__restrict__ dst,
+                                                        size_t dst_fs, size_t dst_rs)
+{
+    extern __shared__ uint32_t px[];   // [R][w_pad] pixels, r | g << 8 | b << 16
+    const int groups = (rows + R - 1) / R;
+    const int f = blockIdx.x / groups, r0 = (blockIdx.x % groups) * R;
+    const int w_pad = (w + 3) & ~3;
+    const int n4 = w_pad >> 2;
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        if (r0 + r >= rows) break;
+        const uint8_t *row = src + (size_t)f * src_fs + (size_t)(r0 + r) * src_rs;
+        const uint8_t *end = row + 3 * (size_t)w;
+        for (int g = threadIdx.x; g < n4; g += blockDim.x) {
+            // four pixels = twelve bytes from byte 12 g of the row
+            const uint8_t *p = row + 12 * (size_t)g;
+            const uintptr_t a = (uintptr_t)p & ~(uintptr_t)3;
+            const uint32_t s = (uint32_t)((uintptr_t)p & 3);
+            uint32_t d[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) d[j] = (const uint8_t *)(a + 4 * j) < end ? ((const uint32_t *)a)[j] : 0u;
+            const uint32_t e0 = __builtin_amdgcn_alignbyte(d[1], d[0], s), e1 = __builtin_amdgcn_alignbyte(d[2], d[1], s),
+                           e2 = __builtin_amdgcn_alignbyte(d[3], d[2], s);
+            uint4 q;
+            q.x = e0 & 0xffffffu;
+            q.y = (e0 >> 24) | ((e1 & 0xffffu) << 8);
+            q.z = (e1 >> 16) | ((e2 & 0xffu) << 16);
+            q.w = e2 >> 8;
+            *(uint4 *)&px[r * w_pad + 4 * g] = q;
+        }
+    }
+    __syncthreads();
+    const int x = threadIdx.x;
+    if (x >= W) return;
+    const int2 bd = bounds[x];
+    int32_t acc[R][3];
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r][0] = acc[r][1] = acc[r][2] = 1 << (kPrecisionBits - 1);
+    const uint32_t *pr = px + bd.x;
+    const int32_t *kp = k_taps + x;
+#pragma unroll 4
+    for (int j = 0; j < bd.y; j++) {
+        const int32_t c = kp[(size_t)j * W];
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const uint32_t v = pr[r * w_pad + j];
+            acc[r][0] += __mul24((int)(v & 0xffu), c);
+            acc[r][1] += __mul24((int)((v >> 8) & 0xffu), c);
+            acc[r][2] += __mul24((int)(v >> 16), c);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        if (r0 + r >= rows) break;
+        uint8_t *o = dst + (size_t)f * dst_fs + (size_t)(r0 + r) * dst_rs + 3 * (size_t)x;
+        o[0] = (uint8_t)clamp_shift(acc[r][0]);
+        o[1] = (uint8_t)clamp_shift(acc[r][1]);
+        o[2] = (uint8_t)clamp_shift(acc[r][2]);
+    }
+}
+
+// Vertical pass: src [frames][rows_in][row_bytes] (byte strides) -> dst [frames][H][row_bytes] (byte strides).  Workgroup
+// = one output row's `blocks_per_row`-th part; thread = four bytes of it.
+__global__ __launch_bounds__(256) void resize_v_kernel(const uint8_t *__restrict__ src, size_t src_fs, size_t src_rs,
+                                                       int row_bytes, int H, int blocks_per_row, const int2 *__restrict__ bounds,
+                                                       const int32_t *__restrict__ k_rows, int ksize, uint8_t *__restrict__ dst,
+                                                       size_t dst_fs, size_t dst_rs)
+{
+    const int bpr = blocks_per_row;
+    const int fy = blockIdx.x / bpr;
+    const int f = fy / H, y = fy % H;
+    const int j = ((blockIdx.x % bpr) * 256 + threadIdx.x) * 4;
+    if (j >= row_bytes) return;
+    const int2 bd = bounds[y];
+    const int32_t *k = k_rows + (size_t)y * ksize;
+    const uint8_t *col = src + (size_t)f * src_fs + (size_t)bd.x * src_rs + j;
+    int32_t a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0, a3 = a0;
+    for (int t = 0; t < bd.y; t++) {
+        const uint8_t *p = col + (size_t)t * src_rs;
+        const uint32_t v = load_unaligned(p, p - j + row_bytes);
+        const int32_t c = k[t];
+        a0 += __mul24((int)(v & 0xffu), c);
+        a1 += __mul24((int)((v >> 8) & 0xffu), c);
+        a2 += __mul24((int)((v >> 16) & 0xffu), c);
+        a3 += __mul24((int)(v >> 24), c);
+    }
+    const uint32_t out = clamp_shift(a0) | (clamp_shift(a1) << 8) | (clamp_shift(a2) << 16) | (clamp_shift(a3) << 24);
+    uint8_t *o = dst + (size_t)f * dst_fs + (size_t)y * dst_rs + j;
+    if (j + 4 <= row_bytes && ((uintptr_t)o & 3) == 0) {
+        *(uint32_t *)o = out;
+    } else {
+        const int nb = row_bytes - j < 4 ? row_bytes - j : 4;
+        for (int b = 0; b < nb; b++) o[b] = (uint8_t)(out >> (8 * b));
+    }
+}
+
+int launch_h(const uint8_t *src, size_t src_fs, size_t src_rs, int frames, int rows, int w, int W, const Table &t, uint8_t *dst,
+             size_t dst_fs, size_t dst_rs, hipStream_t st)
+{
+    const int threads = (W + 63) & ~63;
+    const int w_pad = (w + 3) & ~3;
+    if (w_pad <= 4096) {
+        const unsigned blocks = (unsigned)frames * (unsigned)((rows + 1) / 2);
+        hipLaunchKernelGGL(resize_h_kernel<2>, dim3(blocks), dim3(threads), (size_t)2 * w_pad * 4, st, src, src_fs, src_rs, rows, w,
+                           W, t.bounds, t.k_taps, dst, dst_fs, dst_rs);
+    } else {
+        const unsigned blocks = (unsigned)frames * (unsigned)rows;
+        hipLaunchKernelGGL(resize_h_kernel<1>, dim3(blocks), dim3(threads), (size_t)w_pad * 4, st, src, src_fs, src_rs, rows, w,
+                           W, t.bounds, t.k_taps, dst, dst_fs, dst_rs);
+    }
+    return hip_check(hipGetLastError(), "resize_h_kernel launch");
+}
+
+int launch_v(const uint8_t *src, size_t src_fs, size_t src_rs, int frames, int row_bytes, int H, const Table &t, uint8_t *dst,
+             size_t dst_fs, size_t dst_rs, hipStream_t st)
+{
+    const int bpr = (row_bytes + 1023) / 1024;
+    const unsigned blocks = (unsigned)frames * (unsigned)H * (unsigned)bpr;
+    hipLaunchKernelGGL(resize_v_kernel, dim3(blocks), dim3(256), 0, st, src, src_fs, src_rs, row_bytes, H, bpr, t.bounds, t.k_rows,
+                       t.ksize, dst, dst_fs, dst_rs);
+    return hip_check(hipGetLastError(), "resize_v_kernel launch");
+}
+
+}  // namespace
+}  // namespace iiv
+
+using namespace iiv;
+
+extern "C" int iiv_resize_coeffs(int in_size, int out_size, int *ksize, int32_t *bounds, int32_t *coeffs)
+{
+    if (in_size < 1 || in_size > kMaxIn || out_size < 1 || out_size > kMaxOut || !ksize)
+        return set_error(IIV_ERR_INVALID, "iiv_resize_coeffs: in_size 1..%d, out_size 1..%d, ksize not NULL (got %d, %d)", kMaxIn,
+                         kMaxOut, in_size, out_size);
+    *ksize = ksize_of(in_size, out_size);
+    if (!bounds && !coeffs) return IIV_OK;
+    if (!bounds || !coeffs) return set_error(IIV_ERR_INVALID, "iiv_resize_coeffs: bounds and coeffs both or neither NULL");
+    make_coeffs(in_size, out_size, *ksize, bounds, coeffs);
+    return IIV_OK;
+}
+
+extern "C" int iiv_resize_frames(int n, int h, int w, const uint8_t *d_src, size_t frame_stride, size_t row_stride, int H, int W,
+                                 uint8_t *d_dst, void *stream)
+{
+    if (n < 0 || h < 1 || h > kMaxIn || w < 1 || w > kMaxIn || H < 1 || H > kMaxOut || W < 1 || W > kMaxOut)
+        return set_error(IIV_ERR_INVALID, "iiv_resize_frames: n >= 0, h, w in 1..%d, H, W in 1..%d (got n %d, %dx%d -> %dx%d)", kMaxIn,
+                         kMaxOut, n, h, w, H, W);
+    if (n == 0) return IIV_OK;
+    const size_t src_row = 3 * (size_t)w, src_frame = (size_t)(h - 1) * row_stride + src_row;
+    if (!d_src || !d_dst || row_stride < (h > 1 ? src_row : 0) || (n > 1 && frame_stride < src_frame))
+        return set_error(IIV_ERR_INVALID, "iiv_resize_frames: d_src / d_dst NULL, or rows / frames overlap (row_stride %zu < %zu or "
+                         "frame_stride %zu < %zu)", row_stride, src_row, frame_stride, src_frame);
+    const hipStream_t st = (hipStream_t)stream;
+    const bool resize_w = W != w, resize_h = H != h;
+    const size_t dst_rs = 3 * (size_t)W, dst_fs = (size_t)H * dst_rs;
+    const Table *th = nullptr, *tv = nullptr;
+    int rc;
+    // (same size: Pillow copies; the vertical pass with the in == out table -- one unit tap per row -- is that copy)
+    if (resize_w && (rc = get_table(w, W, &th))) return rc;
+    if ((resize_h || !resize_w) && (rc = get_table(h, H, &tv))) return rc;
+    if (!(resize_w && resize_h)) {
+        // one pass, straight into d_dst, in slices of frames that keep the grid within range
+        const int step = 65536;
+        for (int f0 = 0; f0 < n; f0 += step) {
+            const int fn = n - f0 < step ? n - f0 : step;
+            const uint8_t *s = d_src + (size_t)f0 * frame_stride;
+            uint8_t *d = d_dst + (size_t)f0 * dst_fs;
+            rc = resize_w ? launch_h(s, frame_stride, row_stride, fn, h, w, W, *th, d, dst_fs, dst_rs, st)
+                          : launch_v(s, frame_stride, row_stride, fn, 3 * w, H, *tv, d, dst_fs, dst_rs, st);
+            if (rc) return rc;
+        }
+        return IIV_OK;
+    }
+    // two passes through a stream-ordered scratch: (h, W) after a horizontal first pass, (H, w) after a vertical one
+    const bool v_first = h > 100 * w;
+    const size_t mid_rs = ((v_first ? 3 * (size_t)w : 3 * (size_t)W) + 3) & ~(size_t)3;
+    const size_t mid_fs = (size_t)(v_first ? H : h) * mid_rs;
+    size_t chunk = kChunkMidBytes / mid_fs;
+    if (chunk < 1) chunk = 1;
+    if (chunk > 65536) chunk = 65536;
+    if (chunk > (size_t)n) chunk = (size_t)n;
+    uint8_t *mid = nullptr;
+    IIV_HIP(hipMallocAsync((void **)&mid, chunk * mid_fs, st));
+    for (int f0 = 0; f0 < n && !rc; f0 += (int)chunk) {
+        const int fn = n - f0 < (int)chunk ? n - f0 : (int)chunk;
+        const uint8_t *s = d_src + (size_t)f0 * frame_stride;
+        uint8_t *d = d_dst + (size_t)f0 * dst_fs;
+        if (v_first) {
+            rc = launch_v(s, frame_stride, row_stride, fn, 3 * w, H, *tv, mid, mid_fs, mid_rs, st);
+            if (!rc) rc = launch_h(mid, mid_fs, mid_rs, fn, H, w, W, *th, d, dst_fs, dst_rs, st);
+        } else {
+            rc = launch_h(s, frame_stride, row_stride, fn, h, w, W, *th, mid, mid_fs, mid_rs, st);
+            if (!rc) rc = launch_v(mid, mid_fs, mid_rs, fn, 3 * W, H, *tv, d, dst_fs, dst_rs, st);
+        }
+    }
+    const int rc_free = hip_check(hipFreeAsync(mid, st), "hipFreeAsync(resize scratch)");
+    return rc ? rc : rc_free;
+}

@@ -50,6 +50,7 @@ SYMBOLS = [
     "iiv_check_diff_weight_pieces",
     "iiv_emit_stream", "iiv_emit_chunk", "iiv_frames_to_memory_maps",
     "iiv_audio_tick_count", "iiv_audio_ticks", "iiv_audio_resample", "iiv_audio_normalization",
+    "iiv_resize_coeffs", "iiv_resize_frames",
 ]
 
 
@@ -169,13 +170,17 @@ def lib():
         L.iiv_audio_ticks.argtypes = [i32, vp, sz, vp, vp, vp, i32, lg, vp, vp, sz, vp, vp]
         L.iiv_audio_resample.argtypes = [i32, vp, sz, vp, vp, vp, i32, vp, sz, vp, vp]
         L.iiv_audio_normalization.argtypes = [i32, vp, sz, vp, vp, vp, i32, vp, vp]
+    if hasattr(L, "iiv_resize_frames") or "IIV_LIB" not in os.environ:
+        L.iiv_resize_coeffs.argtypes = [i32, i32, C.POINTER(C.c_int), vp, vp]
+        L.iiv_resize_frames.argtypes = [i32, i32, i32, vp, sz, sz, i32, i32, vp, vp]
     if hasattr(L, "iiv_encoder_launch_forms") or "IIV_LIB" not in os.environ:
         L.iiv_encoder_launch_forms.argtypes = [vp, C.POINTER(C.c_int64)]
     for name in SYMBOLS:
         if "IIV_LIB" in os.environ and name in ("iiv_encoder_launch_forms", "iiv_check_diff_weight_pieces", "iiv_encoder_info", "iiv_encoder_get_video_brief_async",
                                                  "iiv_encoder_live_queue", "iiv_encode_live", "iiv_encoder_set_state_async",
                                                  "iiv_audio_tick_count", "iiv_audio_ticks", "iiv_audio_resample",
-                                                 "iiv_audio_normalization") and not hasattr(L, name):
+                                                 "iiv_audio_normalization", "iiv_resize_coeffs",
+                                                 "iiv_resize_frames") and not hasattr(L, name):
             continue   # (an older build under IIV_LIB: tools/ab_libs.sh)
         getattr(L, name)  # AttributeError if the library lacks a declared symbol
     _lib = L
@@ -834,4 +839,42 @@ def audio_normalization(pcm, n_frames, channels, rate, bitrate=AUDIO_BITRATE):
     out = np.zeros(S, dtype=np.float64)
     check(lib().iiv_audio_normalization(S, dptr(pcm), int(pcm.stride(0)), hptr(nf), hptr(ch), hptr(rt), int(bitrate),
                                         hptr(out), stream_ptr()))
+    return out
+
+
+# ---- f5: the resize -----------------------------------------------------------------
+
+RESIZE_SIZE = (192, 280)   # (H, W): frame_grabber.py:75,100 resize((280, 192), resample=Image.LANCZOS)
+
+
+def resize_coeffs(in_size, out_size):
+    """The Lanczos coefficient table of one axis, in_size -> out_size samples, as Pillow builds it.  Host only ->
+    (bounds int32 (out, 2) = (first input sample, taps used), coefficients int32 (out, ksize) in 22-bit fixed point)."""
+    ks = C.c_int(0)
+    check(lib().iiv_resize_coeffs(int(in_size), int(out_size), C.byref(ks), None, None))
+    bounds = np.zeros((int(out_size), 2), np.int32)
+    k = np.zeros((int(out_size), ks.value), np.int32)
+    check(lib().iiv_resize_coeffs(int(in_size), int(out_size), C.byref(ks), hptr(bounds), hptr(k)))
+    return bounds, k
+
+
+def resize_frames(rgb, size=RESIZE_SIZE, out=None):
+    """Image.resize((W, H), LANCZOS) of every frame, byte-exact: rgb CUDA uint8 (n, h, w, 3) with unit channel stride and
+    pixel stride 3 (any frame and row strides: a crop or a letterbox cut is passed as a view) -> CUDA uint8 (n, H, W, 3).
+    out: a contiguous CUDA uint8 tensor of n * H * W * 3 bytes to write into.  Asynchronous on torch's current stream once a
+    size pair has been used on the device (the first call with it uploads its coefficient tables and synchronises); `rgb`
+    and `out` must stay alive and untouched until that stream has reached this call (as for frames_to_memory_maps)."""
+    torch = _torch()
+    H, W = (int(v) for v in size)
+    if not (rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 4 and rgb.shape[3] == 3 and rgb.stride(3) == 1
+            and rgb.stride(2) == 3):
+        raise ValueError("rgb must be a CUDA uint8 tensor (n, h, w, 3) with channel stride 1 and pixel stride 3")
+    n, h, w = (int(v) for v in rgb.shape[:3])
+    if out is None:
+        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=rgb.device)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n * H * W * 3):
+        raise ValueError("out must be a contiguous CUDA uint8 tensor of n * %d * %d * 3 bytes" % (H, W))
+    with torch.cuda.device(rgb.device):
+        check(lib().iiv_resize_frames(n, h, w, dptr(rgb), int(rgb.stride(0)), int(rgb.stride(1)), H, W, dptr(out),
+                                      stream_ptr()))
     return out

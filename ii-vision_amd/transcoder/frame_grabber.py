@@ -7,9 +7,10 @@ Mirrors the interface of the reference's transcoder/frame_grabber.py: FrameGrabb
 
 What differs, and why: the reference decodes with ffmpeg, resizes each frame to 280x192 with
 PIL (frame_grabber.py:75,100) and shells out to the external tool /usr/local/bin/bmp2dhr for
-the image -> memory-map conversion (frame_grabber.py:78-82,103-108).  Decoding and resizing
-stay out of scope (they are not on the transcode hot path); the conversion itself is row f3
-of SURVEY 8f and runs here as a HIP kernel (csrc/iiv_ingest.hip).  bmp2dhr is not part of the
+the image -> memory-map conversion (frame_grabber.py:78-82,103-108).  Decoding stays out of
+scope; the resize runs on the device, byte-exact with Pillow's LANCZOS (csrc/iiv_resize.hip,
+ArrayFrameGrabber(..., resize=True)); the conversion itself is row f3 of SURVEY 8f and runs
+here as a HIP kernel (csrc/iiv_ingest.hip).  bmp2dhr is not part of the
 reference's source, so its output cannot be matched: the conversion is specified in
 include/iivision.h (iiv_frames_to_memory_maps) and the tests hold the kernel to it.
 """
@@ -38,15 +39,21 @@ class FrameGrabber:
 
 class ArrayFrameGrabber(FrameGrabber):
     """Frames given as an array (n, 192, 280, 3) uint8 -- what FileFrameGrabber holds after its
-    resize -- converted `batch` frames at a time by iiv_frames_to_memory_maps."""
+    resize -- converted `batch` frames at a time by iiv_frames_to_memory_maps.  With resize=True the
+    frames may be any size (n, h, w, 3) (1 <= h, w <= 8192): each is resized to 280x192 on the device
+    first, byte for byte as the reference's Image.resize((280, 192), LANCZOS) (frame_grabber.py:75,100)."""
 
     def __init__(self, frames_rgb, mode: VideoMode, palette: Palette = Palette.NTSC, dither: int = 32,
-                 input_frame_rate: float = 30, batch: int = 256):
+                 input_frame_rate: float = 30, batch: int = 256, resize: bool = False):
         super().__init__(mode)
         rgb = np.asarray(frames_rgb)
-        if rgb.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[1:] != (192, 280, 3):
+        if resize:
+            if rgb.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[3] != 3:
+                raise ValueError("frames must be uint8 (n, h, w, 3) RGB")
+        elif rgb.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[1:] != (192, 280, 3):
             raise ValueError("frames must be uint8 (n, 192, 280, 3) (frame_grabber.py:75: 280x192 RGB)")
         self._rgb = rgb
+        self.resize = bool(resize)
         self.palette = palette
         # 0..255: amplitude of the 4x4 ordered dither; "diffusion" (= native.DITHER_DIFFUSION): Floyd-Steinberg error
         # diffusion, the kind of dither the reference asks bmp2dhr for (D9, frame_grabber.py:80-82,106-108)
@@ -60,6 +67,8 @@ class ArrayFrameGrabber(FrameGrabber):
         import torch
         count = len(self._rgb) - first if count is None else count
         rgb = torch.from_numpy(np.ascontiguousarray(self._rgb[first:first + count])).cuda()
+        if self.resize and tuple(rgb.shape[1:3]) != native.RESIZE_SIZE:
+            rgb = native.resize_frames(rgb)   # on the same stream as the conversion below
         mode = native.DHGR if self.video_mode == VideoMode.DHGR else native.HGR
         pal = palette_mod.PALETTES[self.palette].rgb_array()
         return native.frames_to_memory_maps(mode, pal, rgb, self.dither)

@@ -545,6 +545,35 @@ int iiv_audio_resample(int n_streams, const int16_t *d_pcm, size_t pcm_stride, c
 int iiv_audio_normalization(int n_streams, const int16_t *d_pcm, size_t pcm_stride, const long *n_frames, const int *channels,
                             const int *rate, int bitrate, double *normalization, void *stream);
 
+/* ==== f5: the resize ========================================================
+ * frame_grabber.py:75,100 (`_frame.resize((280, 192), resample=Image.LANCZOS)`): every decoded frame is resized to
+ * 280x192 before anything else.  Byte-exact with Pillow's Image.resize(..., LANCZOS) of a uint8 RGB image (DESIGN.md 11;
+ * pinned against Pillow 12.2.0 -- the reference pins 9.4.0, whose fixed-point core is assumed to be the same):
+ *   - per axis (in -> out samples): scale = in / out, filterscale = max(scale, 1), support = 3 filterscale,
+ *     ksize = 2 ceil(support) + 1; output xx: center = (xx + 0.5) scale, xmin = max((int)(center - support + 0.5), 0),
+ *     count = min((int)(center + support + 0.5), in) - xmin, w[x] = lanczos((x + xmin - center + 0.5) * (1 / filterscale))
+ *     for x < count, lanczos(x) = sinc(x) sinc(x / 3) on [-3, 3), all float64 with libm sin; the weights are divided by
+ *     their sum (summed in order; when it is non-zero) and rounded to k = (int)(w 2^22 +- 0.5) (the sign of w);
+ *   - a pass: out = clamp((2^21 + sum_x pixel[xmin + x] k[x]) >> 22, 0, 255) in int32, each channel on its own;
+ *   - (h, w) == (H, W): a copy; one axis changed: one pass; otherwise the horizontal pass first -- the vertical one first
+ *     when h > 100 w (the installed Pillow's rule) -- and the uint8 result of the first pass feeds the second.
+ * Coefficients are computed on the host; the device only multiplies and adds integers (csrc/iiv_resize.hip). */
+
+/* The coefficient table of one axis (frame_grabber.py:75,100), host only (no device): *ksize receives the taps per
+ * output sample; bounds [out_size][2] = (xmin, count), coeffs [out_size][*ksize] fixed-point, zero past count.
+ * bounds == coeffs == NULL: only *ksize (size query).  in_size 1..8192, out_size 1..1024, else IIV_ERR_INVALID. */
+int iiv_resize_coeffs(int in_size, int out_size, int *ksize, int32_t *bounds, int32_t *coeffs);
+
+/* Resize n frames (frame_grabber.py:75,100): d_src frame f, row y, pixel x, channel c at
+ * d_src + f * frame_stride + y * row_stride + 3 x + c (byte strides: a crop, a letterbox cut or a strided view needs no
+ * copy; rows and frames must not overlap) -> d_dst [n][H][W][3] contiguous.  1 <= h, w <= 8192, 1 <= H, W <= 1024, else
+ * IIV_ERR_INVALID before anything is launched.  No alignment is required.  The coefficient tables are kept per (device,
+ * in, out) for the life of the process: the FIRST call with a size pair on a device builds and uploads them synchronously;
+ * every later call is asynchronous on `stream` (its scratch is allocated and freed stream-ordered), so d_src and d_dst must
+ * stay alive and untouched until `stream` has reached the call. */
+int iiv_resize_frames(int n, int h, int w, const uint8_t *d_src, size_t frame_stride, size_t row_stride, int H, int W,
+                      uint8_t *d_dst, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,8 +10,9 @@ cycle (`--tick`, 4..66 even: movie.py:104-107).
     python tools/transcode_clip.py --synthetic 90 --out /tmp/bars.a2m            # a moving test card
     python tools/transcode_clip.py --frames clip.npy --audio clip.wav --out clip.a2m
 
---frames: uint8 array (n, 192, 280, 3), i.e. what the reference's FileFrameGrabber holds after its resize
-(frame_grabber.py:75).  --dbg: the player's cc65 debug file, from which the opcode entry points are read exactly as
+--frames: uint8 array (n, h, w, 3) of any size (1 <= h, w <= 8192): frames that are not 280x192 are resized on the
+device, byte for byte as the reference's Image.resize((280, 192), LANCZOS) (frame_grabber.py:75,100; csrc/iiv_resize.hip);
+a (n, 192, 280, 3) array is taken as it is.  --dbg: the player's cc65 debug file, from which the opcode entry points are read exactly as
 opcodes._parse_symbol_table does (opcodes.py:168-185); without it the stream is written with placeholder addresses
 and is NOT playable (the tool says so).  --fourth / --joint: the two optional quality modes."""
 import argparse
@@ -37,7 +38,7 @@ def test_card(n):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--frames", help=".npy file, uint8 (n, 192, 280, 3)")
+    ap.add_argument("--frames", help=".npy file, uint8 (n, h, w, 3); resized to 280x192 on the device when not that size")
     ap.add_argument("--synthetic", type=int, default=0, help="instead of --frames: this many frames of a moving test card")
     ap.add_argument("--out", required=True)
     ap.add_argument("--mode", choices=["DHGR", "HGR"], default="DHGR")
@@ -77,7 +78,7 @@ def main():
     pal_id = palette.Palette.NTSC if a.palette == "NTSC" else palette.Palette.IIGS
     t0 = time.perf_counter()
     grab = frame_grabber.ArrayFrameGrabber(rgb, video_mode.VideoMode[a.mode], pal_id,
-                                           dither=a.dither if a.dither == "diffusion" else int(a.dither))
+                                           dither=a.dither if a.dither == "diffusion" else int(a.dither), resize=True)
     main_maps, aux_maps = grab.memory_maps()                       # (n, 32, 256) on the device
     _, dm = native.cie2000_matrix(palette.PALETTES[pal_id].rgb_array())
     table = native.build_table(mode, dm, True)
