@@ -244,31 +244,51 @@ __global__ __launch_bounds__(256) void resize_v_kernel(const uint8_t *__restrict
     }
 }
 
+// One launch holds at most 2^32 - 1 work-items in x (and 2^31 - 1 workgroups): frames beyond that go in further launches.
+// (1x1 -> 1024x1 is 1024 workgroups of 256 a frame: 16383 frames a launch.)
+int frames_per_launch(size_t blocks_per_frame, size_t threads)
+{
+    const size_t by_items = 0xffffffffu / (blocks_per_frame * threads), by_blocks = 0x7fffffffu / blocks_per_frame;
+    const size_t f = by_items < by_blocks ? by_items : by_blocks;
+    return f < 1 ? 1 : (f > 0x7fffffff ? 0x7fffffff : (int)f);
+}
+
 int launch_h(const uint8_t *src, size_t src_fs, size_t src_rs, int frames, int rows, int w, int W, const Table &t, uint8_t *dst,
              size_t dst_fs, size_t dst_rs, hipStream_t st)
 {
     const int threads = (W + 63) & ~63;
     const int w_pad = (w + 3) & ~3;
-    if (w_pad <= 4096) {
-        const unsigned blocks = (unsigned)frames * (unsigned)((rows + 1) / 2);
-        hipLaunchKernelGGL(resize_h_kernel<2>, dim3(blocks), dim3(threads), (size_t)2 * w_pad * 4, st, src, src_fs, src_rs, rows, w,
-                           W, t.bounds, t.k_taps, dst, dst_fs, dst_rs);
-    } else {
-        const unsigned blocks = (unsigned)frames * (unsigned)rows;
-        hipLaunchKernelGGL(resize_h_kernel<1>, dim3(blocks), dim3(threads), (size_t)w_pad * 4, st, src, src_fs, src_rs, rows, w,
-                           W, t.bounds, t.k_taps, dst, dst_fs, dst_rs);
+    const int R = w_pad <= 4096 ? 2 : 1;
+    const unsigned bpf = (unsigned)((rows + R - 1) / R);
+    const int step = frames_per_launch(bpf, (size_t)threads);
+    for (int f0 = 0; f0 < frames; f0 += step) {
+        const int fn = frames - f0 < step ? frames - f0 : step;
+        const uint8_t *s = src + (size_t)f0 * src_fs;
+        uint8_t *d = dst + (size_t)f0 * dst_fs;
+        if (R == 2)
+            hipLaunchKernelGGL(resize_h_kernel<2>, dim3((unsigned)fn * bpf), dim3(threads), (size_t)2 * w_pad * 4, st, s, src_fs,
+                               src_rs, rows, w, W, t.bounds, t.k_taps, d, dst_fs, dst_rs);
+        else
+            hipLaunchKernelGGL(resize_h_kernel<1>, dim3((unsigned)fn * bpf), dim3(threads), (size_t)w_pad * 4, st, s, src_fs,
+                               src_rs, rows, w, W, t.bounds, t.k_taps, d, dst_fs, dst_rs);
+        if (int rc = hip_check(hipGetLastError(), "resize_h_kernel launch")) return rc;
     }
-    return hip_check(hipGetLastError(), "resize_h_kernel launch");
+    return IIV_OK;
 }
 
 int launch_v(const uint8_t *src, size_t src_fs, size_t src_rs, int frames, int row_bytes, int H, const Table &t, uint8_t *dst,
              size_t dst_fs, size_t dst_rs, hipStream_t st)
 {
     const int bpr = (row_bytes + 1023) / 1024;
-    const unsigned blocks = (unsigned)frames * (unsigned)H * (unsigned)bpr;
-    hipLaunchKernelGGL(resize_v_kernel, dim3(blocks), dim3(256), 0, st, src, src_fs, src_rs, row_bytes, H, bpr, t.bounds, t.k_rows,
-                       t.ksize, dst, dst_fs, dst_rs);
-    return hip_check(hipGetLastError(), "resize_v_kernel launch");
+    const unsigned bpf = (unsigned)H * (unsigned)bpr;
+    const int step = frames_per_launch(bpf, 256);
+    for (int f0 = 0; f0 < frames; f0 += step) {
+        const int fn = frames - f0 < step ? frames - f0 : step;
+        hipLaunchKernelGGL(resize_v_kernel, dim3((unsigned)fn * bpf), dim3(256), 0, st, src + (size_t)f0 * src_fs, src_fs, src_rs,
+                           row_bytes, H, bpr, t.bounds, t.k_rows, t.ksize, dst + (size_t)f0 * dst_fs, dst_fs, dst_rs);
+        if (int rc = hip_check(hipGetLastError(), "resize_v_kernel launch")) return rc;
+    }
+    return IIV_OK;
 }
 
 }  // namespace
