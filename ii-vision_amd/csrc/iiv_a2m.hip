@@ -110,8 +110,9 @@ int emit_stream(int mode, int n_streams, long n_ops, const uint8_t *d_ops, const
     if (out_len) *out_len = total;
     if (!d_out) return IIV_OK;  // size query
     if (out_stride < total) return set_error(IIV_ERR_INVALID, "iiv_emit_stream: out_stride %zu < %zu", out_stride, total);
-    uint16_t *d_addr = nullptr;
-    IIV_HIP(hipMalloc(&d_addr, 1024 * sizeof(uint16_t) + sizeof(int)));
+    DeviceBuf<uint16_t> addr;   // the tick addresses, then the error flag
+    if (int rc = addr.alloc(1024 + sizeof(int) / sizeof(uint16_t), "hipMalloc(tick addresses)")) return rc;
+    uint16_t *d_addr = addr;
     int *d_err = reinterpret_cast<int *>(d_addr + 1024);
     int h_err = 0;
     int rc = hip_check(hipMemcpyAsync(d_addr, tick_addr, 1024 * sizeof(uint16_t), hipMemcpyHostToDevice, st), "copy addr");
@@ -124,8 +125,7 @@ int emit_stream(int mode, int n_streams, long n_ops, const uint8_t *d_ops, const
         rc = hip_check(hipGetLastError(), "emit_kernel launch");
     }
     if (!rc) rc = hip_check(hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, st), "read flag");
-    if (!rc) rc = hip_check(hipStreamSynchronize(st), "emit sync");  // tick_addr is caller memory; d_addr freed below
-    (void)hipFree(d_addr);
+    if (!rc) rc = hip_check(hipStreamSynchronize(st), "emit sync");  // tick_addr is caller memory; d_addr is freed on return
     if (!rc && h_err)
         rc = set_error(IIV_ERR_INVALID, "iiv_emit_stream: a tick is not an even number in 4..66, or a page is outside 32..63");
     return rc;

@@ -651,8 +651,8 @@ int iiv_audio_normalization(int n_streams, const int16_t *d_pcm, size_t pcm_stri
         mx = ns[s] > mx ? ns[s] : mx;
     }
     // the prefixes, decoded as one block each (audio.py:67), side by side: stream s at y + off[s]
-    float *d_y = nullptr;
-    IIV_HIP(hipMalloc(&d_y, sizeof(float) * (size_t)total));
+    DeviceBuf<float> d_y;
+    if ((rc = d_y.alloc((size_t)total, "hipMalloc(prefixes)"))) return rc;
     std::map<std::pair<long, long>, std::vector<Job>> groups;
     std::map<long, std::vector<Job>> identity;
     for (int s = 0; s < n_streams; s++) {
@@ -678,41 +678,33 @@ int iiv_audio_normalization(int n_streams, const int16_t *d_pcm, size_t pcm_stri
             frac[s * 2 + h] = vi - (double)lo;
         }
     }
-    uint32_t *d_sel = nullptr;   // [hist n*1024][prefix n*4][rank n*4]
-    float *d_val = nullptr;
-    long *d_meta = nullptr;      // [off n][len n]
+    DeviceBuf<uint32_t> d_sel;   // [hist n*1024][prefix n*4][rank n*4]
+    DeviceBuf<float> d_val;
+    DeviceBuf<long> d_meta;      // [off n][len n]
     std::vector<float> val(4 * (size_t)n_streams);
-    do {
-        if (rc) break;
-        if ((rc = hip_check(hipMalloc(&d_sel, sizeof(uint32_t) * (size_t)n_streams * 1032), "hipMalloc(select)"))) break;
-        if ((rc = hip_check(hipMalloc(&d_val, sizeof(float) * 4 * (size_t)n_streams), "hipMalloc(select values)"))) break;
-        std::vector<long> meta(2 * (size_t)n_streams);
-        for (int s = 0; s < n_streams; s++) meta[s] = off[s], meta[n_streams + s] = ns[s];
-        if ((rc = hip_check(hipMalloc(&d_meta, sizeof(long) * 2 * (size_t)n_streams), "hipMalloc(select meta)"))) break;
-        uint32_t *hist = d_sel, *prefix = d_sel + (size_t)n_streams * 1024, *drank = prefix + (size_t)n_streams * 4;
-        if ((rc = hip_check(hipMemsetAsync(d_sel, 0, sizeof(uint32_t) * (size_t)n_streams * 1028, st), "hipMemsetAsync"))) break;
-        if ((rc = hip_check(hipMemcpyAsync(drank, rank.data(), sizeof(uint32_t) * 4 * n_streams, hipMemcpyHostToDevice, st), "copy ranks"))) break;
-        if ((rc = hip_check(hipMemcpyAsync(d_meta, meta.data(), sizeof(long) * 2 * n_streams, hipMemcpyHostToDevice, st), "copy meta"))) break;
-        unsigned gx = (unsigned)((mx + 255) / 256);
-        gx = gx > 1024 ? 1024 : gx;
-        for (int shift = 24; shift >= 0 && !rc; shift -= 8) {
-            hipLaunchKernelGGL(select_hist_kernel, dim3(gx, (unsigned)n_streams), dim3(256), 0, st, d_y, d_meta, d_meta + n_streams,
-                               prefix, shift, hist);
-            hipLaunchKernelGGL(select_pick_kernel, dim3((unsigned)((4 * n_streams + 63) / 64)), dim3(64), 0, st, n_streams, shift,
-                               hist, prefix, drank);
-            rc = hip_check(hipGetLastError(), "select kernels");
-        }
-        if (rc) break;
-        hipLaunchKernelGGL(select_values_kernel, dim3((unsigned)((4 * n_streams + 63) / 64)), dim3(64), 0, st, 4 * n_streams, prefix, d_val);
-        if ((rc = hip_check(hipGetLastError(), "select_values_kernel"))) break;
-        if ((rc = hip_check(hipMemcpyAsync(val.data(), d_val, sizeof(float) * 4 * n_streams, hipMemcpyDeviceToHost, st), "copy values"))) break;
-        rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
-    } while (0);
-    (void)hipFree(d_meta);
-    (void)hipFree(d_sel);
-    (void)hipFree(d_val);
-    (void)hipFree(d_y);
     if (rc) return rc;
+    if ((rc = d_sel.alloc((size_t)n_streams * 1032, "hipMalloc(select)"))) return rc;
+    if ((rc = d_val.alloc(4 * (size_t)n_streams, "hipMalloc(select values)"))) return rc;
+    std::vector<long> meta(2 * (size_t)n_streams);
+    for (int s = 0; s < n_streams; s++) meta[s] = off[s], meta[n_streams + s] = ns[s];
+    if ((rc = d_meta.alloc(2 * (size_t)n_streams, "hipMalloc(select meta)"))) return rc;
+    uint32_t *hist = d_sel, *prefix = d_sel + (size_t)n_streams * 1024, *drank = prefix + (size_t)n_streams * 4;
+    if ((rc = hip_check(hipMemsetAsync(d_sel, 0, sizeof(uint32_t) * (size_t)n_streams * 1028, st), "hipMemsetAsync"))) return rc;
+    if ((rc = hip_check(hipMemcpyAsync(drank, rank.data(), sizeof(uint32_t) * 4 * n_streams, hipMemcpyHostToDevice, st), "copy ranks"))) return rc;
+    if ((rc = hip_check(hipMemcpyAsync(d_meta, meta.data(), sizeof(long) * 2 * n_streams, hipMemcpyHostToDevice, st), "copy meta"))) return rc;
+    unsigned gx = (unsigned)((mx + 255) / 256);
+    gx = gx > 1024 ? 1024 : gx;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        hipLaunchKernelGGL(select_hist_kernel, dim3(gx, (unsigned)n_streams), dim3(256), 0, st, d_y.get(), d_meta.get(), d_meta + n_streams,
+                           prefix, shift, hist);
+        hipLaunchKernelGGL(select_pick_kernel, dim3((unsigned)((4 * n_streams + 63) / 64)), dim3(64), 0, st, n_streams, shift,
+                           hist, prefix, drank);
+        if ((rc = hip_check(hipGetLastError(), "select kernels"))) return rc;
+    }
+    hipLaunchKernelGGL(select_values_kernel, dim3((unsigned)((4 * n_streams + 63) / 64)), dim3(64), 0, st, 4 * n_streams, prefix, d_val.get());
+    if ((rc = hip_check(hipGetLastError(), "select_values_kernel"))) return rc;
+    if ((rc = hip_check(hipMemcpyAsync(val.data(), d_val, sizeof(float) * 4 * n_streams, hipMemcpyDeviceToHost, st), "copy values"))) return rc;
+    if ((rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize"))) return rc;   // (the owners free behind it)
     for (int s = 0; s < n_streams; s++) {
         double m = 0.0;
         for (int h = 0; h < 2; h++) {

@@ -25,6 +25,7 @@
 #include "iiv_wave.h"
 
 #include <stdlib.h>
+#include <memory>
 #include <vector>
 
 namespace iiv {
@@ -65,71 +66,81 @@ struct GenState {
 constexpr int kSmallSlots = 4;          // iiv_encoder_set_state_async's staging ring
 constexpr size_t kSmallBytes = 2560;    // >= 625 words
 
+// Every device buffer, pinned buffer and event is held by its owner (iiv_host.h), every plain field starts at the value
+// written here: destroying the object releases everything.
 struct Encoder {
-    int mode;
-    int n_streams;
-    const uint16_t *d_table;
-    const uint16_t *d_store;
-    uint32_t *d_left, *d_right;  // split store table (iiv_stream.h), built at creation when dm is given
-    NarrowTables nt;             // the narrow form of the split store table the greedy kernels read (iiv_stream.h)
-    uint32_t *d_dwl, *d_dwr;     // split diff-weight table, likewise
-    uint32_t *d_left_t, *d_right_t;  // split store table, content innermost (IIV_CONTENT_JOINT_SPLIT; built on first use)
-    uint32_t *d_joint_l, *d_joint_r; // narrow form, content innermost, two byte values per word (IIV_CONTENT_JOINT; built on first use)
-    void *d_brief;                   // iiv_encoder_get_video_brief's staging struct
-    ulonglong2 *d_strings;  // colour string of every masked value (recurrence mode)
-    uint32_t *d_hgr_dots;   // HGR: the window -> dots lookups the prologue copies into LDS (iiv_edit.h: hgr_dot_slot_lo)
-    uint32_t *d_dw_pieces;  // the diff weights' pair-term table the prologue copies into LDS (iiv_tables.hip: dw_piece_kernel)
-    uint16_t *d_sub;        // 16x16 substitute costs
-    int dw_mode;            // IIV_DW_TABLE / IIV_DW_RECURRENCE
-    int greedy_mode;        // IIV_GREEDY_WAVE / IIV_GREEDY_WORKGROUP / IIV_GREEDY_AUTO
-    int partial_sort;       // allow the prologue's prefix sort when the budget is known
-    int greedy_lds_pad;     // IIV_OPT_GREEDY_LDS_PAD
-    int content_choice;     // IIV_OPT_CONTENT_CHOICE
-    int fourth_offset;      // IIV_OPT_FOURTH_OFFSET
-    StreamState *d_states;
-    StreamState *d_snapshot[2];  // iiv_encoder_snapshot copies (lazily allocated; slot 1: iiv_encoder_snapshot_slot)
+    int mode = 0;
+    int n_streams = 0;
+    const uint16_t *d_table = nullptr;   // the caller's
+    const uint16_t *d_store = nullptr;
+    DeviceBuf<uint32_t> d_left, d_right;  // split store table (iiv_stream.h), built at creation when dm is given
+    NarrowTables nt{};                    // the narrow form of the split store table the greedy kernels read (iiv_stream.h) ...
+    DeviceBuf<uint8_t> nt_storage;        // ... and the allocation it points into
+    DeviceBuf<uint32_t> d_dwl, d_dwr;     // split diff-weight table, likewise (IIV_DW_SPLIT; built on first use)
+    DeviceBuf<uint32_t> d_left_t, d_right_t;  // split store table, content innermost (IIV_CONTENT_JOINT_SPLIT; built on first use)
+    DeviceBuf<uint32_t> d_joint_l, d_joint_r; // narrow form, content innermost, two byte values per word (IIV_CONTENT_JOINT; built on first use)
+    DeviceBuf<iiv_video_brief> d_brief;       // iiv_encoder_get_video_brief's staging struct
+    DeviceBuf<ulonglong2> d_strings;  // colour string of every masked value (recurrence mode)
+    DeviceBuf<uint32_t> d_hgr_dots;   // HGR: the window -> dots lookups the prologue copies into LDS (iiv_edit.h: hgr_dot_slot_lo)
+    DeviceBuf<uint32_t> d_dw_pieces;  // the diff weights' pair-term table the prologue copies into LDS (iiv_tables.hip: dw_piece_kernel)
+    DeviceBuf<uint16_t> d_sub;        // 16x16 substitute costs
+    int dw_mode = IIV_DW_TABLE;       // IIV_DW_TABLE / IIV_DW_RECURRENCE (the default when dm is given)
+    int greedy_mode = IIV_GREEDY_AUTO;   // IIV_GREEDY_WAVE / IIV_GREEDY_WORKGROUP / IIV_GREEDY_AUTO
+    int partial_sort = 1;             // allow the prologue's prefix sort when the budget is known
+    int greedy_lds_pad = 0;           // IIV_OPT_GREEDY_LDS_PAD
+    int content_choice = IIV_CONTENT_TARGET;   // IIV_OPT_CONTENT_CHOICE
+    int fourth_offset = 0;            // IIV_OPT_FOURTH_OFFSET
+    DeviceBuf<StreamState> d_states;
+    DeviceBuf<StreamState> d_snapshot[2];  // iiv_encoder_snapshot copies (lazily allocated; slot 1: iiv_encoder_snapshot_slot)
     // iiv_encoder_set_state_async: a small ring of pinned staging slots (one allocation), an event behind each slot's copies
-    uint8_t *h_small[1];
-    hipEvent_t small_ev[4];
-    int small_slot;
+    HostBuf<uint8_t> h_small;
+    Event small_ev[kSmallSlots];
+    int small_slot = 0;
     // live hand-over (iiv_encode_live): two opcode queues in coherent host memory (lazily allocated), and the one / the tag
     // the launches of the call in progress write to (NULL outside such a call)
-    unsigned long long *h_live[2], *d_live[2], *live_now;   // (d_live: the same memory as the device addresses it)
-    uint32_t live_tag;
+    HostBuf<unsigned long long> h_live[2];
+    unsigned long long *d_live[2] = {nullptr, nullptr}, *live_now = nullptr;   // (d_live: the same memory as the device addresses it)
+    uint32_t live_tag = 0;
     // generator bookkeeping: one entry while every stream has run the same schedule, else one per stream
-    std::vector<GenState> gens, snap_gens[2];
+    std::vector<GenState> gens{GenState{0, 0, 0}}, snap_gens[2];
     // launch descriptors: pinned staging ring -> device buffer, both grown on demand
-    LaunchSeg *h_segs[2];
-    hipEvent_t seg_ev[2];
-    size_t h_cap[2];
-    int seg_slot;
-    LaunchSeg *d_segs;
-    int *d_queue;           // one stream counter per launch round of a call (persistent greedy workgroups), zeroed per call
-    size_t queue_cap;
+    HostBuf<LaunchSeg> h_segs[2];
+    Event seg_ev[2];
+    int seg_slot = 0;
+    DeviceBuf<LaunchSeg> d_segs;
+    DeviceBuf<int> d_queue;     // one stream counter per launch round of a call (persistent greedy workgroups), zeroed per call
     // what the one-wave kernels saw (kTieHeavyPercentDHGR / HGR): device counters, their pinned host copy, the event behind the copy
-    unsigned long long *d_tie_stats, *h_tie_stats, tie_seen[3];
-    hipEvent_t tie_ev;
-    bool tie_copy_pending;
-    int tie_heavy;          // -1: not known yet, 0 / 1
-    double tie_rate;        // of the latest interval looked at
-    double ops_per_launch;  // real (not padding) opcodes per stream and launch, likewise
-    size_t d_cap;
+    DeviceBuf<unsigned long long> d_tie_stats;
+    HostBuf<unsigned long long> h_tie_stats;
+    unsigned long long tie_seen[3] = {0, 0, 0};
+    Event tie_ev;
+    bool tie_copy_pending = false;
+    int tie_heavy = -1;         // -1: not known yet, 0 / 1
+    double tie_rate = 0.0;      // of the latest interval looked at
+    double ops_per_launch = 0.0;  // real (not padding) opcodes per stream and launch, likewise
     // scratch for encoder_check / IIV_STATE_PACKED
-    int *d_result;
-    uint64_t *d_packed;
+    DeviceBuf<int> d_result;
+    DeviceBuf<uint64_t> d_packed;
     // profiling
-    int profiling;
-    std::vector<hipEvent_t> ev_pool;
+    int profiling = 0;
+    std::vector<Event> ev_pool;
     std::vector<int> ev_class;  // class of interval i = events [2i, 2i+1]
-    double ms[2];
-    int64_t launches[2];
-    int64_t form_launches[4];   // greedy launches since profiling was switched on: one-wave plain / LDS-shared, team, workgroup
+    double ms[2] = {0, 0};
+    int64_t launches[2] = {0, 0};
+    int64_t form_launches[4] = {0, 0, 0, 0};   // greedy launches since profiling was switched on: one-wave plain / LDS-shared, team, workgroup
     // longest-first launch order of the one-wave kernel: what every stream's latest launch cost, the permutation in use
-    uint32_t *d_cost;
-    int *d_perm;
-    int order_countdown;        // greedy launches until the next re-sort
-    int order_streams;          // IIV_OPT_STREAM_ORDER: 1 (default) / 0
+    DeviceBuf<uint32_t> d_cost;
+    DeviceBuf<int> d_perm;
+    int order_countdown = 2;    // greedy launches until the next re-sort (the first launches have no history: two of them, then the first sort)
+    int order_streams = 1;      // IIV_OPT_STREAM_ORDER: 1 (default) / 0
 };
+
+}  // namespace iiv
+
+// the C ABI's handle (include/iivision.h) is the host object itself
+struct iiv_encoder : iiv::Encoder {};
+
+namespace iiv {
 
 static void seed_by_array(uint32_t mt[624], const uint32_t *key, int n)
 {
@@ -254,52 +265,11 @@ __global__ __launch_bounds__(256) void max_u16_kernel(const uint16_t *__restrict
     if ((threadIdx.x & 63) == 0) atomicMax(result, mx);
 }
 
-void encoder_destroy(Encoder *e)
-{
-    if (!e) return;
-    for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
-    for (int k = 0; k < 2; k++) {
-        if (e->h_segs[k]) (void)hipHostFree(e->h_segs[k]);
-        if (e->seg_ev[k]) (void)hipEventDestroy(e->seg_ev[k]);
-    }
-    if (e->d_segs) (void)hipFree(e->d_segs);
-    if (e->d_queue) (void)hipFree(e->d_queue);
-    if (e->d_tie_stats) (void)hipFree(e->d_tie_stats);
-    if (e->h_tie_stats) (void)hipHostFree(e->h_tie_stats);
-    if (e->tie_ev) (void)hipEventDestroy(e->tie_ev);
-    if (e->d_result) (void)hipFree(e->d_result);
-    if (e->d_cost) (void)hipFree(e->d_cost);
-    if (e->d_perm) (void)hipFree(e->d_perm);
-    if (e->d_packed) (void)hipFree(e->d_packed);
-    if (e->d_states) (void)hipFree(e->d_states);
-    for (int k = 0; k < 2; k++) {
-        if (e->d_snapshot[k]) (void)hipFree(e->d_snapshot[k]);
-        if (e->h_live[k]) (void)hipHostFree(e->h_live[k]);
-    }
-    if (e->h_small[0]) (void)hipHostFree(e->h_small[0]);
-    for (int k = 0; k < kSmallSlots; k++)
-        if (e->small_ev[k]) (void)hipEventDestroy(e->small_ev[k]);
-    if (e->d_strings) (void)hipFree(e->d_strings);
-    if (e->d_hgr_dots) (void)hipFree(e->d_hgr_dots);
-    if (e->d_dw_pieces) (void)hipFree(e->d_dw_pieces);
-    if (e->d_sub) (void)hipFree(e->d_sub);
-    if (e->d_left) (void)hipFree(e->d_left);
-    if (e->d_right) (void)hipFree(e->d_right);
-    free_narrow_tables(&e->nt);
-    if (e->d_dwl) (void)hipFree(e->d_dwl);
-    if (e->d_left_t) (void)hipFree(e->d_left_t);
-    if (e->d_joint_l) (void)hipFree(e->d_joint_l);
-    if (e->d_joint_r) (void)hipFree(e->d_joint_r);
-    if (e->d_brief) (void)hipFree(e->d_brief);
-    if (e->d_right_t) (void)hipFree(e->d_right_t);
-    if (e->d_dwr) (void)hipFree(e->d_dwr);
-    delete e;
-}
-
 int encoder_create(int mode, const uint16_t *d_table, const uint16_t *d_store, const int32_t *dm, int n_streams,
-                   Encoder **out)
+                   iiv_encoder **out)
 {
-    if ((mode != kHGR && mode != kDHGR) || (!d_table && !dm) || !d_store || n_streams <= 0 || !out)
+    if (!out) return set_error(IIV_ERR_INVALID, "iiv_encoder_create: out is NULL");
+    if ((mode != kHGR && mode != kDHGR) || (!d_table && !dm) || !d_store || n_streams <= 0)
         return set_error(IIV_ERR_INVALID, "iiv_encoder_create: bad argument");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -316,120 +286,63 @@ int encoder_create(int mode, const uint16_t *d_table, const uint16_t *d_store, c
             return set_error(IIV_ERR_INVALID, "iiv_encoder_create: max(dm) * MASKED_DOTS = %d exceeds %d",
                              mx * masked_dots(mode), kMaxValue);
     }
-    Encoder *e = new Encoder();
+    std::unique_ptr<iiv_encoder> e(new iiv_encoder);   // (released with everything it holds on every early return)
     e->mode = mode;
     e->n_streams = n_streams;
     e->d_table = d_table;
     e->d_store = d_store;
-    e->d_left = e->d_right = nullptr;
-    e->nt.base = nullptr;
-    e->nt.exact = 0;
-    e->d_dwl = e->d_dwr = nullptr;
-    e->d_left_t = e->d_right_t = nullptr;
-    e->d_joint_l = e->d_joint_r = nullptr;
-    e->d_brief = nullptr;
-    e->d_states = e->d_snapshot[0] = e->d_snapshot[1] = nullptr;
-    e->h_live[0] = e->h_live[1] = e->d_live[0] = e->d_live[1] = e->live_now = nullptr;
-    e->h_small[0] = nullptr;
-    for (int k = 0; k < kSmallSlots; k++) e->small_ev[k] = nullptr;
-    e->small_slot = 0;
-    e->live_tag = 0;
-    e->d_strings = nullptr;
-    e->d_hgr_dots = nullptr;
-    e->d_dw_pieces = nullptr;
-    e->d_sub = nullptr;
     e->dw_mode = dm ? IIV_DW_RECURRENCE : IIV_DW_TABLE;
-    e->greedy_mode = IIV_GREEDY_AUTO;
-    e->partial_sort = 1;
-    e->greedy_lds_pad = 0;
-    e->content_choice = IIV_CONTENT_TARGET;
-    e->fourth_offset = 0;
-    e->gens.assign(1, GenState{0, 0, 0});
-    e->h_segs[0] = e->h_segs[1] = nullptr;
-    e->seg_ev[0] = e->seg_ev[1] = nullptr;
-    e->h_cap[0] = e->h_cap[1] = 0;
-    e->seg_slot = 0;
-    e->d_segs = nullptr;
-    e->d_queue = nullptr;
-    e->queue_cap = 0;
-    e->d_tie_stats = e->h_tie_stats = nullptr;
-    e->tie_seen[0] = e->tie_seen[1] = e->tie_seen[2] = 0;
-    e->ops_per_launch = 0.0;
-    e->tie_ev = nullptr;
-    e->tie_copy_pending = false;
-    e->tie_heavy = -1;
-    e->tie_rate = 0.0;
-    e->d_cap = 0;
-    e->d_result = nullptr;
-    e->d_packed = nullptr;
-    e->profiling = 0;
-    e->ms[0] = e->ms[1] = 0;
-    e->launches[0] = e->launches[1] = 0;
-    e->form_launches[0] = e->form_launches[1] = e->form_launches[2] = e->form_launches[3] = 0;
-    e->d_cost = nullptr;
-    e->d_perm = nullptr;
-    e->order_countdown = 2;     // (the first launches have no history: two of them, then the first sort)
-    e->order_streams = 1;
-    uint32_t *d_rng0 = nullptr;
     int rc = IIV_OK;
-    do {
-        if ((rc = hip_check(hipMalloc(&e->d_states, sizeof(StreamState) * (size_t)n_streams), "hipMalloc(stream states)"))) break;
-        if ((rc = hip_check(hipMalloc(&e->d_result, 2 * sizeof(int)), "hipMalloc(result)"))) break;
-        if (n_streams >= kOrderMinStreams) {
-            if ((rc = hip_check(hipMalloc(&e->d_cost, sizeof(uint32_t) * (size_t)n_streams), "hipMalloc(stream costs)"))) break;
-            if ((rc = hip_check(hipMemset(e->d_cost, 0, sizeof(uint32_t) * (size_t)n_streams), "memset"))) break;
-            if ((rc = hip_check(hipMalloc(&e->d_perm, sizeof(int) * (size_t)n_streams), "hipMalloc(stream order)"))) break;
-        }
-        if ((rc = hip_check(hipMalloc(&e->d_packed, 4096 * 8), "hipMalloc(packed)"))) break;
-        // (the brief's staging struct: here, not on first use -- an allocation inside the asynchronous entry point would synchronise)
-        if ((rc = hip_check(hipMalloc(&e->d_brief, sizeof(iiv_video_brief)), "hipMalloc(brief)"))) break;
-        if ((rc = hip_check(hipEventCreateWithFlags(&e->seg_ev[0], hipEventDisableTiming), "event"))) break;
-        if ((rc = hip_check(hipEventCreateWithFlags(&e->seg_ev[1], hipEventDisableTiming), "event"))) break;
-        if ((rc = hip_check(hipMalloc(&e->d_tie_stats, 3 * sizeof(unsigned long long)), "hipMalloc(tie statistics)"))) break;
-        if ((rc = hip_check(hipMemset(e->d_tie_stats, 0, 3 * sizeof(unsigned long long)), "memset"))) break;
-        if ((rc = hip_check(hipHostMalloc(&e->h_tie_stats, 3 * sizeof(unsigned long long)), "hipHostMalloc(tie statistics)"))) break;
-        e->h_tie_stats[0] = e->h_tie_stats[1] = e->h_tie_stats[2] = 0;
-        if ((rc = hip_check(hipEventCreateWithFlags(&e->tie_ev, hipEventDisableTiming), "event"))) break;
-        // the table values must fit the 11-bit fields too (a caller-made table may not come from dm)
-        uint32_t h_max = 0;
-        if ((rc = hip_check(hipMemset(e->d_result, 0, 8), "memset"))) break;
-        const size_t n_store = (size_t)num_offsets(mode) << (content_bits(mode) + masked_bits(mode));
-        hipLaunchKernelGGL(max_u16_kernel, dim3(1024), dim3(256), 0, 0, d_store, n_store, (uint32_t *)e->d_result);
-        if (!dm && d_table)
-            hipLaunchKernelGGL(max_u16_kernel, dim3(4096), dim3(256), 0, 0, d_table,
-                               (size_t)num_offsets(mode) << (2 * masked_bits(mode)), (uint32_t *)e->d_result);
-        if ((rc = hip_check(hipMemcpy(&h_max, e->d_result, 4, hipMemcpyDeviceToHost), "read max"))) break;
-        if (h_max > (uint32_t)kMaxValue) {
-            rc = set_error(IIV_ERR_INVALID, "iiv_encoder_create: table value %u exceeds %d", h_max, kMaxValue);
-            break;
-        }
-        if (dm) {
-            if ((rc = build_strings(mode, dm, &e->d_strings, &e->d_sub, 0))) break;
-            if (mode == kHGR && (rc = build_hgr_dot_lut(&e->d_hgr_dots, 0))) break;
-            if ((rc = build_dw_piece_table(mode, e->d_sub, &e->d_dw_pieces, 0))) break;
-            if ((rc = hip_check(hipMalloc(&e->d_left, split_entries(mode, 0) * 4), "hipMalloc(split left)"))) break;
-            if ((rc = hip_check(hipMalloc(&e->d_right, split_entries(mode, 1) * 4), "hipMalloc(split right)"))) break;
-            if ((rc = build_split_tables(mode, e->d_strings, e->d_sub, e->d_left, e->d_right, 0))) break;
-            // (the folded narrow form is compared with the caller's store table entry by entry: e->nt.exact)
-            if ((rc = build_narrow_tables(mode, e->d_strings, e->d_sub, e->d_left, d_store, &e->nt, 0))) break;
-        }
-        // Video.__init__ (video.py:21-62); RNG streams default to random.seed(0) / np.random.seed(0)
-        uint32_t rng0[1248], key0 = 0;
-        seed_by_array(rng0, &key0, 1);
-        seed_genrand(rng0 + 624, 0);
-        if ((rc = hip_check(hipMalloc(&d_rng0, sizeof(rng0)), "hipMalloc(rng0)"))) break;
-        if ((rc = hip_check(hipMemcpy(d_rng0, rng0, sizeof(rng0), hipMemcpyHostToDevice), "copy rng0"))) break;
-        if (e->d_perm) hipLaunchKernelGGL(order_streams_kernel, dim3(1), dim3(1024), 0, 0, e->d_cost, n_streams, e->d_perm, 1);
-        hipLaunchKernelGGL(init_states_kernel, dim3(n_streams), dim3(256), 0, 0, e->d_states, d_rng0);
-        if ((rc = hip_check(hipGetLastError(), "init_states launch"))) break;
-        rc = hip_check(hipDeviceSynchronize(), "init sync");
-    } while (0);
-    if (d_rng0) (void)hipFree(d_rng0);
-    if (rc) {
-        encoder_destroy(e);
-        return rc;
+    if ((rc = e->d_states.alloc((size_t)n_streams, "hipMalloc(stream states)"))) return rc;
+    if ((rc = e->d_result.alloc(2, "hipMalloc(result)"))) return rc;
+    if (n_streams >= kOrderMinStreams) {
+        if ((rc = e->d_cost.alloc((size_t)n_streams, "hipMalloc(stream costs)"))) return rc;
+        if ((rc = hip_check(hipMemset(e->d_cost, 0, sizeof(uint32_t) * (size_t)n_streams), "memset"))) return rc;
+        if ((rc = e->d_perm.alloc((size_t)n_streams, "hipMalloc(stream order)"))) return rc;
     }
-    *out = e;
+    if ((rc = e->d_packed.alloc(4096, "hipMalloc(packed)"))) return rc;
+    // (the brief's staging struct: here, not on first use -- an allocation inside the asynchronous entry point would synchronise)
+    if ((rc = e->d_brief.alloc(1, "hipMalloc(brief)"))) return rc;
+    if ((rc = e->seg_ev[0].create(hipEventDisableTiming, "event"))) return rc;
+    if ((rc = e->seg_ev[1].create(hipEventDisableTiming, "event"))) return rc;
+    if ((rc = e->d_tie_stats.alloc(3, "hipMalloc(tie statistics)"))) return rc;
+    if ((rc = hip_check(hipMemset(e->d_tie_stats, 0, 3 * sizeof(unsigned long long)), "memset"))) return rc;
+    if ((rc = e->h_tie_stats.alloc(3, hipHostMallocDefault, "hipHostMalloc(tie statistics)"))) return rc;
+    e->h_tie_stats[0] = e->h_tie_stats[1] = e->h_tie_stats[2] = 0;
+    if ((rc = e->tie_ev.create(hipEventDisableTiming, "event"))) return rc;
+    // the table values must fit the 11-bit fields too (a caller-made table may not come from dm)
+    uint32_t h_max = 0;
+    if ((rc = hip_check(hipMemset(e->d_result, 0, 8), "memset"))) return rc;
+    const size_t n_store = (size_t)num_offsets(mode) << (content_bits(mode) + masked_bits(mode));
+    hipLaunchKernelGGL(max_u16_kernel, dim3(1024), dim3(256), 0, 0, d_store, n_store, (uint32_t *)e->d_result.get());
+    if (!dm && d_table)
+        hipLaunchKernelGGL(max_u16_kernel, dim3(4096), dim3(256), 0, 0, d_table,
+                           (size_t)num_offsets(mode) << (2 * masked_bits(mode)), (uint32_t *)e->d_result.get());
+    if ((rc = hip_check(hipMemcpy(&h_max, e->d_result, 4, hipMemcpyDeviceToHost), "read max"))) return rc;
+    if (h_max > (uint32_t)kMaxValue)
+        return set_error(IIV_ERR_INVALID, "iiv_encoder_create: table value %u exceeds %d", h_max, kMaxValue);
+    if (dm) {
+        if ((rc = build_strings(mode, dm, e->d_strings, e->d_sub, 0))) return rc;
+        if (mode == kHGR && (rc = build_hgr_dot_lut(e->d_hgr_dots, 0))) return rc;
+        if ((rc = build_dw_piece_table(mode, e->d_sub, e->d_dw_pieces, 0))) return rc;
+        if ((rc = e->d_left.alloc(split_entries(mode, 0), "hipMalloc(split left)"))) return rc;
+        if ((rc = e->d_right.alloc(split_entries(mode, 1), "hipMalloc(split right)"))) return rc;
+        if ((rc = build_split_tables(mode, e->d_strings, e->d_sub, e->d_left, e->d_right, 0))) return rc;
+        // (the folded narrow form is compared with the caller's store table entry by entry: e->nt.exact)
+        if ((rc = build_narrow_tables(mode, e->d_strings, e->d_sub, e->d_left, d_store, &e->nt, e->nt_storage, 0))) return rc;
+    }
+    // Video.__init__ (video.py:21-62); RNG streams default to random.seed(0) / np.random.seed(0)
+    uint32_t rng0[1248], key0 = 0;
+    seed_by_array(rng0, &key0, 1);
+    seed_genrand(rng0 + 624, 0);
+    DeviceBuf<uint32_t> d_rng0;
+    if ((rc = d_rng0.alloc(1248, "hipMalloc(rng0)"))) return rc;
+    if ((rc = hip_check(hipMemcpy(d_rng0, rng0, sizeof(rng0), hipMemcpyHostToDevice), "copy rng0"))) return rc;
+    if (e->d_perm) hipLaunchKernelGGL(order_streams_kernel, dim3(1), dim3(1024), 0, 0, e->d_cost.get(), n_streams, e->d_perm.get(), 1);
+    hipLaunchKernelGGL(init_states_kernel, dim3(n_streams), dim3(256), 0, 0, e->d_states.get(), d_rng0.get());
+    if ((rc = hip_check(hipGetLastError(), "init_states launch"))) return rc;
+    if ((rc = hip_check(hipDeviceSynchronize(), "init sync"))) return rc;
+    *out = e.release();
     return IIV_OK;
 }
 
@@ -437,8 +350,11 @@ int encoder_snapshot(Encoder *e, int slot, hipStream_t st)
 {
     if (!e || slot < 0 || slot > 1) return set_error(IIV_ERR_INVALID, "snapshot: null encoder or slot not 0 / 1");
     const size_t bytes = sizeof(StreamState) * (size_t)e->n_streams;
-    if (!e->d_snapshot[slot]) IIV_HIP(hipMalloc(&e->d_snapshot[slot], bytes));
-    IIV_HIP(hipMemcpyAsync(e->d_snapshot[slot], e->d_states, bytes, hipMemcpyDeviceToDevice, st));
+    DeviceBuf<StreamState> fresh;   // (the slot's first snapshot: the slot has it once the copy is under way)
+    if (!e->d_snapshot[slot])
+        if (int rc = fresh.alloc((size_t)e->n_streams, "hipMalloc(snapshot)")) return rc;
+    IIV_HIP(hipMemcpyAsync(fresh ? fresh : e->d_snapshot[slot], e->d_states, bytes, hipMemcpyDeviceToDevice, st));
+    if (fresh) e->d_snapshot[slot] = std::move(fresh);
     e->snap_gens[slot] = e->gens;
     return IIV_OK;
 }
@@ -462,11 +378,14 @@ int encoder_set_option(Encoder *e, int option, int value)
         if (value != IIV_DW_TABLE && value != IIV_DW_RECURRENCE && value != IIV_DW_SPLIT)
             return set_error(IIV_ERR_INVALID, "bad value");
         if (value == IIV_DW_SPLIT && !e->d_dwl) {  // built on first use: 4-5 MiB, a few hundred microseconds
-            IIV_HIP(hipMalloc(&e->d_dwl, split_dw_entries(e->mode, 0) * 4));
-            IIV_HIP(hipMalloc(&e->d_dwr, split_dw_entries(e->mode, 1) * 4));
-            int rc = build_split_dw_tables(e->mode, e->d_strings, e->d_sub, e->d_dwl, e->d_dwr, 0);
+            DeviceBuf<uint32_t> l, r;   // (the encoder has them once they are built)
+            int rc = l.alloc(split_dw_entries(e->mode, 0), "hipMalloc(split diff weights, left)");
+            if (!rc) rc = r.alloc(split_dw_entries(e->mode, 1), "hipMalloc(split diff weights, right)");
+            if (!rc) rc = build_split_dw_tables(e->mode, e->d_strings, e->d_sub, l, r, 0);
             if (rc) return rc;
             IIV_HIP(hipDeviceSynchronize());
+            e->d_dwl = std::move(l);
+            e->d_dwr = std::move(r);
         }
         e->dw_mode = value;
         return IIV_OK;
@@ -502,16 +421,22 @@ int encoder_set_option(Encoder *e, int option, int value)
         // (a store table that the narrow form does not reproduce -- not the one dm yields -- leaves only the split-table form)
         if (value == IIV_CONTENT_JOINT && !e->nt.exact) value = IIV_CONTENT_JOINT_SPLIT;
         if (value == IIV_CONTENT_JOINT && !e->d_joint_l) {
-            int rc = build_joint_tables(e->mode, e->nt, &e->d_joint_l, &e->d_joint_r, 0);
+            DeviceBuf<uint32_t> l, r;
+            int rc = build_joint_tables(e->mode, e->nt, l, r, 0);
             if (rc) return rc;
             IIV_HIP(hipDeviceSynchronize());
+            e->d_joint_l = std::move(l);
+            e->d_joint_r = std::move(r);
         }
         if (value == IIV_CONTENT_JOINT_SPLIT && !e->d_left_t) {
-            IIV_HIP(hipMalloc(&e->d_left_t, split_entries(e->mode, 0) * 4));
-            IIV_HIP(hipMalloc(&e->d_right_t, split_entries(e->mode, 1) * 4));
-            int rc = transpose_split_tables(e->mode, e->d_left, e->d_right, e->d_left_t, e->d_right_t, 0);
+            DeviceBuf<uint32_t> l, r;
+            int rc = l.alloc(split_entries(e->mode, 0), "hipMalloc(split left, transposed)");
+            if (!rc) rc = r.alloc(split_entries(e->mode, 1), "hipMalloc(split right, transposed)");
+            if (!rc) rc = transpose_split_tables(e->mode, e->d_left, e->d_right, l, r, 0);
             if (rc) return rc;
             IIV_HIP(hipDeviceSynchronize());
+            e->d_left_t = std::move(l);
+            e->d_right_t = std::move(r);
         }
         e->content_choice = value;
         return IIV_OK;
@@ -626,17 +551,20 @@ int encoder_set_state_async(Encoder *e, int s, int what, const void *buf, size_t
     if (bytes != want) return set_error(IIV_ERR_INVALID, "set_state_async: item %d is %zu bytes, got %zu", what, want, bytes);
     if (what != IIV_STATE_OUT_OF_WORK && ((const uint32_t *)buf)[624] > 624)
         return set_error(IIV_ERR_INVALID, "set_state_async: RNG index %u > 624", ((const uint32_t *)buf)[624]);
-    if (!e->h_small[0]) {
-        void *p = nullptr;
-        IIV_HIP(hipHostMalloc(&p, kSmallSlots * kSmallBytes, hipHostMallocDefault));
-        e->h_small[0] = static_cast<uint8_t *>(p);
-        for (int k = 0; k < kSmallSlots; k++) IIV_HIP(hipEventCreateWithFlags(&e->small_ev[k], hipEventDisableTiming));
+    if (!e->h_small) {
+        HostBuf<uint8_t> ring;
+        Event ev[kSmallSlots];
+        if (int rc = ring.alloc(kSmallSlots * kSmallBytes, hipHostMallocDefault, "hipHostMalloc(state staging)")) return rc;
+        for (int k = 0; k < kSmallSlots; k++)
+            if (int rc = ev[k].create(hipEventDisableTiming, "event")) return rc;
+        e->h_small = std::move(ring);
+        for (int k = 0; k < kSmallSlots; k++) e->small_ev[k] = std::move(ev[k]);
         e->small_slot = -kSmallSlots;   // (the first round of the ring has nothing to wait for)
     }
     const int k = e->small_slot < 0 ? e->small_slot + kSmallSlots : e->small_slot;
     if (e->small_slot >= 0) IIV_HIP(hipEventSynchronize(e->small_ev[k]));   // the copies that last used this slot are done
     e->small_slot = e->small_slot < 0 ? e->small_slot + 1 : (e->small_slot + 1) % kSmallSlots;
-    uint8_t *slot = e->h_small[0] + (size_t)k * kSmallBytes;
+    uint8_t *slot = e->h_small + (size_t)k * kSmallBytes;
     memcpy(slot, buf, bytes);
     uint8_t *base = reinterpret_cast<uint8_t *>(e->d_states + s);
     if (what == IIV_STATE_OUT_OF_WORK) {
@@ -717,8 +645,7 @@ int encoder_get_video_brief(Encoder *e, int s, iiv_video_brief *out)
 {
     if (!e || !out || s < 0 || s >= e->n_streams) return set_error(IIV_ERR_INVALID, "get_video_brief: bad argument");
     IIV_HIP(hipDeviceSynchronize());
-    if (!e->d_brief) IIV_HIP(hipMalloc(&e->d_brief, sizeof(iiv_video_brief)));
-    hipLaunchKernelGGL(brief_kernel, dim3(1), dim3(256), 0, 0, e->d_states + s, (iiv_video_brief *)e->d_brief);
+    hipLaunchKernelGGL(brief_kernel, dim3(1), dim3(256), 0, 0, e->d_states + s, e->d_brief.get());
     IIV_HIP(hipGetLastError());
     IIV_HIP(hipMemcpy(out, e->d_brief, sizeof(iiv_video_brief), hipMemcpyDeviceToHost));
     return IIV_OK;
@@ -729,8 +656,7 @@ int encoder_get_video_brief(Encoder *e, int s, iiv_video_brief *out)
 int encoder_get_video_brief_async(Encoder *e, int s, iiv_video_brief *out, hipStream_t st)
 {
     if (!e || !out || s < 0 || s >= e->n_streams) return set_error(IIV_ERR_INVALID, "get_video_brief_async: bad argument");
-    if (!e->d_brief) IIV_HIP(hipMalloc(&e->d_brief, sizeof(iiv_video_brief)));
-    hipLaunchKernelGGL(brief_kernel, dim3(1), dim3(256), 0, st, e->d_states + s, (iiv_video_brief *)e->d_brief);
+    hipLaunchKernelGGL(brief_kernel, dim3(1), dim3(256), 0, st, e->d_states + s, e->d_brief.get());
     IIV_HIP(hipGetLastError());
     IIV_HIP(hipMemcpyAsync(out, e->d_brief, sizeof(iiv_video_brief), hipMemcpyDeviceToHost, st));
     return IIV_OK;
@@ -759,11 +685,11 @@ static int prof_begin(Encoder *e, int cls, hipStream_t st, size_t &slot)
 {
     slot = e->ev_class.size();
     if (e->ev_pool.size() < 2 * (slot + 1)) {
-        hipEvent_t a, b;
-        IIV_HIP(hipEventCreate(&a));
-        IIV_HIP(hipEventCreate(&b));
-        e->ev_pool.push_back(a);
-        e->ev_pool.push_back(b);
+        Event a, b;
+        if (int rc = a.create(hipEventDefault, "hipEventCreate")) return rc;
+        if (int rc = b.create(hipEventDefault, "hipEventCreate")) return rc;
+        e->ev_pool.push_back(std::move(a));
+        e->ev_pool.push_back(std::move(b));
     }
     e->ev_class.push_back(cls);
     IIV_HIP(hipEventRecord(e->ev_pool[2 * slot], st));
@@ -911,24 +837,15 @@ static int plan_stream(Encoder *e, int stream, const iiv_segment *segs, int n_se
 static int upload_segs(Encoder *e, const std::vector<LaunchSeg> &host, hipStream_t st)
 {
     const size_t n = host.size();
-    if (n > e->d_cap) {
+    if (n > e->d_segs.count()) {
         IIV_HIP(hipStreamSynchronize(st));  // kernels of earlier calls may still read the old buffer
-        if (e->d_segs) (void)hipFree(e->d_segs);
-        e->d_segs = nullptr;
-        e->d_cap = 0;
-        IIV_HIP(hipMalloc(&e->d_segs, n * sizeof(LaunchSeg) * 2));
-        e->d_cap = 2 * n;
+        if (int rc = e->d_segs.alloc(2 * n, "hipMalloc(launch descriptors)")) return rc;
     }
     const int k = e->seg_slot;
     e->seg_slot ^= 1;
-    if (e->h_cap[k]) IIV_HIP(hipEventSynchronize(e->seg_ev[k]));  // the copy that last used this slot is done
-    if (n > e->h_cap[k]) {
-        if (e->h_segs[k]) (void)hipHostFree(e->h_segs[k]);
-        e->h_segs[k] = nullptr;
-        e->h_cap[k] = 0;
-        IIV_HIP(hipHostMalloc(&e->h_segs[k], n * sizeof(LaunchSeg) * 2, hipHostMallocDefault));
-        e->h_cap[k] = 2 * n;
-    }
+    if (e->h_segs[k].count()) IIV_HIP(hipEventSynchronize(e->seg_ev[k]));  // the copy that last used this slot is done
+    if (n > e->h_segs[k].count())
+        if (int rc = e->h_segs[k].alloc(2 * n, hipHostMallocDefault, "hipHostMalloc(launch descriptors)")) return rc;
     memcpy(e->h_segs[k], host.data(), n * sizeof(LaunchSeg));
     IIV_HIP(hipMemcpyAsync(e->d_segs, e->h_segs[k], n * sizeof(LaunchSeg), hipMemcpyHostToDevice, st));
     IIV_HIP(hipEventRecord(e->seg_ev[k], st));
@@ -938,13 +855,9 @@ static int upload_segs(Encoder *e, const std::vector<LaunchSeg> &host, hipStream
 // zeroed stream counters for the n_rounds launches of a call
 static int reset_queues(Encoder *e, size_t n_rounds, hipStream_t st)
 {
-    if (n_rounds > e->queue_cap) {
+    if (n_rounds > e->d_queue.count()) {
         IIV_HIP(hipStreamSynchronize(st));  // kernels of earlier calls may still count in the old buffer
-        if (e->d_queue) (void)hipFree(e->d_queue);
-        e->d_queue = nullptr;
-        e->queue_cap = 0;
-        IIV_HIP(hipMalloc(&e->d_queue, n_rounds * 2 * sizeof(int)));
-        e->queue_cap = n_rounds * 2;
+        if (int rc = e->d_queue.alloc(n_rounds * 2, "hipMalloc(stream counters)")) return rc;
     }
     IIV_HIP(hipMemsetAsync(e->d_queue, 0, n_rounds * sizeof(int), st));
     return IIV_OK;
@@ -1125,15 +1038,15 @@ int encoder_live_queue(Encoder *e, int slot, uint64_t **host_queue, int *capacit
     if (!e->h_live[slot]) {
         // coherent (fine-grained) and mapped: a kernel's store is a write into host memory, seen by the host without any
         // synchronisation call
-        void *p = nullptr;
-        IIV_HIP(hipHostMalloc(&p, (size_t)kLiveCap * 8, hipHostMallocCoherent | hipHostMallocMapped));
-        memset(p, 0, (size_t)kLiveCap * 8);   // (tag 0 is never used)
+        HostBuf<unsigned long long> q;
+        if (int rc = q.alloc(kLiveCap, hipHostMallocCoherent | hipHostMallocMapped, "hipHostMalloc(live queue)")) return rc;
+        memset(q, 0, (size_t)kLiveCap * 8);   // (tag 0 is never used)
         void *dev = nullptr;
-        IIV_HIP(hipHostGetDevicePointer(&dev, p, 0));
-        e->h_live[slot] = static_cast<unsigned long long *>(p);
+        IIV_HIP(hipHostGetDevicePointer(&dev, q, 0));
+        e->h_live[slot] = std::move(q);
         e->d_live[slot] = static_cast<unsigned long long *>(dev);
     }
-    *host_queue = reinterpret_cast<uint64_t *>(e->h_live[slot]);
+    *host_queue = reinterpret_cast<uint64_t *>(e->h_live[slot].get());
     *capacity = kLiveCap;
     return IIV_OK;
 }
@@ -1248,137 +1161,88 @@ int encoder_check(Encoder *e, int *bad_stream, hipStream_t st)
 }  // namespace iiv
 
 // ------------------------------------------------------------------------- C ABI
-
-struct iiv_encoder {
-    iiv::Encoder *impl;
-};
+// (an iiv_encoder is the host object: the entry points forward to the functions above, which check their arguments)
 
 extern "C" {
 
 int iiv_encoder_create(int mode, const uint16_t *d_table, const uint16_t *d_store_table, const int32_t dm[256],
                        int n_streams, iiv_encoder **out)
 {
-    if (!out) return iiv::set_error(IIV_ERR_INVALID, "iiv_encoder_create: out is NULL");
-    iiv::Encoder *impl = nullptr;
-    int rc = iiv::encoder_create(mode, d_table, d_store_table, dm, n_streams, &impl);
-    if (rc) return rc;
-    *out = new iiv_encoder{impl};
-    return IIV_OK;
+    return iiv::encoder_create(mode, d_table, d_store_table, dm, n_streams, out);
 }
 
-void iiv_encoder_destroy(iiv_encoder *enc)
-{
-    if (!enc) return;
-    iiv::encoder_destroy(enc->impl);
-    delete enc;
-}
+void iiv_encoder_destroy(iiv_encoder *enc) { delete enc; }
 
-int iiv_encoder_snapshot(iiv_encoder *enc, void *stream)
-{
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_snapshot(enc->impl, 0, (hipStream_t)stream);
-}
-
-int iiv_encoder_rollback(iiv_encoder *enc, void *stream)
-{
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_rollback(enc->impl, 0, (hipStream_t)stream);
-}
-
-int iiv_encoder_snapshot_slot(iiv_encoder *enc, int slot, void *stream)
-{
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_snapshot(enc->impl, slot, (hipStream_t)stream);
-}
-
-int iiv_encoder_rollback_slot(iiv_encoder *enc, int slot, void *stream)
-{
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_rollback(enc->impl, slot, (hipStream_t)stream);
-}
-
-int iiv_encoder_set_option(iiv_encoder *enc, int option, int value)
-{
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_set_option(enc->impl, option, value);
-}
+int iiv_encoder_snapshot(iiv_encoder *enc, void *stream) { return iiv::encoder_snapshot(enc, 0, (hipStream_t)stream); }
+int iiv_encoder_rollback(iiv_encoder *enc, void *stream) { return iiv::encoder_rollback(enc, 0, (hipStream_t)stream); }
+int iiv_encoder_snapshot_slot(iiv_encoder *enc, int slot, void *stream) { return iiv::encoder_snapshot(enc, slot, (hipStream_t)stream); }
+int iiv_encoder_rollback_slot(iiv_encoder *enc, int slot, void *stream) { return iiv::encoder_rollback(enc, slot, (hipStream_t)stream); }
+int iiv_encoder_set_option(iiv_encoder *enc, int option, int value) { return iiv::encoder_set_option(enc, option, value); }
 
 int iiv_encoder_info(iiv_encoder *enc, int *mode, int *n_streams)
 {
-    if (!enc || !enc->impl) return iiv::set_error(IIV_ERR_INVALID, "iiv_encoder_info: null encoder");
-    if (mode) *mode = enc->impl->mode;
-    if (n_streams) *n_streams = enc->impl->n_streams;
+    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "iiv_encoder_info: null encoder");
+    if (mode) *mode = enc->mode;
+    if (n_streams) *n_streams = enc->n_streams;
     return IIV_OK;
 }
 
 int iiv_encoder_get_state(iiv_encoder *enc, int stream_index, int what, void *host_buf, size_t bytes)
 {
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_get_state(enc->impl, stream_index, what, host_buf, bytes);
+    return iiv::encoder_get_state(enc, stream_index, what, host_buf, bytes);
 }
 
 int iiv_encoder_set_state(iiv_encoder *enc, int stream_index, int what, const void *host_buf, size_t bytes)
 {
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_set_state(enc->impl, stream_index, 1, what, host_buf, bytes);
+    return iiv::encoder_set_state(enc, stream_index, 1, what, host_buf, bytes);
 }
 
 int iiv_encoder_set_state_async(iiv_encoder *enc, int stream_index, int what, const void *host_buf, size_t bytes, void *stream)
 {
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_set_state_async(enc->impl, stream_index, what, host_buf, bytes, (hipStream_t)stream);
+    return iiv::encoder_set_state_async(enc, stream_index, what, host_buf, bytes, (hipStream_t)stream);
 }
 
 int iiv_encoder_get_video_state(iiv_encoder *enc, int stream_index, iiv_video_state *host_out)
 {
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_get_video_state(enc->impl, stream_index, host_out);
+    return iiv::encoder_get_video_state(enc, stream_index, host_out);
 }
 
 int iiv_encoder_get_video_brief(iiv_encoder *enc, int stream_index, iiv_video_brief *host_out)
 {
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_get_video_brief(enc->impl, stream_index, host_out);
+    return iiv::encoder_get_video_brief(enc, stream_index, host_out);
 }
 
 int iiv_encoder_get_video_brief_async(iiv_encoder *enc, int stream_index, iiv_video_brief *host_out, void *stream)
 {
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_get_video_brief_async(enc->impl, stream_index, host_out, (hipStream_t)stream);
+    return iiv::encoder_get_video_brief_async(enc, stream_index, host_out, (hipStream_t)stream);
 }
 
 int iiv_encoder_set_video_state(iiv_encoder *enc, int stream_index, const iiv_video_state *host_in)
 {
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_set_video_state(enc->impl, stream_index, host_in);
+    return iiv::encoder_set_video_state(enc, stream_index, host_in);
 }
 
 int iiv_encoder_set_state_range(iiv_encoder *enc, int first_stream, int n_streams, int what, const void *host_buf,
                                 size_t bytes_per_stream)
 {
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_set_state(enc->impl, first_stream, n_streams, what, host_buf, bytes_per_stream);
+    return iiv::encoder_set_state(enc, first_stream, n_streams, what, host_buf, bytes_per_stream);
 }
 
 int iiv_encode(iiv_encoder *enc, const uint8_t *d_frames_main, const uint8_t *d_frames_aux, int n_frames,
                const iiv_segment *segments, int n_segments, uint8_t *d_ops_out, void *stream)
 {
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encode(enc->impl, d_frames_main, d_frames_aux, n_frames, segments, n_segments, d_ops_out,
-                       (hipStream_t)stream);
+    return iiv::encode(enc, d_frames_main, d_frames_aux, n_frames, segments, n_segments, d_ops_out, (hipStream_t)stream);
 }
 
 int iiv_encoder_live_queue(iiv_encoder *enc, int slot, uint64_t **host_queue, int *capacity)
 {
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_live_queue(enc->impl, slot, host_queue, capacity);
+    return iiv::encoder_live_queue(enc, slot, host_queue, capacity);
 }
 
 int iiv_encode_live(iiv_encoder *enc, const uint8_t *d_frames_main, const uint8_t *d_frames_aux, int n_frames,
                     const iiv_segment *segments, int n_segments, uint8_t *d_ops_out, int slot, uint32_t tag, void *stream)
 {
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encode_live(enc->impl, d_frames_main, d_frames_aux, n_frames, segments, n_segments, d_ops_out, slot, tag,
+    return iiv::encode_live(enc, d_frames_main, d_frames_aux, n_frames, segments, n_segments, d_ops_out, slot, tag,
                             (hipStream_t)stream);
 }
 
@@ -1386,40 +1250,15 @@ int iiv_encode_streams(iiv_encoder *enc, const uint8_t *d_frames_main, const uin
                        const iiv_segment *segments, const int32_t *seg_begin, uint8_t *d_ops_out, size_t ops_stride,
                        void *stream)
 {
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encode_streams(enc->impl, d_frames_main, d_frames_aux, n_frames, segments, seg_begin, d_ops_out, ops_stride,
+    return iiv::encode_streams(enc, d_frames_main, d_frames_aux, n_frames, segments, seg_begin, d_ops_out, ops_stride,
                                (hipStream_t)stream);
 }
 
-int iiv_encoder_check(iiv_encoder *enc, int *bad_stream, void *stream)
-{
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_check(enc->impl, bad_stream, (hipStream_t)stream);
-}
-
-int iiv_encoder_profile(iiv_encoder *enc, int enable)
-{
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_profile(enc->impl, enable);
-}
-
-int iiv_encoder_profile_read(iiv_encoder *enc, double ms[2], int64_t launches[2])
-{
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_profile_read(enc->impl, ms, launches);
-}
-
-int iiv_encoder_launch_forms(iiv_encoder *enc, int64_t counts[4])
-{
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_launch_forms(enc->impl, counts);
-}
-
-int iiv_encoder_input_stats(iiv_encoder *enc, double stats[2], int *form)
-{
-    if (!enc) return iiv::set_error(IIV_ERR_INVALID, "null encoder");
-    return iiv::encoder_input_stats(enc->impl, stats, form);
-}
+int iiv_encoder_check(iiv_encoder *enc, int *bad_stream, void *stream) { return iiv::encoder_check(enc, bad_stream, (hipStream_t)stream); }
+int iiv_encoder_profile(iiv_encoder *enc, int enable) { return iiv::encoder_profile(enc, enable); }
+int iiv_encoder_profile_read(iiv_encoder *enc, double ms[2], int64_t launches[2]) { return iiv::encoder_profile_read(enc, ms, launches); }
+int iiv_encoder_launch_forms(iiv_encoder *enc, int64_t counts[4]) { return iiv::encoder_launch_forms(enc, counts); }
+int iiv_encoder_input_stats(iiv_encoder *enc, double stats[2], int *form) { return iiv::encoder_input_stats(enc, stats, form); }
 
 int iiv_check_split_diff_table(int mode, const int32_t dm[256], const uint16_t *d_table, unsigned long long *mismatches,
                                void *stream)

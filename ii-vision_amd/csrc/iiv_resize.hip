@@ -109,19 +109,16 @@ int get_table(int in_size, int out_size, const Table **out)
     make_coeffs(in_size, out_size, t.ksize, b.data(), k.data());
     for (int o = 0; o < out_size; o++)
         for (int j = 0; j < t.ksize; j++) kt[(size_t)j * out_size + o] = k[(size_t)o * t.ksize + j];
-    void *mem = nullptr;
-    const size_t bytes = b.size() * 4 + 2 * nk * 4;
-    IIV_HIP(hipMalloc(&mem, bytes));
-    t.bounds = (int2 *)mem;
-    t.k_rows = (int32_t *)((char *)mem + b.size() * 4);
+    DeviceBuf<int32_t> mem;   // bounds | coefficients by row | by tap
+    if (int rc = mem.alloc(b.size() + 2 * nk, "hipMalloc(resize coefficients)")) return rc;
+    t.bounds = (int2 *)mem.get();
+    t.k_rows = mem + b.size();
     t.k_taps = t.k_rows + nk;
     int rc = hip_check(hipMemcpy(t.bounds, b.data(), b.size() * 4, hipMemcpyHostToDevice), "hipMemcpy(resize bounds)");
     if (!rc) rc = hip_check(hipMemcpy(t.k_rows, k.data(), nk * 4, hipMemcpyHostToDevice), "hipMemcpy(resize coefficients)");
     if (!rc) rc = hip_check(hipMemcpy(t.k_taps, kt.data(), nk * 4, hipMemcpyHostToDevice), "hipMemcpy(resize coefficients)");
-    if (rc) {
-        (void)hipFree(mem);
-        return rc;
-    }
+    if (rc) return rc;
+    (void)mem.release();   // (the cache keeps it for the life of the process)
     *out = &(cache[key] = t);
     return IIV_OK;
 }

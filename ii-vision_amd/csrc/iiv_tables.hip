@@ -374,53 +374,39 @@ int expand_narrow_tables(int mode, const NarrowTables &nt, const uint16_t *d_sto
                          hipStream_t st)
 {
     const size_t n = (size_t)num_offsets(mode) << (content_bits(mode) + masked_bits(mode));
-    unsigned long long *d_cnt = nullptr;
-    IIV_HIP(hipMalloc(&d_cnt, 8));
-    int rc = hip_check(hipMemsetAsync(d_cnt, 0, 8, st), "memset");
-    if (!rc) {
-        const dim3 grid((unsigned)((n + 255) / 256));
-        if (mode == kDHGR) hipLaunchKernelGGL(narrow_expand_kernel<kDHGR>, grid, dim3(256), 0, st, nt, d_store, d_out, d_cnt);
-        else hipLaunchKernelGGL(narrow_expand_kernel<kHGR>, grid, dim3(256), 0, st, nt, d_store, d_out, d_cnt);
-        rc = hip_check(hipGetLastError(), "narrow_expand_kernel launch");
-    }
-    if (!rc) rc = hip_check(hipMemcpyAsync(n_mismatch, d_cnt, 8, hipMemcpyDeviceToHost, st), "copy count");
-    if (!rc) rc = hip_check(hipStreamSynchronize(st), "sync");
-    (void)hipFree(d_cnt);
-    return rc;
+    DeviceBuf<unsigned long long> d_cnt;
+    if (int rc = d_cnt.alloc(1, "hipMalloc(count)")) return rc;
+    IIV_HIP(hipMemsetAsync(d_cnt, 0, 8, st));
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (mode == kDHGR) hipLaunchKernelGGL(narrow_expand_kernel<kDHGR>, grid, dim3(256), 0, st, nt, d_store, d_out, d_cnt.get());
+    else hipLaunchKernelGGL(narrow_expand_kernel<kHGR>, grid, dim3(256), 0, st, nt, d_store, d_out, d_cnt.get());
+    if (int rc = hip_check(hipGetLastError(), "narrow_expand_kernel launch")) return rc;
+    IIV_HIP(hipMemcpyAsync(n_mismatch, d_cnt, 8, hipMemcpyDeviceToHost, st));
+    return hip_check(hipStreamSynchronize(st), "sync");
 }
 
 // d_strings / d_sub: build_strings; d_left: the u32 left half (build_split_tables); d_store: the dense store table the
-// folded form is held to -- out->exact says whether every one of its entries is reproduced
+// folded form is held to -- out->exact says whether every one of its entries is reproduced.  `storage` receives the
+// allocation *out points into (both are left as they were if the build fails).
 int build_narrow_tables(int mode, const ulonglong2 *d_strings, const uint16_t *d_sub, const uint32_t *d_left, const uint16_t *d_store,
-                        NarrowTables *out, hipStream_t st)
+                        NarrowTables *out, DeviceBuf<uint8_t> &storage, hipStream_t st)
 {
     const size_t total = mode == kDHGR ? narrow_total_bytes<kDHGR>() : narrow_total_bytes<kHGR>();
     const size_t n_fill = split_entries(mode, 0) + split_entries(mode, 1);
-    uint8_t *buf = nullptr;
-    IIV_HIP(hipMalloc(&buf, total));
+    DeviceBuf<uint8_t> buf;
+    if (int rc = buf.alloc(total, "hipMalloc(narrow tables)")) return rc;
     if (mode == kDHGR)
-        hipLaunchKernelGGL(narrow_fold_kernel<kDHGR>, dim3((unsigned)((n_fill + 255) / 256)), dim3(256), 0, st, d_strings, d_sub, d_left, buf);
+        hipLaunchKernelGGL(narrow_fold_kernel<kDHGR>, dim3((unsigned)((n_fill + 255) / 256)), dim3(256), 0, st, d_strings, d_sub, d_left, buf.get());
     else
-        hipLaunchKernelGGL(narrow_fold_kernel<kHGR>, dim3((unsigned)((n_fill + 255) / 256)), dim3(256), 0, st, d_strings, d_sub, d_left, buf);
-    int rc = hip_check(hipGetLastError(), "narrow_fold_kernel launch");
-    out->base = buf;
-    out->right_off = mode == kDHGR ? narrow_right_off<kDHGR>() : narrow_right_off<kHGR>();
-    out->exact = 0;
+        hipLaunchKernelGGL(narrow_fold_kernel<kHGR>, dim3((unsigned)((n_fill + 255) / 256)), dim3(256), 0, st, d_strings, d_sub, d_left, buf.get());
+    if (int rc = hip_check(hipGetLastError(), "narrow_fold_kernel launch")) return rc;
+    NarrowTables nt{buf, mode == kDHGR ? narrow_right_off<kDHGR>() : narrow_right_off<kHGR>(), 0};
     unsigned long long bad = 0;
-    if (!rc) rc = expand_narrow_tables(mode, *out, d_store, nullptr, &bad, st);
-    if (rc) {
-        (void)hipFree(buf);
-        out->base = nullptr;
-        return rc;
-    }
-    out->exact = bad == 0 ? 1 : 0;
+    if (int rc = expand_narrow_tables(mode, nt, d_store, nullptr, &bad, st)) return rc;
+    nt.exact = bad == 0 ? 1 : 0;
+    *out = nt;
+    storage = std::move(buf);
     return IIV_OK;
-}
-
-void free_narrow_tables(NarrowTables *nt)
-{
-    if (nt->base) (void)hipFree(const_cast<uint8_t *>(nt->base));
-    nt->base = nullptr;
 }
 
 // The halves with content innermost -- T[o][row][content part] -- for the joint content choice
@@ -488,17 +474,17 @@ __global__ __launch_bounds__(256) void joint_pack_kernel(const uint8_t *__restri
     (is_left ? jl : jr)[idx] = v;
 }
 
-int build_joint_tables(int mode, const NarrowTables &nt, uint32_t **d_jl, uint32_t **d_jr, hipStream_t st)
+int build_joint_tables(int mode, const NarrowTables &nt, DeviceBuf<uint32_t> &d_jl, DeviceBuf<uint32_t> &d_jr, hipStream_t st)
 {
     const size_t nl = mode == kDHGR ? joint_left_entries<kDHGR>() : joint_left_entries<kHGR>();
     const size_t nr = mode == kDHGR ? joint_right_entries<kDHGR>() : joint_right_entries<kHGR>();
-    IIV_HIP(hipMalloc(d_jl, nl * 4));
-    IIV_HIP(hipMalloc(d_jr, nr * 4));
+    if (int rc = d_jl.alloc(nl, "hipMalloc(joint left)")) return rc;
+    if (int rc = d_jr.alloc(nr, "hipMalloc(joint right)")) return rc;
     const dim3 grid((unsigned)((nl + nr + 255) / 256));
     if (mode == kDHGR)
-        hipLaunchKernelGGL(joint_pack_kernel<kDHGR>, grid, dim3(256), 0, st, nt.base, nt.right_off, *d_jl, *d_jr);
+        hipLaunchKernelGGL(joint_pack_kernel<kDHGR>, grid, dim3(256), 0, st, nt.base, nt.right_off, d_jl.get(), d_jr.get());
     else
-        hipLaunchKernelGGL(joint_pack_kernel<kHGR>, grid, dim3(256), 0, st, nt.base, nt.right_off, *d_jl, *d_jr);
+        hipLaunchKernelGGL(joint_pack_kernel<kHGR>, grid, dim3(256), 0, st, nt.base, nt.right_off, d_jl.get(), d_jr.get());
     return hip_check(hipGetLastError(), "joint_pack_kernel launch");
 }
 
@@ -619,10 +605,10 @@ __global__ __launch_bounds__(256) void hgr_dot_lut_check_kernel(const uint32_t *
     if ((lut[hgr_dot_slot_lo(m, odd)] | lut[hgr_dot_slot_hi(m, odd)]) != (to_dots<kHGR>(m, odd) << 1)) atomicAdd(mismatches, 1ull);
 }
 
-int build_hgr_dot_lut(uint32_t **d_out, hipStream_t st)
+int build_hgr_dot_lut(DeviceBuf<uint32_t> &d_out, hipStream_t st)
 {
-    IIV_HIP(hipMalloc(d_out, kHgrDotLutEntries * sizeof(uint32_t)));
-    hipLaunchKernelGGL(hgr_dot_lut_kernel, dim3((kHgrDotLutEntries + 63) / 64), dim3(64), 0, st, *d_out);
+    if (int rc = d_out.alloc(kHgrDotLutEntries, "hipMalloc(HGR dot lookups)")) return rc;
+    hipLaunchKernelGGL(hgr_dot_lut_kernel, dim3((kHgrDotLutEntries + 63) / 64), dim3(64), 0, st, d_out.get());
     return hip_check(hipGetLastError(), "hgr_dot_lut_kernel launch");
 }
 
@@ -676,13 +662,13 @@ __global__ __launch_bounds__(256) void dw_piece_kernel(int mode, const uint16_t 
     out[mode == kDHGR ? (uint32_t)idx : cur6 * kHgrPieceStride + tgt6] = v;
 }
 
-int build_dw_piece_table(int mode, const uint16_t *d_sub, uint32_t **d_out, hipStream_t st)
+int build_dw_piece_table(int mode, const uint16_t *d_sub, DeviceBuf<uint32_t> &d_out, hipStream_t st)
 {
     const int n = (mode == kDHGR ? 2 : 1) * 4096;
     const size_t words = mode == kDHGR ? (size_t)n : (size_t)kHgrPieceWords;
-    IIV_HIP(hipMalloc(d_out, words * sizeof(uint32_t)));
-    IIV_HIP(hipMemsetAsync(*d_out, 0, words * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(dw_piece_kernel, dim3(n / 256), dim3(256), 0, st, mode, d_sub, *d_out);
+    if (int rc = d_out.alloc(words, "hipMalloc(diff-weight pieces)")) return rc;
+    IIV_HIP(hipMemsetAsync(d_out, 0, words * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(dw_piece_kernel, dim3(n / 256), dim3(256), 0, st, mode, d_sub, d_out.get());
     return hip_check(hipGetLastError(), "dw_piece_kernel launch");
 }
 
@@ -719,81 +705,65 @@ __global__ __launch_bounds__(256) void dw_piece_check_hgr_kernel(const uint32_t 
 
 int check_dw_piece_table(int mode, const int32_t dm[256], const uint16_t *d_table, unsigned long long *mismatches, hipStream_t st)
 {
-    uint16_t sub[256], *d_sub = nullptr;
-    uint32_t *d_p = nullptr, *d_dots = nullptr;
-    unsigned long long *d_cnt = nullptr;
+    uint16_t sub[256];
+    DeviceBuf<uint16_t> d_sub;
+    DeviceBuf<uint32_t> d_p, d_dots;
+    DeviceBuf<unsigned long long> d_cnt;
     substitute_costs(dm, sub);
-    int rc = IIV_OK;
-    do {
-        if ((rc = hip_check(hipMalloc(&d_sub, sizeof(sub)), "hipMalloc(sub)"))) break;
-        if ((rc = hip_check(hipMemcpy(d_sub, sub, sizeof(sub), hipMemcpyHostToDevice), "copy sub"))) break;
-        if ((rc = hip_check(hipMalloc(&d_cnt, 8), "hipMalloc(count)"))) break;
-        if ((rc = hip_check(hipMemsetAsync(d_cnt, 0, 8, st), "memset"))) break;
-        if ((rc = build_dw_piece_table(mode, d_sub, &d_p, st))) break;
-        if (mode == kDHGR) {
-            hipLaunchKernelGGL(dw_piece_check_kernel, dim3((unsigned)(((size_t)4 << 26) / 256)), dim3(256), 0, st, d_p, d_table, d_cnt);
-        } else {
-            if ((rc = build_hgr_dot_lut(&d_dots, st))) break;
-            hipLaunchKernelGGL(hgr_dot_lut_check_kernel, dim3((2 << 14) / 256), dim3(256), 0, st, d_dots, d_cnt);
-            hipLaunchKernelGGL(dw_piece_check_hgr_kernel, dim3((unsigned)(((size_t)2 << 28) / 256)), dim3(256), 0, st, d_p, d_dots, d_table, d_cnt);
-        }
-        if ((rc = hip_check(hipGetLastError(), "dw_piece_check_kernel launch"))) break;
-        if ((rc = hip_check(hipMemcpyAsync(mismatches, d_cnt, 8, hipMemcpyDeviceToHost, st), "copy count"))) break;
-        rc = hip_check(hipStreamSynchronize(st), "sync");
-    } while (0);
-    if (d_sub) (void)hipFree(d_sub);
-    if (d_p) (void)hipFree(d_p);
-    if (d_dots) (void)hipFree(d_dots);
-    if (d_cnt) (void)hipFree(d_cnt);
-    return rc;
+    if (int rc = d_sub.alloc(256, "hipMalloc(sub)")) return rc;
+    if (int rc = hip_check(hipMemcpy(d_sub, sub, sizeof(sub), hipMemcpyHostToDevice), "copy sub")) return rc;
+    if (int rc = d_cnt.alloc(1, "hipMalloc(count)")) return rc;
+    IIV_HIP(hipMemsetAsync(d_cnt, 0, 8, st));
+    if (int rc = build_dw_piece_table(mode, d_sub, d_p, st)) return rc;
+    if (mode == kDHGR) {
+        hipLaunchKernelGGL(dw_piece_check_kernel, dim3((unsigned)(((size_t)4 << 26) / 256)), dim3(256), 0, st, d_p.get(), d_table, d_cnt.get());
+    } else {
+        if (int rc = build_hgr_dot_lut(d_dots, st)) return rc;
+        hipLaunchKernelGGL(hgr_dot_lut_check_kernel, dim3((2 << 14) / 256), dim3(256), 0, st, d_dots.get(), d_cnt.get());
+        hipLaunchKernelGGL(dw_piece_check_hgr_kernel, dim3((unsigned)(((size_t)2 << 28) / 256)), dim3(256), 0, st, d_p.get(), d_dots.get(), d_table, d_cnt.get());
+    }
+    if (int rc = hip_check(hipGetLastError(), "dw_piece_check_kernel launch")) return rc;
+    if (int rc = hip_check(hipMemcpyAsync(mismatches, d_cnt, 8, hipMemcpyDeviceToHost, st), "copy count")) return rc;
+    return hip_check(hipStreamSynchronize(st), "sync");   // (the scratch is freed on return)
 }
 
-struct TableScratch {
-    ulonglong2 *strings = nullptr;
-    uint16_t *sub = nullptr;
-    ~TableScratch()
-    {
-        if (strings) (void)hipFree(strings);
-        if (sub) (void)hipFree(sub);
-    }
-};
-
-static int prepare_scratch(int mode, const int32_t dm[256], TableScratch &sc, hipStream_t st)
+// the colour strings and substitute costs of dm, what every builder below starts from (the strings are enqueued on `st`)
+static int prepare_strings(int mode, const int32_t dm[256], DeviceBuf<ulonglong2> &d_strings, DeviceBuf<uint16_t> &d_sub, hipStream_t st)
 {
     size_t n = (size_t)num_offsets(mode) << masked_bits(mode);
-    IIV_HIP(hipMalloc(&sc.strings, n * sizeof(ulonglong2)));
-    IIV_HIP(hipMalloc(&sc.sub, 256 * sizeof(uint16_t)));
+    if (int rc = d_strings.alloc(n, "hipMalloc(colour strings)")) return rc;
+    if (int rc = d_sub.alloc(256, "hipMalloc(sub)")) return rc;
     uint16_t sub[256];
     substitute_costs(dm, sub);
-    IIV_HIP(hipMemcpyAsync(sc.sub, sub, sizeof(sub), hipMemcpyHostToDevice, st));
+    IIV_HIP(hipMemcpyAsync(d_sub, sub, sizeof(sub), hipMemcpyHostToDevice, st));
     IIV_HIP(hipStreamSynchronize(st));  // `sub` is a stack buffer
-    return pixel_strings(mode, nullptr, nullptr, sc.strings, st);
+    return pixel_strings(mode, nullptr, nullptr, d_strings, st);
 }
 
-int build_strings(int mode, const int32_t dm[256], ulonglong2 **d_strings, uint16_t **d_sub, hipStream_t st)
+int build_strings(int mode, const int32_t dm[256], DeviceBuf<ulonglong2> &d_strings, DeviceBuf<uint16_t> &d_sub, hipStream_t st)
 {
-    TableScratch sc;
-    int rc = prepare_scratch(mode, dm, sc, st);
+    DeviceBuf<ulonglong2> strings;
+    DeviceBuf<uint16_t> sub;
+    int rc = prepare_strings(mode, dm, strings, sub, st);
     if (rc) return rc;
     IIV_HIP(hipStreamSynchronize(st));
-    *d_strings = sc.strings;
-    *d_sub = sc.sub;
-    sc.strings = nullptr;  // ownership passes to the caller
-    sc.sub = nullptr;
+    d_strings = std::move(strings);
+    d_sub = std::move(sub);
     return IIV_OK;
 }
 
 int build_table(int mode, const int32_t dm[256], uint16_t *d_out, int symmetric, hipStream_t st)
 {
-    TableScratch sc;
-    int rc = prepare_scratch(mode, dm, sc, st);
+    DeviceBuf<ulonglong2> strings;
+    DeviceBuf<uint16_t> sub;
+    int rc = prepare_strings(mode, dm, strings, sub, st);
     if (rc) return rc;
     int bits = masked_bits(mode);
     dim3 grid((1u << bits) / (256 * kTableColsPerThread), (1u << bits) / kTableRowsPerBlock, num_offsets(mode));
     if (mode == kDHGR)
-        hipLaunchKernelGGL(table_kernel<kDHGR>, grid, dim3(256), 0, st, sc.strings, sc.sub, d_out, symmetric);
+        hipLaunchKernelGGL(table_kernel<kDHGR>, grid, dim3(256), 0, st, strings.get(), sub.get(), d_out, symmetric);
     else
-        hipLaunchKernelGGL(table_kernel<kHGR>, grid, dim3(256), 0, st, sc.strings, sc.sub, d_out, symmetric);
+        hipLaunchKernelGGL(table_kernel<kHGR>, grid, dim3(256), 0, st, strings.get(), sub.get(), d_out, symmetric);
     rc = hip_check(hipGetLastError(), "table_kernel launch");
     if (rc) return rc;
     IIV_HIP(hipStreamSynchronize(st));  // scratch is freed on return
@@ -802,15 +772,16 @@ int build_table(int mode, const int32_t dm[256], uint16_t *d_out, int symmetric,
 
 int build_store_table(int mode, const int32_t dm[256], uint16_t *d_out, hipStream_t st)
 {
-    TableScratch sc;
-    int rc = prepare_scratch(mode, dm, sc, st);
+    DeviceBuf<ulonglong2> strings;
+    DeviceBuf<uint16_t> sub;
+    int rc = prepare_strings(mode, dm, strings, sub, st);
     if (rc) return rc;
     size_t n = (size_t)num_offsets(mode) << (content_bits(mode) + masked_bits(mode));
     dim3 grid((unsigned)((n + 255) / 256));
     if (mode == kDHGR)
-        hipLaunchKernelGGL(store_kernel<kDHGR>, grid, dim3(256), 0, st, sc.strings, sc.sub, d_out);
+        hipLaunchKernelGGL(store_kernel<kDHGR>, grid, dim3(256), 0, st, strings.get(), sub.get(), d_out);
     else
-        hipLaunchKernelGGL(store_kernel<kHGR>, grid, dim3(256), 0, st, sc.strings, sc.sub, d_out);
+        hipLaunchKernelGGL(store_kernel<kHGR>, grid, dim3(256), 0, st, strings.get(), sub.get(), d_out);
     rc = hip_check(hipGetLastError(), "store_kernel launch");
     if (rc) return rc;
     IIV_HIP(hipStreamSynchronize(st));
@@ -872,31 +843,26 @@ __global__ __launch_bounds__(256) void split_dw_check_kernel(const uint32_t *__r
 int check_split_dw_table(int mode, const int32_t dm[256], const uint16_t *d_table, unsigned long long *mismatches,
                          hipStream_t st)
 {
-    TableScratch sc;
-    int rc = prepare_scratch(mode, dm, sc, st);
+    DeviceBuf<ulonglong2> strings;
+    DeviceBuf<uint16_t> sub;
+    int rc = prepare_strings(mode, dm, strings, sub, st);
     if (rc) return rc;
-    uint32_t *d_l = nullptr, *d_r = nullptr;
-    unsigned long long *d_cnt = nullptr;
-    do {
-        if ((rc = hip_check(hipMalloc(&d_l, split_dw_entries(mode, 0) * 4), "hipMalloc(dw left)"))) break;
-        if ((rc = hip_check(hipMalloc(&d_r, split_dw_entries(mode, 1) * 4), "hipMalloc(dw right)"))) break;
-        if ((rc = hip_check(hipMalloc(&d_cnt, 8), "hipMalloc(count)"))) break;
-        if ((rc = hip_check(hipMemsetAsync(d_cnt, 0, 8, st), "memset"))) break;
-        if ((rc = build_split_dw_tables(mode, sc.strings, sc.sub, d_l, d_r, st))) break;
-        const size_t n = (size_t)num_offsets(mode) << (2 * masked_bits(mode));
-        const dim3 grid((unsigned)((n + 255) / 256));
-        if (mode == kDHGR)
-            hipLaunchKernelGGL(split_dw_check_kernel<kDHGR>, grid, dim3(256), 0, st, d_l, d_r, d_table, d_cnt);
-        else
-            hipLaunchKernelGGL(split_dw_check_kernel<kHGR>, grid, dim3(256), 0, st, d_l, d_r, d_table, d_cnt);
-        if ((rc = hip_check(hipGetLastError(), "split_dw_check_kernel launch"))) break;
-        if ((rc = hip_check(hipMemcpyAsync(mismatches, d_cnt, 8, hipMemcpyDeviceToHost, st), "copy count"))) break;
-        rc = hip_check(hipStreamSynchronize(st), "sync");
-    } while (0);
-    if (d_l) (void)hipFree(d_l);
-    if (d_r) (void)hipFree(d_r);
-    if (d_cnt) (void)hipFree(d_cnt);
-    return rc;
+    DeviceBuf<uint32_t> d_l, d_r;
+    DeviceBuf<unsigned long long> d_cnt;
+    if ((rc = d_l.alloc(split_dw_entries(mode, 0), "hipMalloc(dw left)"))) return rc;
+    if ((rc = d_r.alloc(split_dw_entries(mode, 1), "hipMalloc(dw right)"))) return rc;
+    if ((rc = d_cnt.alloc(1, "hipMalloc(count)"))) return rc;
+    IIV_HIP(hipMemsetAsync(d_cnt, 0, 8, st));
+    if ((rc = build_split_dw_tables(mode, strings.get(), sub.get(), d_l, d_r, st))) return rc;
+    const size_t n = (size_t)num_offsets(mode) << (2 * masked_bits(mode));
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (mode == kDHGR)
+        hipLaunchKernelGGL(split_dw_check_kernel<kDHGR>, grid, dim3(256), 0, st, d_l.get(), d_r.get(), d_table, d_cnt.get());
+    else
+        hipLaunchKernelGGL(split_dw_check_kernel<kHGR>, grid, dim3(256), 0, st, d_l.get(), d_r.get(), d_table, d_cnt.get());
+    if ((rc = hip_check(hipGetLastError(), "split_dw_check_kernel launch"))) return rc;
+    if ((rc = hip_check(hipMemcpyAsync(mismatches, d_cnt, 8, hipMemcpyDeviceToHost, st), "copy count"))) return rc;
+    return hip_check(hipStreamSynchronize(st), "sync");   // (the scratch is freed on return)
 }
 
 size_t split_entries(int mode, int right)
@@ -908,17 +874,20 @@ size_t split_entries(int mode, int right)
 int build_split_store_table(int mode, const int32_t dm[256], uint32_t *d_left, uint32_t *d_right, uint16_t *d_expanded,
                             hipStream_t st)
 {
-    TableScratch sc;
-    int rc = prepare_scratch(mode, dm, sc, st);
+    DeviceBuf<ulonglong2> strings;
+    DeviceBuf<uint16_t> sub;
+    int rc = prepare_strings(mode, dm, strings, sub, st);
     if (rc) return rc;
-    uint32_t *tmp_l = nullptr, *tmp_r = nullptr;
-    if (!d_left) { IIV_HIP(hipMalloc(&tmp_l, split_entries(mode, 0) * 4)); d_left = tmp_l; }
+    DeviceBuf<uint32_t> tmp_l, tmp_r;   // (a half the caller does not ask for)
+    if (!d_left) {
+        if ((rc = tmp_l.alloc(split_entries(mode, 0), "hipMalloc(split left)"))) return rc;
+        d_left = tmp_l;
+    }
     if (!d_right) {
-        hipError_t he = hipMalloc(&tmp_r, split_entries(mode, 1) * 4);
-        if (he != hipSuccess) { if (tmp_l) (void)hipFree(tmp_l); return hip_check(he, "hipMalloc(split right)"); }
+        if ((rc = tmp_r.alloc(split_entries(mode, 1), "hipMalloc(split right)"))) return rc;
         d_right = tmp_r;
     }
-    rc = build_split_tables(mode, sc.strings, sc.sub, d_left, d_right, st);
+    rc = build_split_tables(mode, strings.get(), sub.get(), d_left, d_right, st);
     if (!rc && d_expanded) {
         size_t n = (size_t)num_offsets(mode) << (content_bits(mode) + masked_bits(mode));
         dim3 grid((unsigned)((n + 255) / 256));
@@ -929,8 +898,6 @@ int build_split_store_table(int mode, const int32_t dm[256], uint32_t *d_left, u
         rc = hip_check(hipGetLastError(), "split_expand_kernel launch");
     }
     hipError_t he = hipStreamSynchronize(st);  // scratch is freed on return
-    if (tmp_l) (void)hipFree(tmp_l);
-    if (tmp_r) (void)hipFree(tmp_r);
     if (rc) return rc;
     return hip_check(he, "sync");
 }
@@ -940,22 +907,18 @@ int build_split_store_table(int mode, const int32_t dm[256], uint32_t *d_left, u
 int build_narrow_store_table(int mode, const int32_t dm[256], const uint16_t *d_store, uint16_t *d_expanded,
                              unsigned long long *n_mismatch, hipStream_t st)
 {
-    TableScratch sc;
-    int rc = prepare_scratch(mode, dm, sc, st);
+    DeviceBuf<ulonglong2> strings;
+    DeviceBuf<uint16_t> sub;
+    int rc = prepare_strings(mode, dm, strings, sub, st);
     if (rc) return rc;
-    uint32_t *d_l = nullptr, *d_r = nullptr;
+    DeviceBuf<uint32_t> d_l, d_r;
+    DeviceBuf<uint8_t> nt_storage;
     NarrowTables nt{};
-    do {
-        if ((rc = hip_check(hipMalloc(&d_l, split_entries(mode, 0) * 4), "hipMalloc(split left)"))) break;
-        if ((rc = hip_check(hipMalloc(&d_r, split_entries(mode, 1) * 4), "hipMalloc(split right)"))) break;
-        if ((rc = build_split_tables(mode, sc.strings, sc.sub, d_l, d_r, st))) break;
-        if ((rc = build_narrow_tables(mode, sc.strings, sc.sub, d_l, d_store, &nt, st))) break;
-        rc = expand_narrow_tables(mode, nt, d_store, d_expanded, n_mismatch, st);
-    } while (0);
-    free_narrow_tables(&nt);
-    if (d_l) (void)hipFree(d_l);
-    if (d_r) (void)hipFree(d_r);
-    return rc;
+    if ((rc = d_l.alloc(split_entries(mode, 0), "hipMalloc(split left)"))) return rc;
+    if ((rc = d_r.alloc(split_entries(mode, 1), "hipMalloc(split right)"))) return rc;
+    if ((rc = build_split_tables(mode, strings.get(), sub.get(), d_l, d_r, st))) return rc;
+    if ((rc = build_narrow_tables(mode, strings.get(), sub.get(), d_l, d_store, &nt, nt_storage, st))) return rc;
+    return expand_narrow_tables(mode, nt, d_store, d_expanded, n_mismatch, st);   // (synchronises `st`)
 }
 
 int symmetrise_table(int mode, uint16_t *d_table, hipStream_t st)
@@ -978,45 +941,36 @@ int store_table_from_table(int mode, const uint16_t *d_table, uint16_t *d_store,
 
 int delta_e_pairs(int n, const double *lab1, const double *lab2, double *out, hipStream_t st)
 {
-    double *d = nullptr;
-    IIV_HIP(hipMalloc(&d, (size_t)n * 7 * sizeof(double)));
-    int rc = hip_check(hipMemcpyAsync(d, lab1, (size_t)n * 24, hipMemcpyHostToDevice, st), "copy lab1");
-    if (!rc) rc = hip_check(hipMemcpyAsync(d + 3 * (size_t)n, lab2, (size_t)n * 24, hipMemcpyHostToDevice, st), "copy lab2");
-    if (!rc) {
-        hipLaunchKernelGGL(delta_e_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, d, d + 3 * (size_t)n, d + 6 * (size_t)n);
-        rc = hip_check(hipGetLastError(), "delta_e_kernel launch");
-    }
-    if (!rc) rc = hip_check(hipMemcpyAsync(out, d + 6 * (size_t)n, (size_t)n * 8, hipMemcpyDeviceToHost, st), "copy out");
-    if (!rc) rc = hip_check(hipStreamSynchronize(st), "sync");
-    (void)hipFree(d);
-    return rc;
+    DeviceBuf<double> buf;
+    if (int rc = buf.alloc((size_t)n * 7, "hipMalloc(Lab pairs)")) return rc;
+    double *d = buf;
+    if (int rc = hip_check(hipMemcpyAsync(d, lab1, (size_t)n * 24, hipMemcpyHostToDevice, st), "copy lab1")) return rc;
+    if (int rc = hip_check(hipMemcpyAsync(d + 3 * (size_t)n, lab2, (size_t)n * 24, hipMemcpyHostToDevice, st), "copy lab2")) return rc;
+    hipLaunchKernelGGL(delta_e_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, d, d + 3 * (size_t)n, d + 6 * (size_t)n);
+    if (int rc = hip_check(hipGetLastError(), "delta_e_kernel launch")) return rc;
+    if (int rc = hip_check(hipMemcpyAsync(out, d + 6 * (size_t)n, (size_t)n * 8, hipMemcpyDeviceToHost, st), "copy out")) return rc;
+    return hip_check(hipStreamSynchronize(st), "sync");
 }
 
 int cie2000_matrix(const uint8_t rgb[48], double out_f[256], int32_t out_i[256], hipStream_t st)
 {
-    uint8_t *d_rgb = nullptr;
-    double *d_f = nullptr;
-    int32_t *d_i = nullptr;
-    IIV_HIP(hipMalloc(&d_rgb, 48));
-    IIV_HIP(hipMalloc(&d_f, 256 * sizeof(double)));
-    IIV_HIP(hipMalloc(&d_i, 256 * sizeof(int32_t)));
-    int rc = IIV_OK;
-    do {
-        if ((rc = hip_check(hipMemcpyAsync(d_rgb, rgb, 48, hipMemcpyHostToDevice, st), "copy rgb"))) break;
-        hipLaunchKernelGGL(cie2000_kernel, dim3(1), dim3(256), 0, st, d_rgb, d_f, d_i);
-        if ((rc = hip_check(hipGetLastError(), "cie2000_kernel launch"))) break;
-        double f[256];
-        int32_t iv[256];
-        if ((rc = hip_check(hipMemcpyAsync(f, d_f, sizeof(f), hipMemcpyDeviceToHost, st), "copy f"))) break;
-        if ((rc = hip_check(hipMemcpyAsync(iv, d_i, sizeof(iv), hipMemcpyDeviceToHost, st), "copy i"))) break;
-        if ((rc = hip_check(hipStreamSynchronize(st), "sync"))) break;
-        if (out_f) memcpy(out_f, f, sizeof(f));
-        if (out_i) memcpy(out_i, iv, sizeof(iv));
-    } while (0);
-    (void)hipFree(d_rgb);
-    (void)hipFree(d_f);
-    (void)hipFree(d_i);
-    return rc;
+    DeviceBuf<uint8_t> d_rgb;
+    DeviceBuf<double> d_f;
+    DeviceBuf<int32_t> d_i;
+    if (int rc = d_rgb.alloc(48, "hipMalloc(rgb)")) return rc;
+    if (int rc = d_f.alloc(256, "hipMalloc(delta-E)")) return rc;
+    if (int rc = d_i.alloc(256, "hipMalloc(delta-E, int)")) return rc;
+    if (int rc = hip_check(hipMemcpyAsync(d_rgb, rgb, 48, hipMemcpyHostToDevice, st), "copy rgb")) return rc;
+    hipLaunchKernelGGL(cie2000_kernel, dim3(1), dim3(256), 0, st, d_rgb.get(), d_f.get(), d_i.get());
+    if (int rc = hip_check(hipGetLastError(), "cie2000_kernel launch")) return rc;
+    double f[256];
+    int32_t iv[256];
+    if (int rc = hip_check(hipMemcpyAsync(f, d_f, sizeof(f), hipMemcpyDeviceToHost, st), "copy f")) return rc;
+    if (int rc = hip_check(hipMemcpyAsync(iv, d_i, sizeof(iv), hipMemcpyDeviceToHost, st), "copy i")) return rc;
+    if (int rc = hip_check(hipStreamSynchronize(st), "sync")) return rc;
+    if (out_f) memcpy(out_f, f, sizeof(f));
+    if (out_i) memcpy(out_i, iv, sizeof(iv));
+    return IIV_OK;
 }
 
 }  // namespace iiv
