@@ -51,6 +51,7 @@ SYMBOLS = [
     "iiv_emit_stream", "iiv_emit_chunk", "iiv_frames_to_memory_maps",
     "iiv_audio_tick_count", "iiv_audio_ticks", "iiv_audio_resample", "iiv_audio_normalization",
     "iiv_resize_coeffs", "iiv_resize_frames",
+    "iiv_frames_to_memory_maps_mono",
 ]
 
 
@@ -173,6 +174,8 @@ def lib():
     if hasattr(L, "iiv_resize_frames") or "IIV_LIB" not in os.environ:
         L.iiv_resize_coeffs.argtypes = [i32, i32, C.POINTER(C.c_int), vp, vp]
         L.iiv_resize_frames.argtypes = [i32, i32, i32, vp, sz, sz, i32, i32, vp, vp]
+    if hasattr(L, "iiv_frames_to_memory_maps_mono") or "IIV_LIB" not in os.environ:
+        L.iiv_frames_to_memory_maps_mono.argtypes = [i32, i32, vp, i32, vp, vp, vp]
     if hasattr(L, "iiv_encoder_launch_forms") or "IIV_LIB" not in os.environ:
         L.iiv_encoder_launch_forms.argtypes = [vp, C.POINTER(C.c_int64)]
     for name in SYMBOLS:
@@ -180,7 +183,7 @@ def lib():
                                                  "iiv_encoder_live_queue", "iiv_encode_live", "iiv_encoder_set_state_async",
                                                  "iiv_audio_tick_count", "iiv_audio_ticks", "iiv_audio_resample",
                                                  "iiv_audio_normalization", "iiv_resize_coeffs",
-                                                 "iiv_resize_frames") and not hasattr(L, name):
+                                                 "iiv_resize_frames", "iiv_frames_to_memory_maps_mono") and not hasattr(L, name):
             continue   # (an older build under IIV_LIB: tools/ab_libs.sh)
         getattr(L, name)  # AttributeError if the library lacks a declared symbol
     _lib = L
@@ -753,6 +756,37 @@ def frames_to_memory_maps(mode, palette_rgb, rgb, dither=0, out=None):
         if mode != DHGR:
             aux = None
     check(lib().iiv_frames_to_memory_maps(mode, hptr(pal), n, dptr(rgb), int(dither), dptr(main), dptr(aux), stream_ptr()))
+    return main, aux
+
+
+# ---- f6: mono playback mode -----------------------------------------------------------
+
+MONO_SIZE = {HGR: (192, 280), DHGR: (192, 560)}   # (H, W) of a source frame: one pixel per dot of a monochrome screen
+
+
+def frames_to_memory_maps_mono(mode, rgb, dither=0, out=None):
+    """rgb: CUDA uint8 (n, 192, W, 3), W = 560 (DHGR) or 280 (HGR): one pixel per dot of a monochrome screen -> (main, aux)
+    CUDA uint8 (n, 32, 256); aux is None for HGR (include/iivision.h: iiv_frames_to_memory_maps_mono).
+    dither: 0..255 = amplitude of the 4x4 ordered dither, DITHER_DIFFUSION = Floyd-Steinberg over the dots.
+    out=(main, aux) and the asynchrony on torch's current stream: exactly as frames_to_memory_maps."""
+    torch = _torch()
+    if mode not in MONO_SIZE:
+        raise ValueError("mode must be HGR or DHGR")
+    shape = MONO_SIZE[mode] + (3,)
+    if not (rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 4 and tuple(rgb.shape[1:]) == shape and rgb.is_contiguous()):
+        raise ValueError("rgb must be a contiguous CUDA uint8 tensor (n, %d, %d, 3)" % shape[:2])
+    n = int(rgb.shape[0])
+    if out is None:
+        main = torch.empty((n, 32, 256), dtype=torch.uint8, device="cuda")
+        aux = torch.empty((n, 32, 256), dtype=torch.uint8, device="cuda") if mode == DHGR else None
+    else:
+        main, aux = out
+        for t in ((main, aux) if mode == DHGR else (main,)):
+            if not (t is not None and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n * 8192):
+                raise ValueError("out tensors must be contiguous CUDA uint8 tensors of n * 8192 bytes")
+        if mode != DHGR:
+            aux = None
+    check(lib().iiv_frames_to_memory_maps_mono(mode, n, dptr(rgb), int(dither), dptr(main), dptr(aux), stream_ptr()))
     return main, aux
 
 

@@ -41,17 +41,22 @@ class ArrayFrameGrabber(FrameGrabber):
     """Frames given as an array (n, 192, 280, 3) uint8 -- what FileFrameGrabber holds after its
     resize -- converted `batch` frames at a time by iiv_frames_to_memory_maps.  With resize=True the
     frames may be any size (n, h, w, 3) (1 <= h, w <= 8192): each is resized to 280x192 on the device
-    first, byte for byte as the reference's Image.resize((280, 192), LANCZOS) (frame_grabber.py:75,100)."""
+    first, byte for byte as the reference's Image.resize((280, 192), LANCZOS) (frame_grabber.py:75,100).
+    palette=Palette.MONO (a monochrome monitor): a frame is one pixel per DOT -- (192, 560) for DHGR,
+    (192, 280) for HGR --, resize=True resizes to that size, and the conversion is iiv_frames_to_memory_maps_mono."""
 
     def __init__(self, frames_rgb, mode: VideoMode, palette: Palette = Palette.NTSC, dither: int = 32,
                  input_frame_rate: float = 30, batch: int = 256, resize: bool = False):
         super().__init__(mode)
         rgb = np.asarray(frames_rgb)
+        mode_id = native.DHGR if mode == VideoMode.DHGR else native.HGR
+        self.frame_size = native.MONO_SIZE[mode_id] if palette == Palette.MONO else native.RESIZE_SIZE   # (H, W)
         if resize:
             if rgb.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[3] != 3:
                 raise ValueError("frames must be uint8 (n, h, w, 3) RGB")
-        elif rgb.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[1:] != (192, 280, 3):
-            raise ValueError("frames must be uint8 (n, 192, 280, 3) (frame_grabber.py:75: 280x192 RGB)")
+        elif rgb.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[1:] != self.frame_size + (3,):
+            raise ValueError("frames must be uint8 (n, %d, %d, 3)%s" % (self.frame_size + (
+                " (one pixel per dot of a monochrome screen)" if palette == Palette.MONO else " (frame_grabber.py:75: 280x192 RGB)",)))
         self._rgb = rgb
         self.resize = bool(resize)
         self.palette = palette
@@ -67,9 +72,11 @@ class ArrayFrameGrabber(FrameGrabber):
         import torch
         count = len(self._rgb) - first if count is None else count
         rgb = torch.from_numpy(np.ascontiguousarray(self._rgb[first:first + count])).cuda()
-        if self.resize and tuple(rgb.shape[1:3]) != native.RESIZE_SIZE:
-            rgb = native.resize_frames(rgb)   # on the same stream as the conversion below
+        if self.resize and tuple(rgb.shape[1:3]) != self.frame_size:
+            rgb = native.resize_frames(rgb, size=self.frame_size)   # on the same stream as the conversion below
         mode = native.DHGR if self.video_mode == VideoMode.DHGR else native.HGR
+        if self.palette == Palette.MONO:
+            return native.frames_to_memory_maps_mono(mode, rgb, self.dither)
         pal = palette_mod.PALETTES[self.palette].rgb_array()
         return native.frames_to_memory_maps(mode, pal, rgb, self.dither)
 

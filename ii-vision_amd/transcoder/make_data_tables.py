@@ -134,7 +134,20 @@ def make_edit_distance(pal: Type[palette.BasePalette], edp: EditDistanceParams,
     np.savez(data, edit_distance=dist)
 
 
-def main():
+def mono_substitute_costs():
+    """compute_substitute_costs for palette.MonoPalette: its diff matrix is a formula, not a colour distance."""
+    edp = EditDistanceParams()
+    dm = palette.MonoPalette.diff_matrix()
+    edp.diff_matrix = dm
+    idx = np.array([ord(c) for c in PIXEL_CHARS])
+    edp.substitute_costs[np.ix_(idx, idx)] = dm
+    edp.error_substitute_costs[np.ix_(idx, idx)] = 5 * dm
+    return edp
+
+
+def main(mono: bool = False):
+    """mono (not in the reference, default off): also write the two tables of palette.MonoPalette,
+    <MODE>_palette_100_edit_distance.npz; the reference's four files are written as ever."""
     os.makedirs(DATA_DIR, mode=0o755, exist_ok=True)
     t0 = time.time()
     for p in palette.PALETTES.values():
@@ -142,6 +155,11 @@ def main():
         edp = compute_substitute_costs(p)
         make_edit_distance(p, edp, screen.HGRBitmap, colours.HGRColours)
         make_edit_distance(p, edp, screen.DHGRBitmap, colours.DHGRColours)
+    if mono:
+        print("Processing palette %s" % palette.MonoPalette)
+        edp = mono_substitute_costs()
+        make_edit_distance(palette.MonoPalette, edp, screen.HGRBitmap, colours.HGRColours)
+        make_edit_distance(palette.MonoPalette, edp, screen.DHGRBitmap, colours.DHGRColours)
     print("make_data_tables: %.2f s" % (time.time() - t0))
 
 
@@ -261,4 +279,4 @@ if __name__ == "__main__":
     import sys
     if len(sys.argv) >= 2 and sys.argv[1] == "--verify":
         sys.exit(1 if verify(sys.argv[2] if len(sys.argv) > 2 else DATA_DIR) else 0)
-    main()
+    main(mono="--mono" in sys.argv[1:])

@@ -41,6 +41,7 @@ class Palette(enum.Enum):
     UNKNOWN = -1
     IIGS = 0
     NTSC = 5
+    MONO = 100   # a monochrome monitor: not a BMP2DHR palette number (MonoPalette below)
 
 
 class BasePalette:
@@ -78,7 +79,47 @@ class IIGSPalette(BasePalette):
                   (255, 153, 136), (34, 34, 255), (102, 170, 255), (0, 255, 153), (255, 255, 255)))
 
 
+def _popcount4(v):
+    return (v & 1) + ((v >> 1) & 1) + ((v >> 2) & 1) + ((v >> 3) & 1)
+
+
+class MonoPalette(BasePalette):
+    """A monochrome monitor (the reference README's "mono playback mode").  A colour value of the sliding-window model
+    is four dots, bit k the dot at screen position = k mod 4 (colours.py:100-134); a mono screen shows the dots
+    themselves, so what a change of colour value costs is the dots it changes -- diff_matrix() -- and no RGB
+    distance.  RGB is the grey of the lit share of the four dots, for display only."""
+    ID = Palette.MONO
+    RGB = {c: rgb(*(3 * ((255 * _popcount4(c.value) + 2) // 4,))) for c in HGRColours}
+
+    @classmethod
+    def diff_matrix(cls) -> np.ndarray:
+        """(16, 16) int32: dm[a][b] = 16 |popcount(a) - popcount(b)| + 8 popcount(a ^ b): how many dots are lit, and
+        which.  A metric; the smallest off-diagonal entry is 16, which keeps the reference's regime "a transpose (cost 1)
+        is always cheaper than a substitution" (make_data_tables.py:38-41); the largest is 96, and 96 x MASKED_DOTS
+        stays inside the 2047 iiv_encoder_create demands."""
+        a = np.arange(16)[:, None]
+        b = np.arange(16)[None, :]
+        return (16 * np.abs(_popcount4(a) - _popcount4(b)) + 8 * _popcount4(a ^ b)).astype(np.int32)
+
+
+# (exactly the reference's two: make_data_tables.main() writes one pair of files per entry)
 PALETTES = {
     Palette.IIGS: IIGSPalette,
     Palette.NTSC: NTSCPalette
 }  # type: Dict[Palette, Type[BasePalette]]
+
+
+def palette_class(palette_id: Palette) -> Type[BasePalette]:
+    """The palette class of an id, MONO included (PALETTES holds only the reference's colour palettes)."""
+    if palette_id == Palette.MONO:
+        return MonoPalette
+    return PALETTES[palette_id]
+
+
+def diff_matrix(palette_id: Palette) -> np.ndarray:
+    """The (16, 16) int32 substitution-cost matrix of a palette: CIE2000 between its colours (on the device), or the
+    mono dot distance."""
+    if palette_id == Palette.MONO:
+        return MonoPalette.diff_matrix()
+    import make_data_tables
+    return make_data_tables.compute_diff_matrix(PALETTES[palette_id])

@@ -306,8 +306,7 @@ class Bitmap:
             dist = np.load(data)["edit_distance"]
             table, store = native.load_table(cls.MODE, dist)
             return DeviceTable(cls.MODE, table, store, None)
-        import make_data_tables
-        dm = make_data_tables.compute_diff_matrix(pal.PALETTES[palette_id])
+        dm = pal.diff_matrix(palette_id)   # CIE2000 of the palette's colours; Palette.MONO: the dot distance
         table = native.build_table(cls.MODE, dm, symmetric=True)
         store = native.build_store_table(cls.MODE, dm)
         return DeviceTable(cls.MODE, table, store, dm)

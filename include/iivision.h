@@ -574,6 +574,34 @@ int iiv_resize_coeffs(int in_size, int out_size, int *ksize, int32_t *bounds, in
 int iiv_resize_frames(int n, int h, int w, const uint8_t *d_src, size_t frame_stride, size_t row_stride, int H, int W,
                       uint8_t *d_dst, void *stream);
 
+/* ==== f6: mono playback mode ================================================
+ * RGB frames -> memory maps for a MONOCHROME monitor (the reference README's "mono playback mode", not started there).
+ * On such a monitor a (D)HGR screen is a W x 192 one-bit picture, W = 560 dots (DHGR) or 280 (HGR), so the source frame
+ * has one pixel per dot.  Like f3 the conversion is SPECIFIED here, integer arithmetic only, so every implementation
+ * agrees bit for bit (tests/mono_model.py restates it; csrc/iiv_mono.hip computes it):
+ *   - luma Y = (77 R + 150 G + 29 B + 128) >> 8 of source pixel (X, y) = dot X of row y;
+ *   - ordered dither, amplitude `dither` 0..255: v = clamp(Y + floor((2 * B[y & 3][X & 3] - 15) * dither / 16), 0, 255), B the
+ *     4x4 Bayer matrix of f3; dot = v >= 128;
+ *   - dither == IIV_DITHER_DIFFUSION: Floyd-Steinberg over the W x 192 dots, rows top to bottom, dots left to right:
+ *     v = clamp(Y + floor(acc / 16), 0, 255), dot = v >= 128, e = v - 255 * dot; acc[right] += 7 e, acc[below left] += 3 e,
+ *     acc[below] += 5 e, acc[below right] += e (sixteenths; targets outside the picture are dropped); floor is towards
+ *     minus infinity, as in f3;
+ *   - packing: dot X goes to bit X % 7 of byte X / 7 of the row.  DHGR: even bytes of the row's 80 go to the aux bank and
+ *     odd ones to main, column X / 14 (screen.py:822-826).  HGR: the row's 40 bytes go to main (on a mono screen the palette
+ *     bit is only a half-dot shift: it stays clear).  Bit 7 is clear in both modes;
+ *   - bytes land at y_to_base_addr (screen.py:16-22); the screen holes are written as 0.
+ * The cost matrix that goes with it (palette.MonoPalette.diff_matrix(), host) prices a change of colour value a -> b of
+ * the sliding-window model -- four dots, bit k the dot at screen position = k mod 4 -- by the dots it changes:
+ * dm[a][b] = 16 |popcount(a) - popcount(b)| + 8 popcount(a ^ b); iiv_build_table / iiv_build_store_table /
+ * iiv_encoder_create take it as they take any 16 x 16 matrix.
+ * d_rgb: [n_frames][192][W][3] u8, 4-byte aligned; d_main / d_aux: [n_frames][32][256] u8 memory maps, 8-byte aligned (d_aux
+ * ignored for HGR).  IIV_ERR_INVALID for a bad mode, dither or alignment, before anything is launched.  Asynchronous on
+ * `stream`, as iiv_frames_to_memory_maps is: nothing synchronises, the error diffusion's scratch (the frames' luma in the
+ * order its lanes read it) is allocated and freed stream-ordered, so d_rgb, d_main and d_aux must stay alive and untouched
+ * until `stream` has reached the call. */
+int iiv_frames_to_memory_maps_mono(int mode, int n_frames, const uint8_t *d_rgb, int dither, uint8_t *d_main,
+                                   uint8_t *d_aux, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

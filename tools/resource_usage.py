@@ -19,6 +19,7 @@ def demangle(names):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
     res = []
     for n in out[:len(names)]:
+        n = n.replace("(anonymous namespace)::", "")
         n = re.sub(r"\(.*$", "", n)          # arguments off
         n = re.sub(r"^void ", "", n).replace("iiv::", "")
         res.append(n)

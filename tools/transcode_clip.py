@@ -10,6 +10,9 @@ cycle (`--tick`, 4..66 even: movie.py:104-107).
     python tools/transcode_clip.py --synthetic 90 --out /tmp/bars.a2m            # a moving test card
     python tools/transcode_clip.py --frames clip.npy --audio clip.wav --out clip.a2m
 
+--palette MONO: the stream is encoded for a monochrome monitor: frames are taken at one pixel per dot
+(560x192 for DHGR, 280x192 for HGR; anything else is resized to that), converted by csrc/iiv_mono.hip and priced by
+palette.MonoPalette.diff_matrix().
 --frames: uint8 array (n, h, w, 3) of any size (1 <= h, w <= 8192): frames that are not 280x192 are resized on the
 device, byte for byte as the reference's Image.resize((280, 192), LANCZOS) (frame_grabber.py:75,100; csrc/iiv_resize.hip);
 a (n, 192, 280, 3) array is taken as it is.  --dbg: the player's cc65 debug file, from which the opcode entry points are read exactly as
@@ -25,11 +28,12 @@ sys.path.insert(0, os.path.join(ROOT, "ii-vision_amd", "transcoder"))
 import numpy as np  # noqa: E402
 
 
-def test_card(n):
-    """n frames (192, 280, 3): colour bars drifting over a grey ramp"""
-    y, x = np.mgrid[0:192, 0:280]
+def test_card(n, width=280):
+    """n frames (192, width, 3): colour bars drifting over a grey ramp (width 560: the same card at one pixel per DHGR dot)"""
+    y, x = np.mgrid[0:192, 0:width]
+    x = x * 280 // width
     bars = np.array([[255, 255, 255], [255, 255, 0], [0, 255, 255], [0, 255, 0], [255, 0, 255], [255, 0, 0], [0, 0, 255], [0, 0, 0]], np.uint8)
-    out = np.empty((n, 192, 280, 3), np.uint8)
+    out = np.empty((n, 192, width, 3), np.uint8)
     for f in range(n):
         out[f] = bars[((x + 3 * f) // 35) % 8]
         out[f, 128:] = ((x[128:] + y[128:] - 2 * f) % 256)[..., None]
@@ -42,7 +46,8 @@ def main():
     ap.add_argument("--synthetic", type=int, default=0, help="instead of --frames: this many frames of a moving test card")
     ap.add_argument("--out", required=True)
     ap.add_argument("--mode", choices=["DHGR", "HGR"], default="DHGR")
-    ap.add_argument("--palette", choices=["NTSC", "IIGS"], default="NTSC")
+    ap.add_argument("--palette", choices=["NTSC", "IIGS", "MONO"], default="NTSC",
+                    help="MONO: a monochrome monitor -- one source pixel per dot (560x192 DHGR, 280x192 HGR), dot-level distances (DESIGN.md 12)")
     ap.add_argument("--dither", default="diffusion", help='"diffusion" (Floyd-Steinberg) or the amplitude 0..255 of the ordered dither')
     ap.add_argument("--dbg", help="player/iivision.dbg (opcode entry points)")
     ap.add_argument("--tick", type=int, default=34, help="without audio: speaker duty cycle of every opcode (4..66, even)")
@@ -73,14 +78,14 @@ def main():
     import stream_batch
     import video_mode
 
-    rgb = np.load(a.frames) if a.frames else test_card(a.synthetic)
     mode = native.DHGR if a.mode == "DHGR" else native.HGR
-    pal_id = palette.Palette.NTSC if a.palette == "NTSC" else palette.Palette.IIGS
+    pal_id = palette.Palette[a.palette]
+    rgb = np.load(a.frames) if a.frames else test_card(a.synthetic, native.MONO_SIZE[mode][1] if pal_id == palette.Palette.MONO else 280)
     t0 = time.perf_counter()
     grab = frame_grabber.ArrayFrameGrabber(rgb, video_mode.VideoMode[a.mode], pal_id,
                                            dither=a.dither if a.dither == "diffusion" else int(a.dither), resize=True)
     main_maps, aux_maps = grab.memory_maps()                       # (n, 32, 256) on the device
-    _, dm = native.cie2000_matrix(palette.PALETTES[pal_id].rgb_array())
+    dm = palette.diff_matrix(pal_id)                               # CIE2000 of the palette's colours; MONO: the dot distance
     table = native.build_table(mode, dm, True)
     store = native.build_store_table(mode, dm)
     torch.cuda.synchronize()
