@@ -30,30 +30,6 @@ OPT_CONTENT_CHOICE, CONTENT_TARGET, CONTENT_JOINT, CONTENT_JOINT_SPLIT = 6, 0, 1
 OPT_FOURTH_OFFSET = 7
 OPT_STREAM_ORDER = 8
 
-# every symbol include/iivision.h declares
-SYMBOLS = [
-    "iiv_version", "iiv_last_error", "iiv_device_count",
-    "iiv_masked_bits", "iiv_masked_dots", "iiv_num_offsets", "iiv_table_entries",
-    "iiv_store_table_entries",
-    "iiv_cie2000_matrix", "iiv_delta_e_cie2000", "iiv_pixel_strings", "iiv_build_table", "iiv_build_store_table",
-    "iiv_symmetrise_table", "iiv_store_table_from_table",
-    "iiv_pack", "iiv_diff_weights", "iiv_compute_delta_pages",
-    "iiv_encoder_create", "iiv_encoder_destroy", "iiv_encoder_set_option", "iiv_encoder_info",
-    "iiv_encoder_snapshot", "iiv_encoder_rollback", "iiv_encoder_snapshot_slot", "iiv_encoder_rollback_slot", "iiv_encoder_get_state", "iiv_encoder_set_state",
-    "iiv_encoder_set_state_range", "iiv_encoder_get_video_state", "iiv_encoder_set_video_state",
-    "iiv_encoder_get_video_brief", "iiv_encoder_get_video_brief_async",
-    "iiv_encode", "iiv_encode_streams", "iiv_encoder_live_queue", "iiv_encode_live", "iiv_encoder_set_state_async",
-    "iiv_encoder_check", "iiv_encoder_profile", "iiv_encoder_profile_read", "iiv_encoder_input_stats",
-    "iiv_encoder_launch_forms",
-    "iiv_build_split_store_table", "iiv_split_table_entries", "iiv_check_split_diff_table",
-    "iiv_build_narrow_store_table",
-    "iiv_check_diff_weight_pieces",
-    "iiv_emit_stream", "iiv_emit_chunk", "iiv_frames_to_memory_maps",
-    "iiv_audio_tick_count", "iiv_audio_ticks", "iiv_audio_resample", "iiv_audio_normalization",
-    "iiv_resize_coeffs", "iiv_resize_frames",
-    "iiv_frames_to_memory_maps_mono",
-]
-
 
 class Segment(C.Structure):
     _fields_ = [("frame", C.c_int32), ("is_aux", C.c_int32), ("restart", C.c_int32), ("n_ops", C.c_int32)]
@@ -86,11 +62,87 @@ class IIVAssertionError(AssertionError):
     """One of the reference's `assert`s fired on the device."""
 
 
+_vp, _i32, _sz, _lg, _u16 = C.c_void_p, C.c_int, C.c_size_t, C.c_long, C.c_uint16
+
+# The C ABI, declared once: name -> (restype, argtypes) of every function of include/iivision.h, in the header's order.
+# tests/test_abi.py compares each entry with the header's prototype; lib() applies them.
+_SIGNATURES = {
+    "iiv_version": (C.c_char_p, []),
+    "iiv_last_error": (C.c_char_p, []),
+    "iiv_device_count": (_i32, []),
+    # ---- mode constants
+    "iiv_masked_bits": (_i32, [_i32]),
+    "iiv_masked_dots": (_i32, [_i32]),
+    "iiv_num_offsets": (_i32, [_i32]),
+    "iiv_table_entries": (_sz, [_i32]),
+    "iiv_store_table_entries": (_sz, [_i32]),
+    # ---- P1: make_data_tables
+    "iiv_cie2000_matrix": (_i32, [_vp, _vp, _vp, _vp]),
+    "iiv_delta_e_cie2000": (_i32, [_i32, _vp, _vp, _vp, _vp]),
+    "iiv_pixel_strings": (_i32, [_i32, _vp, _vp, _vp]),
+    "iiv_build_table": (_i32, [_i32, _vp, _vp, _i32, _vp]),
+    "iiv_build_store_table": (_i32, [_i32, _vp, _vp, _vp]),
+    "iiv_symmetrise_table": (_i32, [_i32, _vp, _vp]),
+    "iiv_store_table_from_table": (_i32, [_i32, _vp, _vp, _vp]),
+    # ---- P2: screen.Bitmap operations
+    "iiv_pack": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),
+    "iiv_diff_weights": (_i32, [_i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "iiv_compute_delta_pages": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    # ---- P3: video.Video
+    "iiv_build_split_store_table": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp]),
+    "iiv_split_table_entries": (_sz, [_i32, _i32]),
+    "iiv_build_narrow_store_table": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp]),
+    "iiv_check_split_diff_table": (_i32, [_i32, _vp, _vp, _vp, _vp]),
+    "iiv_check_diff_weight_pieces": (_i32, [_i32, _vp, _vp, _vp, _vp]),
+    "iiv_encoder_create": (_i32, [_i32, _vp, _vp, _vp, _i32, C.POINTER(_vp)]),
+    "iiv_encoder_destroy": (None, [_vp]),
+    "iiv_encoder_set_option": (_i32, [_vp, _i32, _i32]),
+    "iiv_encoder_info": (_i32, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "iiv_encoder_get_state": (_i32, [_vp, _i32, _i32, _vp, _sz]),
+    "iiv_encoder_set_state": (_i32, [_vp, _i32, _i32, _vp, _sz]),
+    "iiv_encoder_set_state_async": (_i32, [_vp, _i32, _i32, _vp, _sz, _vp]),
+    "iiv_encoder_set_state_range": (_i32, [_vp, _i32, _i32, _i32, _vp, _sz]),
+    "iiv_encoder_get_video_state": (_i32, [_vp, _i32, C.POINTER(VideoState)]),
+    "iiv_encoder_set_video_state": (_i32, [_vp, _i32, C.POINTER(VideoState)]),
+    "iiv_encoder_get_video_brief": (_i32, [_vp, _i32, C.POINTER(VideoBrief)]),
+    "iiv_encoder_get_video_brief_async": (_i32, [_vp, _i32, C.POINTER(VideoBrief), _vp]),
+    "iiv_encoder_snapshot": (_i32, [_vp, _vp]),
+    "iiv_encoder_rollback": (_i32, [_vp, _vp]),
+    "iiv_encoder_snapshot_slot": (_i32, [_vp, _i32, _vp]),
+    "iiv_encoder_rollback_slot": (_i32, [_vp, _i32, _vp]),
+    "iiv_encode": (_i32, [_vp, _vp, _vp, _i32, C.POINTER(Segment), _i32, _vp, _vp]),
+    "iiv_encode_streams": (_i32, [_vp, _vp, _vp, _i32, C.POINTER(Segment), C.POINTER(C.c_int32), _vp, _sz, _vp]),
+    "iiv_encoder_live_queue": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int)]),
+    "iiv_encode_live": (_i32, [_vp, _vp, _vp, _i32, C.POINTER(Segment), _i32, _vp, _i32, C.c_uint32, _vp]),
+    "iiv_encoder_check": (_i32, [_vp, C.POINTER(C.c_int), _vp]),
+    "iiv_encoder_profile": (_i32, [_vp, _i32]),
+    "iiv_encoder_profile_read": (_i32, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "iiv_encoder_input_stats": (_i32, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "iiv_encoder_launch_forms": (_i32, [_vp, C.POINTER(C.c_int64)]),
+    # ---- f2: byte emission
+    "iiv_emit_stream": (_i32, [_i32, _i32, _lg, _vp, _vp, _vp, _u16, _u16, _lg, _vp, _sz, C.POINTER(_sz), _vp]),
+    # ---- f3: frame ingest (the header declares f2's slice emission behind it)
+    "iiv_frames_to_memory_maps": (_i32, [_i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "iiv_emit_chunk": (_i32, [_i32, _i32, _lg, _lg, _vp, _sz, _vp, _sz, _i32, _vp, _u16, _vp, _sz,
+                              C.POINTER(_sz), C.POINTER(_sz), _vp, _vp]),
+    # ---- f4: the audio track
+    "iiv_audio_tick_count": (_lg, [_lg, _i32, _i32, _lg]),
+    "iiv_audio_ticks": (_i32, [_i32, _vp, _sz, _vp, _vp, _vp, _i32, _lg, _vp, _vp, _sz, _vp, _vp]),
+    "iiv_audio_resample": (_i32, [_i32, _vp, _sz, _vp, _vp, _vp, _i32, _vp, _sz, _vp, _vp]),
+    "iiv_audio_normalization": (_i32, [_i32, _vp, _sz, _vp, _vp, _vp, _i32, _vp, _vp]),
+    # ---- f5: the resize
+    "iiv_resize_coeffs": (_i32, [_i32, _i32, C.POINTER(C.c_int), _vp, _vp]),
+    "iiv_resize_frames": (_i32, [_i32, _i32, _i32, _vp, _sz, _sz, _i32, _i32, _vp, _vp]),
+    # ---- f6: mono playback mode
+    "iiv_frames_to_memory_maps_mono": (_i32, [_i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+}
+SYMBOLS = list(_SIGNATURES)
+
 _lib = None
 
 
 def lib():
-    """Load libiivision.so; fails loudly if it has not been built."""
+    """Load libiivision.so and declare every function of _SIGNATURES on it; fails loudly if it has not been built."""
     global _lib
     if _lib is not None:
         return _lib
@@ -103,89 +155,14 @@ def lib():
     # in one process cannot both own the device.
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
-    vp, i32, sz = C.c_void_p, C.c_int, C.c_size_t
-    L.iiv_version.restype = C.c_char_p
-    L.iiv_last_error.restype = C.c_char_p
-    L.iiv_device_count.restype = i32
-    for f in ("iiv_masked_bits", "iiv_masked_dots", "iiv_num_offsets"):
-        getattr(L, f).restype = i32
-        getattr(L, f).argtypes = [i32]
-    for f in ("iiv_table_entries", "iiv_store_table_entries"):
-        getattr(L, f).restype = sz
-        getattr(L, f).argtypes = [i32]
-    L.iiv_cie2000_matrix.argtypes = [vp, vp, vp, vp]
-    L.iiv_delta_e_cie2000.argtypes = [i32, vp, vp, vp, vp]
-    L.iiv_pixel_strings.argtypes = [i32, vp, vp, vp]
-    L.iiv_build_table.argtypes = [i32, vp, vp, i32, vp]
-    L.iiv_build_store_table.argtypes = [i32, vp, vp, vp]
-    L.iiv_symmetrise_table.argtypes = [i32, vp, vp]
-    L.iiv_store_table_from_table.argtypes = [i32, vp, vp, vp]
-    L.iiv_pack.argtypes = [i32, i32, vp, vp, vp, vp]
-    L.iiv_diff_weights.argtypes = [i32, vp, i32, vp, vp, i32, vp, vp]
-    L.iiv_compute_delta_pages.argtypes = [i32, vp, i32, vp, vp, vp, vp, i32, vp, vp]
-    L.iiv_encoder_create.argtypes = [i32, vp, vp, vp, i32, C.POINTER(vp)]
-    L.iiv_encoder_set_option.argtypes = [vp, i32, i32]
-    if hasattr(L, "iiv_encoder_info") or "IIV_LIB" not in os.environ:
-        L.iiv_encoder_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.iiv_encoder_snapshot.argtypes = [vp, vp]
-    L.iiv_encoder_rollback.argtypes = [vp, vp]
-    L.iiv_encoder_snapshot_slot.argtypes = [vp, i32, vp]
-    L.iiv_encoder_rollback_slot.argtypes = [vp, i32, vp]
-    L.iiv_encoder_destroy.argtypes = [vp]
-    L.iiv_encoder_destroy.restype = None
-    L.iiv_encoder_get_state.argtypes = [vp, i32, i32, vp, sz]
-    L.iiv_encoder_set_state.argtypes = [vp, i32, i32, vp, sz]
-    L.iiv_encoder_set_state_range.argtypes = [vp, i32, i32, i32, vp, sz]
-    L.iiv_encoder_get_video_state.argtypes = [vp, i32, C.POINTER(VideoState)]
-    L.iiv_encoder_get_video_brief.argtypes = [vp, i32, C.POINTER(VideoBrief)]
-    if hasattr(L, "iiv_encoder_get_video_brief_async") or "IIV_LIB" not in os.environ:
-        L.iiv_encoder_get_video_brief_async.argtypes = [vp, i32, C.POINTER(VideoBrief), vp]
-    L.iiv_encoder_set_video_state.argtypes = [vp, i32, C.POINTER(VideoState)]
-    L.iiv_encode.argtypes = [vp, vp, vp, i32, C.POINTER(Segment), i32, vp, vp]
-    L.iiv_encode_streams.argtypes = [vp, vp, vp, i32, C.POINTER(Segment), C.POINTER(C.c_int32), vp, sz, vp]
-    if hasattr(L, "iiv_encode_live") or "IIV_LIB" not in os.environ:
-        L.iiv_encoder_live_queue.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_int)]
-        L.iiv_encode_live.argtypes = [vp, vp, vp, i32, C.POINTER(Segment), i32, vp, i32, C.c_uint32, vp]
-    if hasattr(L, "iiv_encoder_set_state_async") or "IIV_LIB" not in os.environ:
-        L.iiv_encoder_set_state_async.argtypes = [vp, i32, i32, vp, sz, vp]
-    L.iiv_build_split_store_table.argtypes = [i32, vp, vp, vp, vp, vp]
-    L.iiv_split_table_entries.restype = sz
-    L.iiv_check_split_diff_table.argtypes = [i32, vp, vp, vp, vp]
-    L.iiv_build_narrow_store_table.argtypes = [i32, vp, vp, vp, vp, vp]
-    if hasattr(L, "iiv_check_diff_weight_pieces") or "IIV_LIB" not in os.environ:   # (IIV_LIB: A/B runs against older builds, tools/ab_libs.sh)
-        L.iiv_check_diff_weight_pieces.argtypes = [i32, vp, vp, vp, vp]
-    L.iiv_split_table_entries.argtypes = [i32, i32]
-    L.iiv_encoder_check.argtypes = [vp, C.POINTER(i32), vp]
-    L.iiv_encoder_profile.argtypes = [vp, i32]
-    L.iiv_encoder_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    L.iiv_encoder_input_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]
-    L.iiv_emit_stream.argtypes = [i32, i32, C.c_long, vp, vp, vp, C.c_uint16, C.c_uint16, C.c_long, vp, sz,
-                                  C.POINTER(sz), vp]
-    L.iiv_emit_chunk.argtypes = [i32, i32, C.c_long, C.c_long, vp, sz, vp, sz, i32, vp, C.c_uint16, vp, sz,
-                                 C.POINTER(sz), C.POINTER(sz), vp, vp]
-    L.iiv_frames_to_memory_maps.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp]
-    if hasattr(L, "iiv_audio_ticks") or "IIV_LIB" not in os.environ:
-        lg = C.c_long
-        L.iiv_audio_tick_count.restype = lg
-        L.iiv_audio_tick_count.argtypes = [lg, i32, i32, lg]
-        L.iiv_audio_ticks.argtypes = [i32, vp, sz, vp, vp, vp, i32, lg, vp, vp, sz, vp, vp]
-        L.iiv_audio_resample.argtypes = [i32, vp, sz, vp, vp, vp, i32, vp, sz, vp, vp]
-        L.iiv_audio_normalization.argtypes = [i32, vp, sz, vp, vp, vp, i32, vp, vp]
-    if hasattr(L, "iiv_resize_frames") or "IIV_LIB" not in os.environ:
-        L.iiv_resize_coeffs.argtypes = [i32, i32, C.POINTER(C.c_int), vp, vp]
-        L.iiv_resize_frames.argtypes = [i32, i32, i32, vp, sz, sz, i32, i32, vp, vp]
-    if hasattr(L, "iiv_frames_to_memory_maps_mono") or "IIV_LIB" not in os.environ:
-        L.iiv_frames_to_memory_maps_mono.argtypes = [i32, i32, vp, i32, vp, vp, vp]
-    if hasattr(L, "iiv_encoder_launch_forms") or "IIV_LIB" not in os.environ:
-        L.iiv_encoder_launch_forms.argtypes = [vp, C.POINTER(C.c_int64)]
-    for name in SYMBOLS:
-        if "IIV_LIB" in os.environ and name in ("iiv_encoder_launch_forms", "iiv_check_diff_weight_pieces", "iiv_encoder_info", "iiv_encoder_get_video_brief_async",
-                                                 "iiv_encoder_live_queue", "iiv_encode_live", "iiv_encoder_set_state_async",
-                                                 "iiv_audio_tick_count", "iiv_audio_ticks", "iiv_audio_resample",
-                                                 "iiv_audio_normalization", "iiv_resize_coeffs",
-                                                 "iiv_resize_frames", "iiv_frames_to_memory_maps_mono") and not hasattr(L, name):
-            continue   # (an older build under IIV_LIB: tools/ab_libs.sh)
-        getattr(L, name)  # AttributeError if the library lacks a declared symbol
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        try:
+            f = getattr(L, name)
+        except AttributeError:
+            if "IIV_LIB" in os.environ:   # an A/B run against an older build (tools/ab_libs.sh) does without it
+                continue
+            raise AttributeError("%s does not export %s, which include/iivision.h declares" % (LIB_PATH, name)) from None
+        f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -271,11 +248,16 @@ def pixel_strings(mode):
     return dots.view(shape), pix.view(shape + (nd,))
 
 
+def _diff_matrix(dm):
+    """The 16x16 int diff matrix as the C ABI takes it: const int32_t dm[256]."""
+    return np.ascontiguousarray(dm, dtype=np.int32).reshape(256)
+
+
 def build_table(mode, dm, symmetric=True):
     """Device tensor (num_offsets, 2**(2*bits)) int16-typed storage of the u16 table."""
     torch = _torch()
     L = lib()
-    dm = np.ascontiguousarray(dm, dtype=np.int32).reshape(256)
+    dm = _diff_matrix(dm)
     bits = L.iiv_masked_bits(mode)
     out = torch.empty((L.iiv_num_offsets(mode), 1 << (2 * bits)), dtype=torch.int16, device="cuda")
     check(L.iiv_build_table(mode, hptr(dm), dptr(out), 1 if symmetric else 0, stream_ptr()))
@@ -285,7 +267,7 @@ def build_table(mode, dm, symmetric=True):
 def build_store_table(mode, dm):
     torch = _torch()
     L = lib()
-    dm = np.ascontiguousarray(dm, dtype=np.int32).reshape(256)
+    dm = _diff_matrix(dm)
     out = torch.empty(L.iiv_store_table_entries(mode), dtype=torch.int16, device="cuda")
     check(L.iiv_build_store_table(mode, hptr(dm), dptr(out), stream_ptr()))
     return out
@@ -295,7 +277,7 @@ def check_split_diff_table(mode, dm, table):
     """Number of entries of the full symmetric table that differ from the combination of the
     two halves of the split diff-weight table built from dm (0 = exact everywhere)."""
     _torch()
-    dm = np.ascontiguousarray(dm, dtype=np.int32).reshape(256)
+    dm = _diff_matrix(dm)
     n = C.c_ulonglong(0)
     check(lib().iiv_check_split_diff_table(mode, hptr(dm), dptr(table), C.byref(n), stream_ptr()))
     return int(n.value)
@@ -304,7 +286,7 @@ def check_split_diff_table(mode, dm, table):
 def check_diff_weight_pieces(mode, dm, table):
     """Entries of the full symmetric table that differ from the sum of pixel-pair terms the prologue
     evaluates instead of the recurrence (include/iivision.h: iiv_check_diff_weight_pieces); both modes."""
-    dm = np.ascontiguousarray(dm, dtype=np.int32).reshape(256)
+    dm = _diff_matrix(dm)
     n = C.c_ulonglong(0)
     check(lib().iiv_check_diff_weight_pieces(mode, hptr(dm), dptr(table), C.byref(n), stream_ptr()))
     return int(n.value)
@@ -315,7 +297,7 @@ def build_narrow_store_table(mode, dm, store):
     form of the split table (S = L1 + RF, two u16 tables), and the number of entries that differ
     from `store` (0 when both come from the same dm)."""
     torch = _torch()
-    dm = np.ascontiguousarray(dm, dtype=np.int32).reshape(256)
+    dm = _diff_matrix(dm)
     exp = torch.empty_like(store)
     n = C.c_ulonglong(0)
     check(lib().iiv_build_narrow_store_table(mode, hptr(dm), dptr(store), dptr(exp), C.byref(n), stream_ptr()))
@@ -327,7 +309,7 @@ def build_split_store_table(mode, dm, expanded=True):
     (optionally) the dense store table rebuilt from them with the encoder's index arithmetic."""
     torch = _torch()
     L = lib()
-    dm = np.ascontiguousarray(dm, dtype=np.int32).reshape(256)
+    dm = _diff_matrix(dm)
     left = torch.empty(L.iiv_split_table_entries(mode, 0), dtype=torch.int32, device="cuda")
     right = torch.empty(L.iiv_split_table_entries(mode, 1), dtype=torch.int32, device="cuda")
     exp = torch.empty(L.iiv_store_table_entries(mode), dtype=torch.int16, device="cuda") if expanded else None
@@ -406,41 +388,56 @@ def encoder_info(handle):
     return mode.value, n.value
 
 
+def _cuda_u8(t, name):
+    """ValueError unless t is a contiguous CUDA uint8 tensor."""
+    torch = _torch_mod or _torch()
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+        raise ValueError("%s must be a contiguous CUDA uint8 tensor" % name)
+
+
+def _frames_bank(t, name, n_streams):
+    """ValueError unless t is one bank of target frames, (n_streams, n_frames, 32, 256), as validate_frames wants it."""
+    _cuda_u8(t, name)
+    if t.dim() != 4 or tuple(t.shape[2:]) != (32, 256):
+        raise ValueError("%s has shape %s, not (n_streams, n_frames, 32, 256)" % (name, tuple(t.shape)))
+    if int(t.shape[0]) != n_streams:
+        raise ValueError("%s holds %d streams, the encoder was created for %d" % (name, int(t.shape[0]), n_streams))
+
+
 def validate_frames(handle, frames_main, frames_aux):
     """iiv_encode / iiv_encode_streams read n_streams x n_frames x 8192 bytes of every bank whatever the caller's tensors
     hold: refuse anything else here instead of letting a kernel read out of bounds.  Returns (n_streams, n_frames)."""
-    torch = _torch()
     mode, n_streams = encoder_info(handle)
-
-    def one(t, name):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
-            raise ValueError("%s must be a contiguous CUDA uint8 tensor (n_streams, n_frames, 32, 256)" % name)
-        if t.dim() != 4 or tuple(t.shape[2:]) != (32, 256):
-            raise ValueError("%s has shape %s, not (n_streams, n_frames, 32, 256)" % (name, tuple(t.shape)))
-        if int(t.shape[0]) != n_streams:
-            raise ValueError("%s holds %d streams, the encoder was created for %d" % (name, int(t.shape[0]), n_streams))
-
-    one(frames_main, "frames_main")
+    _frames_bank(frames_main, "frames_main", n_streams)
     n_frames = int(frames_main.shape[1])
     if n_frames <= 0:
         raise ValueError("frames_main holds no frame")
     if mode == DHGR:
         if frames_aux is None:
             raise ValueError("DHGR needs frames_aux")
-        one(frames_aux, "frames_aux")
+        _frames_bank(frames_aux, "frames_aux", n_streams)
         if int(frames_aux.shape[1]) != n_frames:
             raise ValueError("frames_aux holds %d frames per stream, frames_main %d" % (int(frames_aux.shape[1]), n_frames))
     elif frames_aux is not None:
-        one(frames_aux, "frames_aux")   # (HGR ignores it; a tensor of the wrong kind is still a caller's mistake)
+        _frames_bank(frames_aux, "frames_aux", n_streams)   # (HGR ignores it; a tensor of the wrong kind is still a caller's mistake)
     return n_streams, n_frames
 
 
 def validate_ops_out(ops_out, need_bytes):
-    torch = _torch()
-    if not (isinstance(ops_out, torch.Tensor) and ops_out.is_cuda and ops_out.dtype == torch.uint8 and ops_out.is_contiguous()):
-        raise ValueError("ops_out must be a contiguous CUDA uint8 tensor")
+    _cuda_u8(ops_out, "ops_out")
     if ops_out.numel() < need_bytes:
         raise ValueError("ops_out holds %d bytes, this call writes %d (n_streams * total opcodes * 6)" % (ops_out.numel(), need_bytes))
+
+
+def segment_array(segments):
+    """[(frame, is_aux, restart, n_ops), ...] -> the iiv_segment array of the C ABI (never of length 0: ctypes needs one entry)."""
+    return (Segment * max(len(segments), 1))(*[Segment(int(f), int(a), int(r), int(k)) for (f, a, r, k) in segments])
+
+
+def _state_array(what, value, n=None):
+    """`value` as the C ABI takes state item `what`: its dtype and shape (Encoder._ITEMS), n of them back to back if n is given."""
+    shape, dt = Encoder._ITEMS[what]
+    return np.ascontiguousarray(value, dtype=dt).reshape(shape if n is None else (n,) + shape)
 
 
 class Encoder:
@@ -457,7 +454,7 @@ class Encoder:
         h = C.c_void_p()
         dmp = C.c_void_p(0)
         if dm is not None:
-            self._dm = np.ascontiguousarray(dm, dtype=np.int32).reshape(256)
+            self._dm = _diff_matrix(dm)
             dmp = hptr(self._dm)
         check(lib().iiv_encoder_create(mode, dptr(table), dptr(store_table), dmp, self.n_streams, C.byref(h)))
         self._h = h
@@ -543,14 +540,13 @@ class Encoder:
         return out
 
     def set_state(self, what, value, stream=0):
-        shape, dt = self._ITEMS[what]
-        a = np.ascontiguousarray(value, dtype=dt).reshape(shape)
+        a = _state_array(what, value)
         check(lib().iiv_encoder_set_state(self._h, int(stream), what, hptr(a), a.nbytes))
 
     def set_state_async(self, what, value, stream=0):
         """STATE_OUT_OF_WORK / STATE_RNG_PY / STATE_RNG_NP of one stream, enqueued behind the launches already on the current
         HIP stream: no device-wide synchronisation (iiv_encoder_set_state_async)."""
-        shape, dt = self._ITEMS[what]
+        shape, dt = self._ITEMS[what]   # (_state_array, written out: the drop-in Video calls this once per generator)
         a = np.ascontiguousarray(value, dtype=dt).reshape(shape)
         check(lib().iiv_encoder_set_state_async(self._h, int(stream), what, hptr(a), a.nbytes, stream_ptr()))
 
@@ -574,11 +570,9 @@ class Encoder:
 
     def set_state_all(self, what, values, first=0):
         """values: (n, ...) array, item `what` of streams first .. first + n - 1 in one upload."""
-        shape, dt = self._ITEMS[what]
-        a = np.ascontiguousarray(values, dtype=dt)
-        n = a.shape[0]
-        a = a.reshape((n,) + shape)
-        check(lib().iiv_encoder_set_state_range(self._h, int(first), int(n), what, hptr(a), a[0].nbytes))
+        n = np.shape(values)[0]
+        a = _state_array(what, values, n)
+        check(lib().iiv_encoder_set_state_range(self._h, int(first), n, what, hptr(a), a[0].nbytes))
 
     def encode_streams(self, frames_main, frames_aux, schedules, ops_out=None):
         """Per-stream schedules: schedules[s] = list of (frame, is_aux, restart, n_ops) of stream s.
@@ -588,7 +582,7 @@ class Encoder:
         if len(schedules) != self.n_streams:
             raise ValueError("%d schedules for %d streams" % (len(schedules), self.n_streams))
         flat = [g for sch in schedules for g in sch]
-        segs = (Segment * max(len(flat), 1))(*[Segment(int(f), int(a), int(r), int(k)) for (f, a, r, k) in flat])
+        segs = segment_array(flat)
         begin = np.zeros(self.n_streams + 1, dtype=np.int32)
         begin[1:] = np.cumsum([len(sch) for sch in schedules])
         totals = [sum(int(g[3]) for g in sch) for sch in schedules]
@@ -609,7 +603,7 @@ class Encoder:
         (n_streams, total_ops, 6).  Asynchronous."""
         torch = _torch()
         _, n_frames = validate_frames(self._h, frames_main, frames_aux)
-        segs = (Segment * max(len(segments), 1))(*[Segment(int(f), int(a), int(r), int(k)) for (f, a, r, k) in segments])
+        segs = segment_array(segments)
         total = sum(int(s[3]) for s in segments)
         need = self.n_streams * total * 6
         if ops_out is None:
@@ -637,9 +631,9 @@ class Encoder:
         keep it off the team kernel."""
         _, n_frames = validate_frames(self._h, frames_main, frames_aux)
         f, a, r, k = segment
-        seg = (Segment * 1)(Segment(int(f), int(a), int(r), int(k)))
+        seg = Segment(int(f), int(a), int(r), int(k))
         validate_ops_out(ops_out, self.n_streams * int(k) * 6)
-        check(lib().iiv_encode_live(self._h, dptr(frames_main), dptr(frames_aux), int(n_frames), seg, 1, dptr(ops_out),
+        check(lib().iiv_encode_live(self._h, dptr(frames_main), dptr(frames_aux), int(n_frames), C.byref(seg), 1, dptr(ops_out),
                                     int(slot), int(tag), stream_ptr()))
 
     def snapshot(self, slot=0):
@@ -730,6 +724,22 @@ def emit_chunk(mode, ops, first_op, d_tick_addr, ack_addr, out, ticks=None, cons
 DITHER_DIFFUSION = 256   # IIV_DITHER_DIFFUSION: Floyd-Steinberg error diffusion instead of the ordered dither
 
 
+def _memory_maps_out(mode, n, out):
+    """The (main, aux) memory maps an ingest call writes: new (n, 32, 256) tensors, or the caller's out=(main, aux) once they
+    are known to hold n * 8192 bytes each; aux is None for HGR."""
+    torch = _torch()
+    if out is None:
+        main = torch.empty((n, 32, 256), dtype=torch.uint8, device="cuda")
+        aux = torch.empty((n, 32, 256), dtype=torch.uint8, device="cuda") if mode == DHGR else None
+        return main, aux
+    main, aux = out
+    for t in ((main, aux) if mode == DHGR else (main,)):
+        _cuda_u8(t, "each out tensor")
+        if t.numel() != n * 8192:
+            raise ValueError("each out tensor must hold n * 8192 bytes")
+    return main, aux if mode == DHGR else None
+
+
 def frames_to_memory_maps(mode, palette_rgb, rgb, dither=0, out=None):
     """rgb: CUDA uint8 (n, 192, 280, 3) -> (main, aux) CUDA uint8 (n, 32, 256); aux is None for HGR.
     dither: 0..255 = amplitude of the 4x4 ordered dither, DITHER_DIFFUSION = error diffusion.
@@ -740,21 +750,12 @@ def frames_to_memory_maps(mode, palette_rgb, rgb, dither=0, out=None):
     safe as they are (the caching allocator re-uses a freed block on that stream only behind its pending work); tensors
     that belong to ANOTHER stream -- a conversion on a side stream writing into the encoder's target buffers, as bench.py's
     e2e leg does -- need tensor.record_stream(torch.cuda.current_stream()) or an event between the streams."""
-    torch = _torch()
-    if not (rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 4 and tuple(rgb.shape[1:]) == (192, 280, 3) and rgb.is_contiguous()):
-        raise ValueError("rgb must be a contiguous CUDA uint8 tensor (n, 192, 280, 3)")
+    _cuda_u8(rgb, "rgb")
+    if tuple(rgb.shape[1:]) != (192, 280, 3):
+        raise ValueError("rgb has shape %s, not (n, 192, 280, 3)" % (tuple(rgb.shape),))
     n = int(rgb.shape[0])
     pal = np.ascontiguousarray(palette_rgb, dtype=np.uint8).reshape(48)
-    if out is None:
-        main = torch.empty((n, 32, 256), dtype=torch.uint8, device="cuda")
-        aux = torch.empty((n, 32, 256), dtype=torch.uint8, device="cuda") if mode == DHGR else None
-    else:
-        main, aux = out
-        for t in ((main, aux) if mode == DHGR else (main,)):
-            if not (t is not None and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n * 8192):
-                raise ValueError("out tensors must be contiguous CUDA uint8 tensors of n * 8192 bytes")
-        if mode != DHGR:
-            aux = None
+    main, aux = _memory_maps_out(mode, n, out)
     check(lib().iiv_frames_to_memory_maps(mode, hptr(pal), n, dptr(rgb), int(dither), dptr(main), dptr(aux), stream_ptr()))
     return main, aux
 
@@ -769,23 +770,13 @@ def frames_to_memory_maps_mono(mode, rgb, dither=0, out=None):
     CUDA uint8 (n, 32, 256); aux is None for HGR (include/iivision.h: iiv_frames_to_memory_maps_mono).
     dither: 0..255 = amplitude of the 4x4 ordered dither, DITHER_DIFFUSION = Floyd-Steinberg over the dots.
     out=(main, aux) and the asynchrony on torch's current stream: exactly as frames_to_memory_maps."""
-    torch = _torch()
     if mode not in MONO_SIZE:
         raise ValueError("mode must be HGR or DHGR")
-    shape = MONO_SIZE[mode] + (3,)
-    if not (rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 4 and tuple(rgb.shape[1:]) == shape and rgb.is_contiguous()):
-        raise ValueError("rgb must be a contiguous CUDA uint8 tensor (n, %d, %d, 3)" % shape[:2])
+    _cuda_u8(rgb, "rgb")
+    if tuple(rgb.shape[1:]) != MONO_SIZE[mode] + (3,):
+        raise ValueError("rgb has shape %s, not (n, %d, %d, 3)" % ((tuple(rgb.shape),) + MONO_SIZE[mode]))
     n = int(rgb.shape[0])
-    if out is None:
-        main = torch.empty((n, 32, 256), dtype=torch.uint8, device="cuda")
-        aux = torch.empty((n, 32, 256), dtype=torch.uint8, device="cuda") if mode == DHGR else None
-    else:
-        main, aux = out
-        for t in ((main, aux) if mode == DHGR else (main,)):
-            if not (t is not None and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n * 8192):
-                raise ValueError("out tensors must be contiguous CUDA uint8 tensors of n * 8192 bytes")
-        if mode != DHGR:
-            aux = None
+    main, aux = _memory_maps_out(mode, n, out)
     check(lib().iiv_frames_to_memory_maps_mono(mode, n, dptr(rgb), int(dither), dptr(main), dptr(aux), stream_ptr()))
     return main, aux
 
@@ -906,8 +897,10 @@ def resize_frames(rgb, size=RESIZE_SIZE, out=None):
     n, h, w = (int(v) for v in rgb.shape[:3])
     if out is None:
         out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=rgb.device)
-    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n * H * W * 3):
-        raise ValueError("out must be a contiguous CUDA uint8 tensor of n * %d * %d * 3 bytes" % (H, W))
+    else:
+        _cuda_u8(out, "out")
+        if out.numel() != n * H * W * 3:
+            raise ValueError("out must hold n * %d * %d * 3 bytes" % (H, W))
     with torch.cuda.device(rgb.device):
         check(lib().iiv_resize_frames(n, h, w, dptr(rgb), int(rgb.stride(0)), int(rgb.stride(1)), H, W, dptr(out),
                                       stream_ptr()))
