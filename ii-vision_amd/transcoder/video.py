@@ -1,59 +1,45 @@
 """Encode a sequence of images as an optimized stream of screen changes -- on the GPU.
 
-Host-side mirror of the reference's transcoder/video.py: `Video` keeps the same
-constructor, attributes (memory_map, aux_memory_map, pixelmap, update_priority,
-aux_update_priority, out_of_work, frame_number) and methods (tick, encode_frame),
-and `encode_frame` is still a lazy, never-ending generator of
-(page, content, offsets) tuples.  The work -- diff weights, priority ranking, the
-greedy selection loop and both MT19937 nonce streams -- runs in the gfx950 kernels
-of csrc/iiv_prologue.hip / iiv_greedy.hip / iiv_team.hip through iiv_encode() (csrc/iiv_encode.hip, include/iivision.h).
+Host-side mirror of the reference's transcoder/video.py: `Video` keeps the same constructor, attributes (memory_map,
+aux_memory_map, pixelmap, update_priority, aux_update_priority, out_of_work, frame_number) and methods (tick, encode_frame),
+and `encode_frame` is still a lazy, never-ending generator of (page, content, offsets) tuples.  The work -- diff weights,
+priority ranking, the greedy selection loop and both MT19937 nonce streams -- runs in the gfx950 kernels behind iiv_encode()
+(include/iivision.h).  Batched, many-stream encoding (what bench.py measures) goes through stream_batch.StreamBatch instead.
 
-State model: the device holds the live state while a generator runs; the host numpy
-arrays (memory maps, update priorities, pixelmap.packed, out_of_work) and Python's /
-NumPy's global RNG states are brought up to date *when somebody looks*: reading any of
-the state attributes brings everything; starting another generator brings the RNG positions
-and out_of_work (5 KB), and carries to the device whatever the caller changed in between --
-arrays it was handed, a reseeded or advanced `random` / `np.random` -- so code that pokes
-`video.memory_map.page_offset` or reseeds `random` between frames keeps working: the same
-points at which the reference's caller (movie.py) looks.
-`Video.STRICT_SYNC = True` restores the literal behaviour (every next() round-trips the
-whole state, global RNG states included), at about 1.5 k opcodes per second.
-Limitation of the default (lightweight) sync: WHILE a generator is live, the host's global
-`random` / `np.random` states are the stale pre-launch ones.  A caller that draws from or reseeds
-them between two next() calls of the same live generator (the reference's movie.py never does) and
-then starts another generator has its draws applied on top of that stale state, which rewinds the
-device's stream: the opcode stream then differs from the reference's.  Drawing or reseeding BETWEEN
-generators -- after the previous one was abandoned, exhausted or its state read -- is supported;
-for anything else set STRICT_SYNC.
+What lives where.  While a generator runs the device holds the live state: memory maps, update priorities, the packed
+pixelmap, out_of_work and the positions of both global generators (`random`, `np.random`: global_rng.py).  The host's copies
+are brought up to date when somebody looks -- the points at which the reference's caller (movie.py) looks:
+  - reading a state attribute settles any speculation and brings everything (300 KB);
+  - starting another generator, or abandoning one, brings the RNG positions and out_of_work -- the 5 KB "brief", which
+    travels home behind every launch -- and carries to the device what the caller changed in between: arrays it was
+    handed, a reseeded or advanced `random` / `np.random`, the fresh out_of_work dict of movie.py:96.
+`Video.STRICT_SYNC = True` is the literal behaviour instead: every next() round-trips the whole state, global RNG states
+included, at about 1.5 k opcodes per second.
+Limitation of the default: WHILE a generator is live the host's global `random` / `np.random` states are the stale pre-launch
+ones.  A caller that draws from or reseeds them between two next() calls of the same live generator (movie.py never does)
+and then starts another generator has its draws applied on top of that stale state, which rewinds the device's stream: the
+opcode stream then differs from the reference's.  Drawing or reseeding BETWEEN generators -- after the previous one was
+abandoned, exhausted or its state read -- is supported; for anything else set STRICT_SYNC.
 
-Budget: a generator may be abandoned after any next() (movie.py:94-109 does so at
-every frame and bank flip), and its side effects must then be exactly those of
-the opcodes consumed.  Without a hint every next() is therefore one device step.
-`encode_frame(target, is_aux, budget=K)` promises that K opcodes will be pulled;
-they are then computed by one launch.  `Video.SPECULATE = N` (default: what one generator of movie.py's
-pacing can be asked for -- 292 opcodes, the gap between two DHGR bank flips, or a frame's worth in HGR; 0 = one device
-step per next()) gets batched launches without a promise: N opcodes are produced from a
-device-side snapshot and rolled back + replayed if fewer were consumed.  Batched, many-stream encoding
-(what bench.py measures) goes through stream_batch.StreamBatch instead.
-
-Look-ahead (round 6, `Video.LOOKAHEAD`): behind a movie.py-paced DHGR generator whose opcodes end at a bank flip, the generator
-the caller will start next -- the other bank of the SAME target (movie.py:139-148) -- is enqueued at once, on a second
-snapshot, so that the device computes it while Python hands out this generator's opcodes.  If encode_frame() is then called
-with that target and bank (and nobody touched the state or the global generators in between) its launch has already run; if not,
-the snapshot is restored and nothing of it is observable.
-
-Live hand-over (round 6, `Video.LIVE`): a speculative launch no longer has to END before its first opcode is handed out.  The
-eight-wave team kernel writes every opcode, as one tagged 8-byte store, into a queue in coherent host memory
-(include/iivision.h: iiv_encode_live), and the generator yields opcode i as soon as slot i carries the launch's tag -- while the
-kernel works on i + 1.  One clip's chain of steps runs at ~0.55 us per opcode on the device, about what a Python caller takes
-to pull one: the two now overlap instead of adding up.  What is observable is unchanged: a generator abandoned after k opcodes
-is rolled back and replayed for exactly k, as before; a launch that ends short (one of the reference's asserts) marks the queue
-behind its last opcode, and the generator then steps exactly from there, so the next() that raises in the reference raises here.
+How many opcodes a launch computes.  A generator may be abandoned after any next() (movie.py:94-109 does so at every frame
+and bank flip), and its side effects must then be exactly those of the opcodes consumed.
+  - `encode_frame(target, is_aux, budget=K)` promises that K opcodes will be pulled: one launch, nothing to undo.
+  - `Video.SPECULATE = N` batches without a promise: N opcodes are produced from a device-side snapshot; if fewer were
+    consumed the snapshot is restored and exactly those are replayed.  None (default): N is what movie.py's pacing will pull,
+    as far as tick() and the bank flips seen so far tell (_paced_chunk); 0 or 1: one device step per next().
+  - `Video.LOOKAHEAD`: behind a movie.py-paced DHGR generator whose opcodes end at a bank flip, the generator the caller
+    starts next -- the other bank of the SAME target (movie.py:139-148) -- is enqueued at once on a second snapshot, into a
+    second set of buffers.  If encode_frame() is then called for that bank and target, nothing touched in between, its
+    launch has already run and the buffer sets change places; if not, the snapshot is restored and nothing of it shows.
+  - `Video.LIVE`: a speculative (or promised) launch's opcodes are handed out WHILE the kernel produces them: it writes
+    each as one tagged 8-byte store into a queue in coherent host memory (iiv_encode_live), and opcode i is yielded as soon
+    as slot i carries the launch's tag.  A launch that ends short (one of the reference's asserts) marks the queue behind its
+    last opcode; the generator then steps exactly from there, so the next() that raises in the reference raises here.
+None of the four changes an opcode or anything observable, only the speed.  How this came about: DESIGN_HISTORY.md.
 """
 
 import ctypes
 import operator
-import random
 import time
 from typing import Iterator, List, Tuple
 
@@ -61,126 +47,89 @@ import numpy as np
 
 import _iiv_native as native
 import screen
+from global_rng import np_random, py_random
 from palette import Palette
 from video_mode import VideoMode
 
-_np_global = [None, None]   # [the bit generator the address below belongs to, that address or 0 = "use get_state / set_state"]
+
+class _Token:
+    """One encode_frame() generator: its bank, its target (host copies and the device buffers they go to), whether its
+    prologue has run."""
+    __slots__ = ("is_aux", "main", "aux", "fm", "fa", "started")
 
 
-def _np_rng_addr():
-    """Address of the process-wide np.random MT19937 state -- key[624] (u32) then pos (i32), the words np.random.get_state()
-    reports -- through numpy's own ctypes interface (BitGenerator.ctypes.state_address): reading and writing 2500 bytes there
-    costs under a microsecond where get_state() / set_state() cost ~50 each, twice per generator.  The layout is numpy's
-    private business (mt19937_state: uint32 key[624]; int pos), so the address is believed only after the bytes there have
-    been seen to BE what get_state() reports, before and after a draw that moves the position; if they are not, 0 is
-    returned and this module goes through get_state() / set_state() (slower, same results)."""
-    bg = np.random.mtrand._rand._bit_generator
-    if _np_global[0] is not bg:
-        if type(bg).__name__ != "MT19937":
-            raise RuntimeError("np.random's global generator is not the MT19937 the reference draws from")
-        addr = 0
-        try:
-            cand = int(bg.ctypes.state_address)
+class _LiveView:
+    """A live launch as its consumer (_live_take) sees it: host queue `q`, the tag its slots carry, its `n` opcodes, and the
+    event behind the brief that follows it.  q16 / q8: the queue's tags -- the top quarter of every slot -- and its bytes."""
+    __slots__ = ("q", "q16", "q8", "tag", "n", "event")
 
-            def same():
-                _, key, pos = np.random.get_state()[:3]
-                raw = np.frombuffer(ctypes.string_at(cand, 2500), dtype=np.uint32)
-                return bool(np.array_equal(raw[:624], np.asarray(key, dtype=np.uint32)) and int(raw[624]) == int(pos))
-            saved = np.random.get_state()
-            ok = same()
-            np.random.random_sample()           # (moves pos, or refills the block)
-            ok = ok and same()
-            np.random.set_state(saved)          # (the caller's stream is where it was)
-            if ok and same():
-                addr = cand
-        except Exception:
-            addr = 0
-        _np_global[0], _np_global[1] = bg, addr
-    return _np_global[1]
+    def __init__(self, q, tag, n, event=None):
+        self.q, self.tag, self.n, self.event = q, tag, n, event
+        self.q16, self.q8 = q.view(np.uint16).reshape(-1, 4)[:, 3], q.view(np.uint8).reshape(-1, 8)
 
 
-def _np_rng_raw():
-    """np.random's MT19937 words as 2500 bytes: key[624], pos"""
-    addr = _np_rng_addr()
-    if addr:
-        return ctypes.string_at(addr, 2500)
-    _, key, pos = np.random.get_state()[:3]
-    return np.asarray(key, dtype=np.uint32).tobytes() + np.array([pos], dtype=np.int32).tobytes()
+class _Launch:
+    """What _launch returns: the n opcodes as an array (in pinned memory, filled by the time the stream is waited for), or
+    the live view they arrive through."""
+    __slots__ = ("ops", "live", "n")
+
+    def __init__(self, n, ops=None, live=None):
+        self.n, self.ops, self.live = n, ops, live
 
 
-def _np_rng_write(words):
-    """the 625 words (ctypes array / buffer of 2500 bytes) become np.random's MT19937 state; has_gauss / cached_gaussian stay the caller's"""
-    addr = _np_rng_addr()
-    if addr:
-        with np.random.mtrand._rand._bit_generator.lock:   # (the generator's own lock: nobody draws while the words change)
-            ctypes.memmove(addr, words, 2500)
-        return
-    w = np.frombuffer(bytes(words), dtype=np.uint32)
-    old = np.random.get_state()
-    np.random.set_state((old[0], w[:624].copy(), int(w[624].astype(np.int32) if hasattr(w[624], "astype") else w[624]), old[3], old[4]))
+class _Ahead:
+    """The generator enqueued ahead of the caller: what it was launched for, on which snapshot, and its launch."""
+    __slots__ = ("is_aux", "main", "aux", "slot", "launch")
+
+    def __init__(self, is_aux, main, aux, slot, launch):
+        self.is_aux, self.main, self.aux, self.slot, self.launch = is_aux, main, aux, slot, launch
 
 
-_py_global = [None, None]   # [the random.Random instance the address belongs to, that address or 0 = "use getstate / setstate"]
+class _Buffers:
+    """Where one generator's launch lands: the opcode buffer on the device, the pinned one it is copied home into, and the
+    pinned brief (vb: the ctypes view of vb_mem) -- with how far that brief has got:
+      stale      it does not describe the device state as it stands (fresh is False);
+      sent       it does, and is here or on its way -- behind `event`, if there is one -- but the host's global RNG positions
+                 and out_of_work have yet to be set from it (fresh, not applied);
+      done       they have been (fresh, applied).
+    A Video has two: the live generator's and the look-ahead's; adopting the look-ahead exchanges them."""
+    __slots__ = ("ops_dev", "ops_host", "vb_mem", "vb", "fresh", "applied", "event")
 
+    def __init__(self):
+        self.ops_dev = self.ops_host = self.vb_mem = None
+        self.vb = native.VideoBrief()       # (pinned with the first launch: torch is needed for it)
+        self.fresh, self.applied, self.event = False, True, None
 
-def _py_rng_addr():
-    """Address of `index` in the process-wide `random` generator's C struct (CPython _randommodule.c RandomObject: PyObject_HEAD,
-    int index, uint32_t state[624]) -- random.getstate()[1] is state[0..623] followed by index.  getstate() builds a tuple of 625
-    ints and setstate() parses one (~15 and ~40 microseconds, both at every generator start); the 2500 bytes themselves move in
-    under one.  The layout is CPython's private business, so -- as for np.random above -- the address is believed only after
-    the bytes there have been seen to BE what getstate() reports, before and after a draw and after a write through it; if
-    not, 0 is returned and this module goes through getstate() / setstate() (slower, same results)."""
-    inst = getattr(random, "_inst", None)
-    if _py_global[0] is not inst or inst is None:
-        addr = 0
-        try:
-            if inst is not None and random.getstate.__self__ is inst and type(inst).__mro__[1].__name__ == "Random":
-                cand = id(inst) + object.__basicsize__      # (PyObject_HEAD of a non-GC base: refcount, type)
+    def reserve(self, n_ops=0):
+        """room for n_ops opcodes, and the brief in page-locked memory: it is also fetched behind a launch, asynchronously"""
+        import torch
+        if self.vb_mem is None:
+            self.vb_mem = torch.empty(ctypes.sizeof(native.VideoBrief), dtype=torch.uint8).pin_memory()
+            self.vb = native.VideoBrief.from_address(self.vb_mem.data_ptr())
+        if self.ops_dev is None or self.ops_dev.shape[1] < n_ops:
+            cap = max(n_ops, 2048)
+            self.ops_dev = torch.empty((1, cap, 6), dtype=torch.uint8, device="cuda")
+            self.ops_host = torch.empty((cap, 6), dtype=torch.uint8).pin_memory()
 
-                def same():
-                    words = np.array(random.getstate()[1], dtype=np.uint32)
-                    raw = np.frombuffer(ctypes.string_at(cand, 2500), dtype=np.uint32)
-                    return bool(np.array_equal(raw[1:], words[:624]) and raw[0] == words[624])
-                saved = random.getstate()
-                try:
-                    ok = same()
-                    random.getrandbits(8)               # (moves index, or refills the block)
-                    ok = ok and same()
-                    if ok:
-                        probe = np.arange(7, 7 + 625, dtype=np.uint32)
-                        probe[0] = 3                    # index
-                        ctypes.memmove(cand, probe.ctypes.data, 2500)
-                        got = random.getstate()[1]
-                        ok = got[624] == 3 and got[:624] == tuple(range(8, 8 + 624))
-                finally:
-                    random.setstate(saved)              # (the caller's stream is where it was)
-                if ok and same():
-                    addr = cand
-        except Exception:
-            addr = 0
-        _py_global[0], _py_global[1] = inst, addr
-    return _py_global[1]
+    def stale(self, launch=False):
+        """launch: a launch is about to write the brief anew -- whatever was still on its way is no longer waited for"""
+        self.fresh = False
+        if launch:
+            self.event = None
 
+    def sent(self, event=None):
+        self.fresh, self.applied = True, False
+        if event is not None:
+            self.event = event
 
-def _py_rng_raw():
-    """random's MT19937 words as 2500 bytes in getstate() order: state[624], index"""
-    addr = _py_rng_addr()
-    if addr:
-        return ctypes.string_at(addr + 4, 2496) + ctypes.string_at(addr, 4)
-    return np.array(random.getstate()[1], dtype=np.uint32).tobytes()
+    def wait(self):
+        """the brief has arrived (behind a live launch it arrives with the launch's end)"""
+        if self.event is not None:
+            self.event.synchronize()
+            self.event = None
 
-
-def _py_rng_write(words):
-    """the 625 words (getstate() order; a ctypes array / buffer of 2500 bytes) become random's state; gauss_next is cleared, as
-    random.setstate((3, words, None)) would"""
-    addr = _py_rng_addr()
-    if addr:
-        base = ctypes.addressof(words) if isinstance(words, ctypes.Array) else np.frombuffer(words, dtype=np.uint8).ctypes.data
-        ctypes.memmove(addr + 4, base, 2496)
-        ctypes.memmove(addr, base + 2496, 4)
-        random._inst.gauss_next = None
-        return
-    random.setstate((3, tuple(np.frombuffer(bytes(words), dtype=np.uint32).tolist()), None))
+    def done(self):
+        self.applied = True
 
 
 class _Chunk:
@@ -213,36 +162,22 @@ class Video:
 
     CLOCK_SPEED = 1024 * 1024  # type: int
 
-    #: Opcodes produced per device call when encode_frame() got no `budget`.
-    #: 0 or 1 = one exact step per next().  N > 1 = speculate: N opcodes are produced
-    #: from a device-side snapshot; if the generator is abandoned (or any state
-    #: attribute is read) after k < N of them were consumed, the snapshot is restored
-    #: and exactly k are replayed, so observable state is always that of the consumed
-    #: opcodes.  Nothing observable depends on it (an assertion of the reference that would
-    #: fire inside the unconsumed part of a chunk makes the generator fall back to exact
-    #: stepping), only the speed does.
-    #: None (default): the number of opcodes movie.py's pacing will pull from this generator, as far as this object can tell
-    #: from what the caller has shown it (_paced_chunk): tick() tells it the tick count, so the tick that starts the next
-    #: frame is known (video.py:64-70); a generator started for the other bank without a new frame was a bank flip, and the
-    #: next one comes 292 opcodes later (2044 bytes of a 2 KiB socket frame / 7, movie.py:139-148).  A right guess is one
-    #: launch and nothing to roll back; a wrong one costs a roll-back or a second launch, never a different opcode.
-    #: Without tick() calls: DHGR 292, HGR a frame's worth (ticks_per_frame).
+    # The four switches below change the speed only, never an opcode (module docstring).
+    #: Opcodes produced per device call when encode_frame() got no `budget`: 0 or 1 = one exact step per next(); N > 1 = N
+    #: from a snapshot, rolled back and replayed if fewer were consumed (an assertion of the reference that would fire inside
+    #: the unconsumed part of a chunk makes the generator fall back to exact stepping).  None (default): what movie.py's
+    #: pacing will pull (_paced_chunk): tick() tells the tick count, so the tick that starts the next frame is known
+    #: (video.py:64-70); a generator started for the other bank without a new frame was a bank flip, and the next one comes
+    #: 292 opcodes later (2044 bytes of a 2 KiB socket frame / 7, movie.py:139-148).  A right guess is one launch and nothing
+    #: to roll back; a wrong one costs a roll-back or a second launch.  Without tick() calls: DHGR 292, HGR a frame's worth.
     SPECULATE = None
-
-    #: True: after every next() the host arrays and the *global* random / np.random states
-    #: are those of the reference at that point (one full state round trip per opcode).
-    #: False (default): the arrays are synchronised whenever a state attribute is read, the global
-    #: RNG positions and out_of_work also whenever another generator starts (a 5 KB round trip:
-    #: iiv_encoder_get_video_brief); draws from / reseeds of random or np.random between two
-    #: generators are noticed and carried to the device.
+    #: True: after every next() the host arrays and the *global* random / np.random states are those of the reference at
+    #: that point (one full state round trip per opcode).  False (default): synchronised when somebody looks.
     STRICT_SYNC = False
-
-    #: True (default): run one generator ahead of a movie.py-paced caller (module docstring).  Speed only.
+    #: True (default): run one generator ahead of a movie.py-paced caller.
     LOOKAHEAD = True
-
-    #: True (default): hand the opcodes of a speculative launch out WHILE the kernel produces them (module docstring: live
-    #: hand-over) instead of after it has ended.  Speed only; encoders whose options keep them off the team kernel
-    #: (joint_content) fall back by themselves.
+    #: True (default): hand the opcodes of a launch out WHILE the kernel produces them.  Encoders whose options keep them off
+    #: the team kernel (joint_content) fall back by themselves.
     LIVE = True
     LIVE_TIMEOUT = 20.0   # seconds without a new opcode before the launch is declared dead
 
@@ -274,21 +209,18 @@ class Video:
         self._host_current = True  # host arrays / global RNG states equal the device's
         self._touched = True  # a state attribute was handed out since the last upload
 
-        # Empty screen (video.py:37-53); the pixelmap aliases the memory maps
+        # Empty screen (video.py:37-53), the pixelmap aliasing the memory maps; pending edit weights, accumulated across
+        # frames (video.py:55-58)
         self._memory_map = screen.MemoryMap(screen_page=1)
-        self._aux_memory_map = None
+        self._update_priority = np.zeros((32, 256), dtype=np.int32)
+        self._aux_memory_map = self._aux_update_priority = None
         if self.mode == VideoMode.DHGR:
             self._aux_memory_map = screen.MemoryMap(screen_page=1)
+            self._aux_update_priority = np.zeros((32, 256), dtype=np.int32)
             self._pixelmap = screen.DHGRBitmap(
                 palette=palette, main_memory=self._memory_map, aux_memory=self._aux_memory_map)
         else:
             self._pixelmap = screen.HGRBitmap(palette=palette, main_memory=self._memory_map)
-
-        # Pending edit weights, accumulated across frames (video.py:55-58)
-        self._update_priority = np.zeros((32, 256), dtype=np.int32)
-        self._aux_update_priority = None
-        if self.mode == VideoMode.DHGR:
-            self._aux_update_priority = np.zeros((32, 256), dtype=np.int32)
 
         # True once the main / aux bank has run out of work (video.py:60-62)
         self._out_of_work = {True: False, False: False}
@@ -302,36 +234,33 @@ class Video:
             self._enc.set_fourth_offset(True)
         self._live = None  # the generator whose state the device currently holds
         self._vs = native.VideoState()   # one staging buffer for every state round trip
-        self._vb_mem = None              # the brief lives in pinned memory: it is also fetched behind a launch, asynchronously
-        self._vb = native.VideoBrief()
-        self._brief_applied = True       # what self._vb says about the global RNG positions / out_of_work has reached the host
+        # the live generator's buffers and brief; the look-ahead's (its results must not overwrite the live generator's)
+        self._bufs, self._ahead_bufs = _Buffers(), _Buffers()
         self._rng_seen = None  # the global (random, np.random) states as this object last left or read them
-        self._brief_fresh = False  # self._vb describes the device state as it stands
         self._dev_main = self._dev_aux = None   # the live generator's target on the device
         self._up_main = self._up_aux = None     # ... and what was last copied there (a bank flip within a frame re-uses it)
-        self._ops_dev = self._ops_host = None   # opcode buffers: device, and pinned host memory the launch copies into
         # what the caller's pacing has shown so far (only the size of speculative launches depends on it)
         self._tick_now = None     # the latest tick() argument
         self._ops_done = 0        # opcodes consumed from settled chunks
         self._flip_base = -1      # _ops_done at the last bank flip seen (movie.py's first socket frame holds 291 opcodes)
         self._last_bank = None    # is_aux of the latest generator that ran
-        # the generator enqueued ahead of the caller (LOOKAHEAD): None, or what it was launched for and where its results land
-        self._ahead = None
+        self._ahead = None        # the generator enqueued ahead of the caller (LOOKAHEAD): None or an _Ahead
         self.lookahead_stats = {"launched": 0, "adopted": 0, "undone": 0}   # (what became of the generators enqueued ahead)
-        self._ahead_bufs = None   # second set of opcode / brief buffers (the look-ahead's results must not overwrite the live generator's)
         # live hand-over: the two host queues the team kernel writes opcodes into (None until first used; False: this encoder's
-        # launches do not run that kernel), the tag of the latest launch, the event behind the brief that follows a launch
+        # launches do not run that kernel) and the tag of the latest launch
         self._live_q = None
         self._live_tag = 0
         self._live_epoch = 0             # how often the tag has started over; per queue: the epoch it was last cleared in
         self._live_q_epoch = [0, 0]
-        self._brief_event = None
         # (launches handed out live; polls of the queue; polls that found nothing and waited, and for how long)
         self.live_stats = {"launches": 0, "takes": 0, "waits": 0, "wait_s": 0.0, "first_wait_s": 0.0}
 
     # ---- the reference's public attributes; reading one settles any speculation first
-    def _settled(name):  # noqa: N805
+    def _settled(name, optional=False):  # noqa: N805
+        """optional: an HGR Video has none (video.py:40-42), and nobody assigns one"""
         def get(self):
+            if optional and getattr(self, name) is None:
+                raise AttributeError(name[1:])
             self._settle()
             self._touched = True  # the caller may change what it gets
             return getattr(self, name)
@@ -340,17 +269,14 @@ class Video:
             self._settle()
             self._touched = True
             setattr(self, name, value)
-        return property(get, set_)
+        return property(get, None if optional else set_)
 
     memory_map = _settled("_memory_map")
     pixelmap = _settled("_pixelmap")
     update_priority = _settled("_update_priority")
-
-    @property
-    def out_of_work(self):
-        self._settle()
-        self._touched = True
-        return self._out_of_work
+    aux_memory_map = _settled("_aux_memory_map", optional=True)
+    aux_update_priority = _settled("_aux_update_priority", optional=True)
+    out_of_work = _settled("_out_of_work")
 
     @out_of_work.setter
     def out_of_work(self, value):
@@ -362,27 +288,10 @@ class Video:
             self._enc.set_state_async(native.STATE_OUT_OF_WORK, np.array([int(bool(value[False])), int(bool(value[True]))], np.int32))
             # (the brief at hand stays good: the two flags are all that changed on the device, and they are known -- once it HAS
             # arrived: a brief still on its way behind a live launch would land on top of what is written here)
-            if self._brief_event is not None:
-                self._brief_event.synchronize()
-                self._brief_event = None
-            self._vb.out_of_work[0] = int(bool(value[False]))
-            self._vb.out_of_work[1] = int(bool(value[True]))
-
-    @property
-    def aux_memory_map(self):
-        if self._aux_memory_map is None:
-            raise AttributeError("aux_memory_map")  # HGR Video has none (video.py:40-42)
-        self._settle()
-        self._touched = True
-        return self._aux_memory_map
-
-    @property
-    def aux_update_priority(self):
-        if self._aux_update_priority is None:
-            raise AttributeError("aux_update_priority")
-        self._settle()
-        self._touched = True
-        return self._aux_update_priority
+            b = self._bufs
+            b.wait()
+            b.vb.out_of_work[0] = int(bool(value[False]))
+            b.vb.out_of_work[1] = int(bool(value[True]))
 
     del _settled
 
@@ -432,9 +341,8 @@ class Video:
         if dhgr:
             st.array("mem_aux", np.uint8, (32, 256))[...] = self._aux_memory_map.page_offset
             st.array("up_aux", np.int32, (32, 256))[...] = self._aux_update_priority
-        py = _py_rng_raw()
+        py, raw = py_random.raw(), np_random.raw()
         st.array("rng_py", np.uint32, (625,))[...] = np.frombuffer(py, dtype=np.uint32)
-        raw = _np_rng_raw()
         st.array("rng_np", np.uint32, (625,))[...] = np.frombuffer(raw, dtype=np.uint32)
         self._rng_seen = (py, raw)
         # movie.py:96 resets the flags at every frame
@@ -442,7 +350,7 @@ class Video:
         st.out_of_work[1] = int(bool(self._out_of_work[True]))
         self._enc.set_video_state(st)
         self._touched = False
-        self._brief_fresh = False
+        self._bufs.stale()
 
     def _download(self):
         """Device state -> host, one call; in place: callers (and self.pixelmap) hold references to the arrays."""
@@ -464,88 +372,69 @@ class Video:
 
     def _set_global_rng(self, st):
         """the device's random / np.random positions (st.rng_py, st.rng_np) become the process's"""
-        _py_rng_write(st.rng_py)
-        _np_rng_write(st.rng_np)
+        py_random.write(st.rng_py)
+        np_random.write(st.rng_np)
         self._rng_seen = (bytes(st.rng_py), bytes(st.rng_np))
 
     def _global_rng_moved(self):
         """did anyone draw from / reseed random or np.random since this object last synchronised them?"""
         if self._rng_seen is None:
             return True
-        return (_py_rng_raw(), _np_rng_raw()) != self._rng_seen
+        return (py_random.raw(), np_random.raw()) != self._rng_seen
 
     def _upload_rng(self):
-        pyraw = _py_rng_raw()
-        py = np.frombuffer(pyraw, dtype=np.uint32).copy()
-        raw = _np_rng_raw()
-        rn = np.frombuffer(raw, dtype=np.uint32).copy()
-        self._enc.set_state_async(native.STATE_RNG_PY, py)
-        self._enc.set_state_async(native.STATE_RNG_NP, rn)
-        self._brief_fresh = False
-        self._rng_seen = (pyraw, raw)
-
-    def _pinned_brief(self):
-        """self._vb in page-locked memory (allocated with the first launch: torch is needed for it)"""
-        if self._vb_mem is None:
-            import ctypes
-            import torch
-            self._vb_mem = torch.empty(ctypes.sizeof(native.VideoBrief), dtype=torch.uint8).pin_memory()
-            self._vb = native.VideoBrief.from_address(self._vb_mem.data_ptr())
-        return self._vb
+        py, raw = py_random.raw(), np_random.raw()
+        self._enc.set_state_async(native.STATE_RNG_PY, np.frombuffer(py, dtype=np.uint32).copy())
+        self._enc.set_state_async(native.STATE_RNG_NP, np.frombuffer(raw, dtype=np.uint32).copy())
+        self._bufs.stale()
+        self._rng_seen = (py, raw)
 
     def _sync_brief(self):
         """Settle the device state and bring home the small things: global RNG positions, out_of_work
         (and the numbers encode_frame prints / asserts).  The arrays stay on the device.  The brief itself usually is at
         hand already: it travels behind every launch (_launch), valid as long as the launch's opcodes are all consumed."""
-        self._settle(download=False, keep_ahead=self._brief_fresh)   # (a brief must be fetched: the device must stand where the caller is)
+        b = self._bufs
+        self._settle(download=False, keep_ahead=b.fresh)   # (a brief must be fetched: the device must stand where the caller is)
         if self._host_current:
             return None  # nothing on the device is newer than what the host holds
-        if not self._brief_fresh:
-            self._enc.get_video_brief(out=self._pinned_brief())
-            self._brief_fresh = True
-            self._brief_applied = False
-        b = self._vb
-        if self._brief_event is not None:
-            # (a live launch: its opcodes were handed out while it ran; the brief behind it arrives with its end)
-            self._brief_event.synchronize()
-            self._brief_event = None
-        if not self._brief_applied:
+        if not b.fresh:
+            b.reserve()
+            self._enc.get_video_brief(out=b.vb)
+            b.sent()
+        b.wait()    # (a live launch: its opcodes were handed out while it ran; the brief behind it arrives with its end)
+        if not b.applied:
             if not self._global_rng_moved():  # (else the caller's draws / reseed win: uploaded at the next launch)
-                self._set_global_rng(b)
-            self._out_of_work[False] = bool(b.out_of_work[0])
-            self._out_of_work[True] = bool(b.out_of_work[1])
-            self._brief_applied = True
-        return b
+                self._set_global_rng(b.vb)
+            self._out_of_work[False] = bool(b.vb.out_of_work[0])
+            self._out_of_work[True] = bool(b.vb.out_of_work[1])
+            b.done()
+        return b.vb
 
-    def _launch_buffers(self, n_ops):
-        import torch
-        if self._ops_dev is None or self._ops_dev.shape[1] < n_ops:
-            cap = max(n_ops, 2048)
-            self._ops_dev = torch.empty((1, cap, 6), dtype=torch.uint8, device="cuda")
-            self._ops_host = torch.empty((cap, 6), dtype=torch.uint8).pin_memory()
-
-    def _launch(self, token, restart, n_ops, fetch=True):
-        """[prologue +] n_ops greedy steps on the device state as it stands.  fetch=False: a replay of opcodes the caller has
-        already consumed (after a roll-back): nothing to bring home and nothing that can fail -- the speculative launch they
-        came from passed its check, and this is a prefix of it -- so the launch is only enqueued."""
-        import torch
-        self._brief_fresh = False
-        self._brief_event = None
+    def _launch(self, token, is_aux, restart, n_ops, bufs, qslot=None, fetch=True, wait=True):
+        """[prologue +] n_ops greedy steps on the device state as it stands, landing in `bufs`.
+        qslot: try the live hand-over through that host queue first (_launch_live).  Otherwise, or if this encoder cannot, the
+        plain launch: the opcodes and the brief of the state behind them ride home on the stream, one wait for everything
+        (check() synchronises and raises what the reference's asserts would; wait=False leaves it to whoever adopts the result).
+        fetch=False: a replay of opcodes the caller has already consumed (after a roll-back): nothing to bring home and nothing
+        that can fail -- it is a prefix of a launch that passed its check -- so it is only enqueued."""
         n_ops = int(n_ops)
-        self._launch_buffers(n_ops)
-        ops = self._enc.encode(token.fm, token.fa, [(0, int(bool(token.is_aux)), int(restart), n_ops)], ops_out=self._ops_dev)
+        bufs.stale(launch=True)
+        bufs.reserve(n_ops)
+        if qslot is not None:
+            live = self._launch_live(token, is_aux, restart, n_ops, qslot, bufs)
+            if live is not None:
+                bufs.sent(live.event)
+                return _Launch(n_ops, live=live)
+        ops = self._enc.encode(token.fm, token.fa, [(0, int(bool(is_aux)), int(restart), n_ops)], ops_out=bufs.ops_dev)
         self._host_current = False
         if not fetch:
             return None
-        # the opcodes and the brief of the state behind them ride home on the stream, one wait for everything: if the caller
-        # pulls all of them -- the rule when the launch was sized by its pacing -- the next generator starts without
-        # another round trip
-        self._ops_host[:n_ops].copy_(ops[0], non_blocking=True)
-        self._enc.get_video_brief_async(self._pinned_brief())
-        self._enc.check()
-        self._brief_fresh = True
-        self._brief_applied = False
-        return self._ops_host[:n_ops].numpy()
+        bufs.ops_host[:n_ops].copy_(ops[0], non_blocking=True)
+        self._enc.get_video_brief_async(bufs.vb)
+        if wait:
+            self._enc.check()
+        bufs.sent()
+        return _Launch(n_ops, ops=bufs.ops_host[:n_ops].numpy())
 
     def _live_queues(self):
         """the two host queues of the live hand-over, or None if this Video does without (LIVE off, or its encoder's
@@ -560,10 +449,10 @@ class Video:
                 return None
         return self._live_q
 
-    def _launch_live(self, token, is_aux, restart, n_ops, qslot, ops_dev, vb):
-        """[prologue +] n_ops greedy steps, the opcodes appearing one by one in host queue `qslot` under a fresh tag; the brief
-        of the state behind them follows into `vb` (pinned), an event behind it.  Nothing waits.  Returns what the consumer
-        needs (_live_take), or None -- nothing launched -- if this encoder cannot (the caller then launches the old way)."""
+    def _launch_live(self, token, is_aux, restart, n_ops, qslot, bufs):
+        """_launch's live form: the opcodes appear one by one in host queue `qslot` under a fresh tag; the brief of the state
+        behind them follows into bufs.vb, an event behind it.  Nothing waits.  Returns what the consumer needs (_live_take), or
+        None -- nothing launched -- if this encoder cannot."""
         import torch
         qs = self._live_queues()
         if qs is None or n_ops > len(qs[qslot]):
@@ -581,26 +470,24 @@ class Video:
             qs[qslot][:] = 0
             self._live_q_epoch[qslot] = self._live_epoch
         try:
-            self._enc.encode_live(token.fm, token.fa, (0, int(bool(is_aux)), int(restart), int(n_ops)), ops_dev, qslot, self._live_tag)
+            self._enc.encode_live(token.fm, token.fa, (0, int(bool(is_aux)), int(restart), int(n_ops)), bufs.ops_dev, qslot, self._live_tag)
         except native.IIVError as e:
             if e.code != native.ERR_INVALID:
                 raise
             self._live_q = False     # (refused before anything was launched: options that keep the encoder off the team kernel)
             return None
         self._host_current = False
-        self._enc.get_video_brief_async(vb)
+        self._enc.get_video_brief_async(bufs.vb)
         ev = torch.cuda.Event()
         ev.record()
         self.live_stats["launches"] += 1
-        q = qs[qslot]
-        # (views of the queue: the tags as uint16 -- the top quarter of every slot --, the slots as bytes)
-        return dict(q=q, q16=q.view(np.uint16).reshape(-1, 4)[:, 3], q8=q.view(np.uint8).reshape(-1, 8), tag=self._live_tag, n=int(n_ops), event=ev)
+        return _LiveView(qs[qslot], self._live_tag, n_ops, ev)
 
     def _live_take(self, lv, k):
         """Opcodes k .. of a live launch that have arrived -- at least one: this waits for slot k -- as a list of
         (page, content, offsets) tuples, and whether the launch ENDED behind them, short of its n_ops (then the list may be
         empty)."""
-        q, tag, n = lv["q"], lv["tag"], lv["n"]
+        q, tag, n = lv.q, lv.tag, lv.n
         st = self.live_stats
         st["takes"] += 1
         if (int(q[k]) >> 48) != tag:
@@ -618,9 +505,9 @@ class Video:
             if k == 0:
                 st["first_wait_s"] += dt     # (of that: for a launch's first opcode -- its prologue, mostly)
         # the slots from k on that carry the tag, up to the first that does not (the waves of a round commit in any order)
-        ok = lv["q16"][k:n] == tag
+        ok = lv.q16[k:n] == tag
         r = int(ok.argmin()) or len(ok)      # (slot k carries it: argmin is 0 only when all of them do)
-        b = lv["q8"][k:k + r]
+        b = lv.q8[k:k + r]
         # an end mark is the last slot its launch writes: if it has arrived it is the last of these
         ended = int(b[r - 1, 0]) == 0xFF
         if ended:
@@ -630,8 +517,7 @@ class Video:
     def _look_ahead(self, token, n_live, slot):
         """Behind the live generator's launch (its n_live opcodes are in hand): if they end at a bank flip inside the frame,
         enqueue the generator movie.py:139-148 starts next -- the other bank, the same target -- on snapshot `slot`, with the
-        opcodes and the brief of the state behind them copied to a second set of pinned buffers.  Nothing waits."""
-        import torch
+        opcodes and the brief of the state behind them copied to the second set of pinned buffers.  Nothing waits."""
         why = []
         self._paced_chunk(after=0, why=why)        # what ends the live generator's count as the pacing stands
         # (the live chunk was sized by this very call before its launch; only a count that a bank flip ended has a successor
@@ -641,41 +527,21 @@ class Video:
         n = self._paced_chunk(after=n_live, flipped=True)
         if n < 1:
             return
-        if self._ahead_bufs is None:
-            self._ahead_bufs = dict(
-                ops_dev=torch.empty((1, 2048, 6), dtype=torch.uint8, device="cuda"),
-                ops_host=torch.empty((2048, 6), dtype=torch.uint8).pin_memory(),
-                vb_mem=torch.empty(ctypes.sizeof(native.VideoBrief), dtype=torch.uint8).pin_memory())
-        bufs = self._ahead_bufs
         self._enc.snapshot(slot)
-        vb = native.VideoBrief.from_address(bufs["vb_mem"].data_ptr())
-        lv = self._launch_live(token, not token.is_aux, 1, int(n), slot, bufs["ops_dev"], vb)
-        if lv is None:
-            ops = self._enc.encode(token.fm, token.fa, [(0, int(not token.is_aux), 1, int(n))], ops_out=bufs["ops_dev"])
-            bufs["ops_host"][:n].copy_(ops[0], non_blocking=True)
-            self._enc.get_video_brief_async(vb)
-        self._host_current = False
-        self._ahead = dict(is_aux=not token.is_aux, main=token.main, aux=token.aux, n=int(n), slot=slot, live=lv)
+        launch = self._launch(token, not token.is_aux, 1, n, self._ahead_bufs, qslot=slot, wait=False)
+        self._ahead = _Ahead(not token.is_aux, token.main, token.aux, slot, launch)
         self.lookahead_stats["launched"] += 1
 
     def _adopt(self, a):
         """The generator enqueued ahead is the one the caller asked for: its launch has run (or is running); wait, check, and
-        swap the buffer sets so that the brief and the opcodes of this generator are the current ones."""
-        lv = a.get("live")
-        if lv is None:
+        exchange the buffer sets so that the brief -- sent, behind the launch's event if it is live -- and the opcodes of this
+        generator are the current ones."""
+        if a.launch.live is None:
             self._enc.check()      # (synchronises; raises what the reference's asserts would)
         self.lookahead_stats["adopted"] += 1
-        bufs = self._ahead_bufs
-        self._pinned_brief()
-        bufs["ops_host"], self._ops_host = self._ops_host, bufs["ops_host"]
-        bufs["ops_dev"], self._ops_dev = self._ops_dev, bufs["ops_dev"]
-        bufs["vb_mem"], self._vb_mem = self._vb_mem, bufs["vb_mem"]
-        self._vb = native.VideoBrief.from_address(self._vb_mem.data_ptr())
+        self._bufs, self._ahead_bufs = self._ahead_bufs, self._bufs
         self._host_current = False
-        self._brief_fresh = True
-        self._brief_applied = False
-        self._brief_event = lv["event"] if lv is not None else None
-        return (None, lv) if lv is not None else (self._ops_host[:a["n"]].numpy(), None)
+        return a.launch
 
     def _settle(self, download=True, keep_ahead=False):
         """Make the device state -- and, with download, the host's -- reflect exactly the opcodes consumed so far.
@@ -694,16 +560,16 @@ class Video:
             self._ahead = None
             self.lookahead_stats["undone"] += 1
             if not partial:
-                # back to the state behind the live generator's opcodes (what self._vb describes, if it is fresh)
-                self._enc.rollback(a["slot"])
+                # back to the state behind the live generator's opcodes (what the brief describes, if it is fresh)
+                self._enc.rollback(a.slot)
                 self._host_current = False
         if partial:
             # abandoned mid-chunk: restore the snapshot and replay only what was consumed (a look-ahead behind it goes with it)
             self._enc.rollback(p.slot)
             self._host_current = False
-            self._brief_fresh = False   # (what travelled behind the launch describes all of its opcodes)
+            self._bufs.stale()   # (what travelled behind the launch describes all of its opcodes)
             if consumed:
-                self._launch(p.token, p.restart, consumed, fetch=False)
+                self._launch(p.token, p.token.is_aux, p.restart, consumed, self._bufs, fetch=False)
             elif p.restart:
                 self._live = p.prev_live  # the prologue never happened
                 p.token.started = False
@@ -746,10 +612,8 @@ class Video:
     def _index_changes(self, target_pixelmap, is_aux, budget):
         import torch
 
-        class _Token:
-            started = False
-
         token = _Token()
+        token.started = False
         token.is_aux = bool(is_aux)
         # the target lives in ONE pair of device buffers per Video (only the latest generator can run,
         # see below); this generator's copy goes there when it starts, after the previous one is settled
@@ -777,10 +641,10 @@ class Video:
                     # is this the generator that was enqueued ahead?  Same bank, same target bytes, the live generator's
                     # opcodes all consumed, nothing touched, nobody drew from the global generators since
                     a = self._ahead
-                    ok = (paced and not self._touched and not self.STRICT_SYNC and a["is_aux"] == token.is_aux
+                    ok = (paced and not self._touched and not self.STRICT_SYNC and a.is_aux == token.is_aux
                           and (self._pending is None or self._pending.consumed() == self._pending.produced)
-                          and np.array_equal(a["main"], token.main)
-                          and (token.aux is None or np.array_equal(a["aux"], token.aux)) and not self._global_rng_moved())
+                          and np.array_equal(a.main, token.main)
+                          and (token.aux is None or np.array_equal(a.aux, token.aux)) and not self._global_rng_moved())
                     self._settle(download=False, keep_ahead=ok)
                     if ok and self._ahead is a:
                         adopt, self._ahead = a, None
@@ -805,101 +669,74 @@ class Video:
                     if token.aux is not None and (self._up_aux is None or not np.array_equal(self._up_aux, token.aux)):
                         self._dev_aux.copy_(torch.from_numpy(token.aux))
                         self._up_aux = token.aux
-                slot = 0
-                live = None     # the launch's opcodes arrive one by one in a host queue (LIVE): what _live_take needs
-                if speculative:
-                    try:
-                        if adopt is not None:
-                            slot = adopt["slot"]
-                            ops, live = self._adopt(adopt)
-                            chunk = adopt["n"]
-                        else:
-                            self._enc.snapshot(slot)
-                            self._brief_fresh = False
-                            self._brief_event = None
-                            self._launch_buffers(chunk)
-                            live = self._launch_live(token, token.is_aux, restart, chunk, slot, self._ops_dev, self._pinned_brief())
-                            if live is not None:
-                                self._brief_fresh = True
-                                self._brief_applied = False
-                                self._brief_event = live["event"]
-                            else:
-                                ops = self._launch(token, restart, chunk)
-                    except native.IIVAssertionError:
-                        # one of the reference's asserts fires somewhere in this chunk -- maybe past
-                        # what the caller will pull: step exactly from here on, so that it is raised
-                        # by the next() that would raise it in the reference
-                        self._enc.rollback(slot)
-                        self._host_current = False
-                        self._brief_fresh = False
-                        speculative, chunk = False, 1
-                        continue
-                elif budget and chunk >= 32 and not self.STRICT_SYNC:
-                    # a promised budget: one launch, nothing to roll back -- handed out while it runs, too
-                    self._brief_fresh = False
-                    self._brief_event = None
-                    self._launch_buffers(chunk)
-                    live = self._launch_live(token, token.is_aux, restart, chunk, 0, self._ops_dev, self._pinned_brief())
-                    if live is not None:
-                        self._brief_fresh = True
-                        self._brief_applied = False
-                        self._brief_event = live["event"]
+                # a speculative launch runs on snapshot `slot` and is handed out live through queue `slot`; a promised budget:
+                # one launch, nothing to roll back -- handed out while it runs, too; an exact step is a plain launch
+                slot = adopt.slot if adopt is not None else 0
+                qslot = slot if speculative or (budget and chunk >= 32 and not self.STRICT_SYNC) else None
+                try:
+                    if adopt is not None:
+                        launch = self._adopt(adopt)
                     else:
-                        ops = self._launch(token, restart, chunk)
-                else:
-                    ops = self._launch(token, restart, chunk)
+                        if speculative:
+                            self._enc.snapshot(slot)
+                        launch = self._launch(token, token.is_aux, restart, chunk, self._bufs, qslot)
+                except native.IIVAssertionError:
+                    if not speculative:
+                        raise
+                    # one of the reference's asserts fires somewhere in this chunk -- maybe past
+                    # what the caller will pull: step exactly from here on, so that it is raised
+                    # by the next() that would raise it in the reference
+                    self._enc.rollback(slot)
+                    self._host_current = False
+                    self._bufs.stale()
+                    speculative, chunk = False, 1
+                    continue
+                live, produced = launch.live, launch.n    # live: the opcodes arrive one by one in a host queue (_live_take)
                 self._live = token
                 token.started = True
                 if self.STRICT_SYNC:
                     self._download()
                 rec = None
-                produced = live["n"] if live is not None else len(ops)
                 if speculative:
                     rec = _Chunk(token, restart, produced, prev_live, slot)
                     self._pending = rec
                     if paced and self.LOOKAHEAD and self.mode == VideoMode.DHGR:
                         self._look_ahead(token, produced, 1 - slot)
-                if live is not None and rec is None:
-                    # (a promised budget, live: nothing is pending -- the state may run ahead of the caller, that is the promise)
-                    tally = _Chunk(token, restart, produced, prev_live, slot)
+                if live is not None:
+                    # hand out what has arrived, as it arrives.  A promised budget (rec is None) leaves nothing pending: the
+                    # state may run ahead of the caller, that is the promise
+                    tally = rec if rec is not None else _Chunk(token, restart, produced, prev_live, slot)
                     ended = False
-                    while tally.base < produced and not ended:
+                    while tally.base < produced and not ended and (rec is None or self._pending is rec):
                         items, ended = self._live_take(live, tally.base)
                         yield from tally.hand_out(items)
-                    if tally.base < produced:
-                        self._enc.check()     # the launch ended short: raises what the device reports, at the next() it belongs to
-                        raise RuntimeError("live hand-over: the launch ended after %d of %d opcodes" % (tally.base, produced))
-                    self._ops_done += produced
-                    chunk = 1
-                    continue
-                if live is not None:
-                    # hand out what has arrived, as it arrives
-                    ended = False
-                    while rec.base < produced and not ended and self._pending is rec:
-                        items, ended = self._live_take(live, rec.base)
-                        yield from rec.hand_out(items)
-                    if self._pending is not rec:
+                    if rec is not None and self._pending is not rec:
                         continue   # settled underneath us: the rest of this launch was rolled back
-                    if rec.base < produced:
-                        # the launch ended short of its opcodes: one of the reference's asserts fires at the next one (or an
-                        # internal limit was hit).  Settle to exactly the opcodes consumed -- roll back, replay them -- and
-                        # step exactly from here: the next() that raises in the reference raises here
+                    if tally.base < produced:
+                        if rec is None:
+                            self._enc.check()     # the launch ended short: raises what the device reports, at the next() it belongs to
+                            raise RuntimeError("live hand-over: the launch ended after %d of %d opcodes" % (tally.base, produced))
+                        # speculative: one of the reference's asserts fires at the next opcode (or an internal limit was hit).
+                        # Settle to exactly the opcodes consumed -- roll back, replay them -- and step exactly from here: the
+                        # next() that raises in the reference raises here
                         self._settle(download=False)
                         speculative, chunk = False, 1
                         continue
-                    self._pending = None
-                    self._ops_done += produced
-                    continue
-                # plain ints, converted once per chunk
-                items = list(zip(ops[:, 0].tolist(), ops[:, 1].tolist(), ops[:, 2:6].tolist()))
-                if rec is None:
-                    yield from items
-                    self._ops_done += len(items)
-                else:
-                    yield from rec.hand_out(items)
-                    if self._pending is rec:   # (else: settled underneath us, the rest of this chunk was rolled back)
+                    if rec is not None:
                         self._pending = None
+                    self._ops_done += produced
+                else:
+                    # plain ints, converted once per chunk
+                    ops = launch.ops
+                    items = list(zip(ops[:, 0].tolist(), ops[:, 1].tolist(), ops[:, 2:6].tolist()))
+                    if rec is None:
+                        yield from items
                         self._ops_done += len(items)
+                    else:
+                        yield from rec.hand_out(items)
+                        if self._pending is rec:   # (else: settled underneath us, the rest of this chunk was rolled back)
+                            self._pending = None
+                            self._ops_done += len(items)
                 if not speculative:
                     chunk = 1
         except GeneratorExit:

@@ -1,5 +1,5 @@
-"""CPU: the host-side logic of the drop-in Video's live hand-over and of the in-place access to `random`'s state
-(ii-vision_amd/transcoder/video.py) -- no GPU: the queue is a numpy array filled by hand, the way the team kernel fills
+"""CPU: the host-side logic of the drop-in Video's live hand-over (ii-vision_amd/transcoder/video.py) and of the in-place
+access to `random`'s state (global_rng.py) -- no GPU: the queue is a numpy array filled by hand, the way the team kernel fills
 the real one (include/iivision.h: iiv_encode_live)."""
 import ctypes
 import random
@@ -22,7 +22,7 @@ def _slot(tag, page, content, offs):
 
 
 def _lv(q, tag, n):
-    return dict(q=q, q16=q.view(np.uint16).reshape(-1, 4)[:, 3], q8=q.view(np.uint8).reshape(-1, 8), tag=tag, n=n, event=None)
+    return _video_module()._LiveView(q, tag, n)
 
 
 def _taker():
@@ -86,29 +86,29 @@ def test_chunk_counts_what_its_iterator_has_handed_out():
 
 
 def test_random_state_in_place_equals_getstate_setstate():
-    video = _video_module()
+    from global_rng import py_random
     saved = random.getstate()
     try:
         random.seed(41)
         [random.random() for _ in range(700)]          # (past a block boundary)
         want = random.getstate()
-        raw = video._py_rng_raw()
+        raw = py_random.raw()
         assert np.array_equal(np.frombuffer(raw, dtype=np.uint32), np.array(want[1], dtype=np.uint32))
         draws = [random.getrandbits(8) for _ in range(1500)]
         words = (ctypes.c_uint32 * 625)(*want[1])
         random.seed(1)
         random.gauss(0, 1)                              # (leaves a cached gauss_next behind: setstate(..., None) clears it)
-        video._py_rng_write(words)
+        py_random.write(words)
         assert random.getstate() == (want[0], want[1], None)
         assert [random.getrandbits(8) for _ in range(1500)] == draws
         # the fallback path gives the same
-        addr, video._py_global[1] = video._py_global[1], 0
+        py_random.distrust()
         try:
-            assert video._py_rng_addr() == 0
+            assert py_random.address() == 0
             random.seed(2)
-            video._py_rng_write(words)
-            assert random.getstate()[1] == want[1] and video._py_rng_raw() == raw
+            py_random.write(words)
+            assert random.getstate()[1] == want[1] and py_random.raw() == raw
         finally:
-            video._py_global[1] = addr
+            py_random.distrust(False)
     finally:
         random.setstate(saved)

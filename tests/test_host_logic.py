@@ -240,17 +240,42 @@ def test_np_random_state_words_read_and_written_in_place():
     """video.Video reads / writes np.random's global MT19937 words through numpy's ctypes interface instead of
     get_state() / set_state(): the same 625 words, and the cached-gaussian part of the legacy state is left alone."""
     import ctypes
-    import video
+    from global_rng import np_random
     np.random.seed(77)
     np.random.standard_normal()          # leaves has_gauss = 1
     st = np.random.get_state()
-    raw = video._np_rng_raw()
+    raw = np_random.raw()
     assert raw[:2496] == st[1].tobytes() and int.from_bytes(raw[2496:], "little") == st[2]
     a = np.random.randint(0, 256, size=700).tolist()      # crosses a block boundary
-    assert video._np_rng_raw() != raw
-    ctypes.memmove(video._np_rng_addr(), raw, 2500)
+    assert np_random.raw() != raw
+    ctypes.memmove(np_random.address(), raw, 2500)
     st2 = np.random.get_state()
     assert (st2[1] == st[1]).all() and st2[2:] == st[2:] and st2[3] == 1
     assert np.random.randint(0, 256, size=700).tolist() == a
     np.random.seed(78)                   # reseeding keeps the generator object: the address stays valid
-    assert video._np_rng_raw()[:2496] == np.random.get_state()[1].tobytes()
+    assert np_random.raw()[:2496] == np.random.get_state()[1].tobytes()
+
+
+def test_np_random_state_words_written_through_set_state_when_no_address():
+    """Without a verified address np.random's words go through get_state() / set_state(): the same 625 words, the
+    cached-gaussian part of the legacy state left alone, and raw() reports what was written."""
+    import ctypes
+    from global_rng import np_random
+    saved = np.random.get_state()
+    np_random.distrust()
+    try:
+        assert np_random.address() == 0
+        np.random.seed(5)
+        [np.random.random_sample() for _ in range(700)]        # (past a block boundary)
+        want = np.random.get_state()
+        words = (ctypes.c_uint32 * 625)(*want[1].tolist(), want[2])
+        np.random.seed(6)
+        np.random.standard_normal()          # leaves has_gauss = 1
+        gauss = np.random.get_state()[3:]
+        np_random.write(words)
+        st = np.random.get_state()
+        assert (st[1] == want[1]).all() and st[2] == want[2] and st[3] == 1 and st[3:] == gauss
+        assert np_random.raw() == bytes(words)
+    finally:
+        np_random.distrust(False)
+        np.random.set_state(saved)

@@ -36,7 +36,7 @@ def run(instrument):
     np.random.seed(1)
     v = video.Video(FG(), ticks_per_second=14700., palette=pal, mode=video_mode.VideoMode.DHGR)
     if instrument:
-        for name in ("_sync_brief", "_settle", "_look_ahead", "_launch_live", "_adopt", "_live_take", "_paced_chunk", "_global_rng_moved", "_set_global_rng"):
+        for name in ("_sync_brief", "_settle", "_look_ahead", "_launch", "_launch_live", "_adopt", "_live_take", "_paced_chunk", "_global_rng_moved", "_set_global_rng"):
             timed(v, name)
         for name in ("encode_live", "snapshot", "get_video_brief_async", "rollback", "check"):
             timed(v._enc, name, "enc." + name)
