@@ -123,6 +123,7 @@ _SIGNATURES = {
     "iiv_emit_stream": (_i32, [_i32, _i32, _lg, _vp, _vp, _vp, _u16, _u16, _lg, _vp, _sz, C.POINTER(_sz), _vp]),
     # ---- f3: frame ingest (the header declares f2's slice emission behind it)
     "iiv_frames_to_memory_maps": (_i32, [_i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "iiv_frames_to_memory_maps_diffused": (_i32, [_i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "iiv_emit_chunk": (_i32, [_i32, _i32, _lg, _lg, _vp, _sz, _vp, _sz, _i32, _vp, _u16, _vp, _sz,
                               C.POINTER(_sz), C.POINTER(_sz), _vp, _vp]),
     # ---- f4: the audio track
@@ -757,6 +758,27 @@ def frames_to_memory_maps(mode, palette_rgb, rgb, dither=0, out=None):
     pal = np.ascontiguousarray(palette_rgb, dtype=np.uint8).reshape(48)
     main, aux = _memory_maps_out(mode, n, out)
     check(lib().iiv_frames_to_memory_maps(mode, hptr(pal), n, dptr(rgb), int(dither), dptr(main), dptr(aux), stream_ptr()))
+    return main, aux
+
+
+def frames_to_memory_maps_diffused(mode, palette_rgb, rgb, weights, divisor, out=None):
+    """frames_to_memory_maps by error diffusion with a chosen kernel (include/iivision.h:
+    iiv_frames_to_memory_maps_diffused; csrc/iiv_diffuse.hip).  weights: 3 x 5 (or 15) integers 0..255, weights[dy][dx + 2] the
+    share, in `divisor`-ths, of pixel (y + dy, k + dx); divisor 1..64.  The library refuses (IIVError, nothing launched) a
+    divisor outside 1..64, a weight on the pixel itself or left of it on its row, and weights that sum to more than the
+    divisor.  rgb, out and the asynchrony: exactly as frames_to_memory_maps.  The named kernels: frame_grabber.DIFFUSION_KERNELS."""
+    _cuda_u8(rgb, "rgb")
+    if tuple(rgb.shape[1:]) != (192, 280, 3):
+        raise ValueError("rgb has shape %s, not (n, 192, 280, 3)" % (tuple(rgb.shape),))
+    w = np.asarray(weights)
+    if w.size != 15 or not np.issubdtype(w.dtype, np.integer) or w.min() < 0 or w.max() > 255:
+        raise ValueError("weights must be 3 x 5 integers in 0..255")
+    w = np.ascontiguousarray(w, dtype=np.uint8).reshape(15)
+    n = int(rgb.shape[0])
+    pal = np.ascontiguousarray(palette_rgb, dtype=np.uint8).reshape(48)
+    main, aux = _memory_maps_out(mode, n, out)
+    check(lib().iiv_frames_to_memory_maps_diffused(mode, hptr(pal), n, dptr(rgb), hptr(w), int(divisor), dptr(main), dptr(aux),
+                                                   stream_ptr()))
     return main, aux
 
 

@@ -26,6 +26,24 @@ from palette import Palette
 from video_mode import VideoMode
 
 
+# Error-diffusion kernels by name: (3 x 5 weights, divisor) -- weights[dy][dx + 2] is the share, in divisor-ths, of pixel
+# (y + dy, k + dx) (include/iivision.h: iiv_frames_to_memory_maps_diffused).  ArrayFrameGrabber(dither=<name>) runs
+# csrc/iiv_diffuse.hip with them; dither="diffusion" stays iiv_frames_to_memory_maps' own Floyd-Steinberg kernel.
+DIFFUSION_KERNELS = {
+    "floyd-steinberg": (((0, 0, 0, 7, 0), (0, 3, 5, 1, 0), (0, 0, 0, 0, 0)), 16),
+    "jarvis": (((0, 0, 0, 7, 5), (3, 5, 7, 5, 3), (1, 3, 5, 3, 1)), 48),
+    "stucki": (((0, 0, 0, 8, 4), (2, 4, 8, 4, 2), (1, 2, 4, 2, 1)), 42),
+    "atkinson": (((0, 0, 0, 1, 1), (0, 1, 1, 1, 0), (0, 0, 1, 0, 0)), 8),       # 6/8 of the error: flat areas stay flat
+    "burkes": (((0, 0, 0, 8, 4), (2, 4, 8, 4, 2), (0, 0, 0, 0, 0)), 32),
+    "sierra": (((0, 0, 0, 5, 3), (2, 4, 5, 4, 2), (0, 2, 3, 2, 0)), 32),
+    "sierra-2": (((0, 0, 0, 4, 3), (1, 2, 3, 2, 1), (0, 0, 0, 0, 0)), 16),
+    "sierra-lite": (((0, 0, 0, 2, 0), (0, 1, 1, 0, 0), (0, 0, 0, 0, 0)), 4),
+    # bmp2dhr's D9, the dither the reference asks it for (frame_grabber.py:80-82,106-108): its weights AS REMEMBERED from
+    # bmp2dhr's source, which is not here to check -- an assumption; no equality with bmp2dhr is claimed
+    "buckels": (((0, 0, 0, 2, 1), (0, 1, 2, 1, 0), (0, 0, 1, 0, 0)), 8),
+}
+
+
 class FrameGrabber:
     """frame_grabber.py:18-24."""
 
@@ -43,9 +61,12 @@ class ArrayFrameGrabber(FrameGrabber):
     frames may be any size (n, h, w, 3) (1 <= h, w <= 8192): each is resized to 280x192 on the device
     first, byte for byte as the reference's Image.resize((280, 192), LANCZOS) (frame_grabber.py:75,100).
     palette=Palette.MONO (a monochrome monitor): a frame is one pixel per DOT -- (192, 560) for DHGR,
-    (192, 280) for HGR --, resize=True resizes to that size, and the conversion is iiv_frames_to_memory_maps_mono."""
+    (192, 280) for HGR --, resize=True resizes to that size, and the conversion is iiv_frames_to_memory_maps_mono.
+    dither: 0..255 = amplitude of the ordered dither; "diffusion" = Floyd-Steinberg (iiv_frames_to_memory_maps); a name of
+    DIFFUSION_KERNELS or (3 x 5 weights, divisor) = error diffusion with that kernel (iiv_frames_to_memory_maps_diffused;
+    colour palettes only)."""
 
-    def __init__(self, frames_rgb, mode: VideoMode, palette: Palette = Palette.NTSC, dither: int = 32,
+    def __init__(self, frames_rgb, mode: VideoMode, palette: Palette = Palette.NTSC, dither=32,
                  input_frame_rate: float = 30, batch: int = 256, resize: bool = False):
         super().__init__(mode)
         rgb = np.asarray(frames_rgb)
@@ -62,7 +83,19 @@ class ArrayFrameGrabber(FrameGrabber):
         self.palette = palette
         # 0..255: amplitude of the 4x4 ordered dither; "diffusion" (= native.DITHER_DIFFUSION): Floyd-Steinberg error
         # diffusion, the kind of dither the reference asks bmp2dhr for (D9, frame_grabber.py:80-82,106-108)
-        self.dither = native.DITHER_DIFFUSION if dither == "diffusion" else int(dither)
+        # a name of DIFFUSION_KERNELS, or (3 x 5 weights, divisor): error diffusion with that kernel (csrc/iiv_diffuse.hip)
+        self.diffusion_kernel = None
+        if isinstance(dither, str) and dither != "diffusion":
+            if dither not in DIFFUSION_KERNELS:
+                raise ValueError("dither: unknown diffusion kernel %r (one of %s, or \"diffusion\")" % (dither, ", ".join(sorted(DIFFUSION_KERNELS))))
+            self.diffusion_kernel = DIFFUSION_KERNELS[dither]
+        elif isinstance(dither, (tuple, list)):
+            if len(dither) != 2:
+                raise ValueError("dither: a diffusion kernel is (3 x 5 weights, divisor)")
+            self.diffusion_kernel = (dither[0], int(dither[1]))
+        if self.diffusion_kernel is not None and palette == Palette.MONO:
+            raise ValueError("Palette.MONO converts with dither=\"diffusion\" or an ordered amplitude: the diffusion kernels are the colour conversion's")
+        self.dither = native.DITHER_DIFFUSION if dither == "diffusion" or self.diffusion_kernel is not None else int(dither)
         self.input_frame_rate = input_frame_rate
         self.batch = int(batch)
 
@@ -78,6 +111,8 @@ class ArrayFrameGrabber(FrameGrabber):
         if self.palette == Palette.MONO:
             return native.frames_to_memory_maps_mono(mode, rgb, self.dither)
         pal = palette_mod.PALETTES[self.palette].rgb_array()
+        if self.diffusion_kernel is not None:
+            return native.frames_to_memory_maps_diffused(mode, pal, rgb, *self.diffusion_kernel)
         return native.frames_to_memory_maps(mode, pal, rgb, self.dither)
 
     def frames(self):

@@ -486,6 +486,31 @@ int iiv_emit_stream(int mode, int n_streams, long n_ops, const uint8_t *d_ops, c
 int iiv_frames_to_memory_maps(int mode, const uint8_t palette_rgb[48], int n_frames, const uint8_t *d_rgb,
                               int dither, uint8_t *d_main, uint8_t *d_aux, void *stream);
 
+/* The error diffusion with a CHOSEN kernel: everything as iiv_frames_to_memory_maps with IIV_DITHER_DIFFUSION -- the
+ * averaging of the two source pixels, the colour distance and its ties, DHGR's nearest of the 16, HGR's palette bit of screen
+ * byte b fixed just before the first pixel whose first dot lies in b is quantised (for both palette bits the nearest-colour
+ * errors of the pixels whose first dot lies in b are summed, each weighted by the number of its dots in b, their values taken
+ * with the error accumulated up to then; the smaller sum wins, ties to 0; a pixel takes the nearest of the four colours of
+ * the palette bit of the byte holding its first dot), packing, holes, alignments, asynchrony, nothing allocated -- except
+ * where a pixel's error goes:
+ *   weights[5 * dy + dx + 2], dy = 0..2, dx = -2..+2, is the share, in `divisor`-ths, of pixel (y + dy, k + dx).
+ *   Rows top to bottom, pixels left to right, per channel:
+ *   value = clamp(mean of the two source pixels + floor(acc / divisor), 0, 255), floor towards minus infinity;
+ *   e = value - chosen colour; acc[y + dy][k + dx] += weights[5 * dy + dx + 2] * e; targets outside the 140 x 192 picture
+ *   are dropped.
+ * IIV_ERR_INVALID before anything is launched, nothing written: a bad mode or alignment; divisor outside 1..64; any of
+ * weights[0..2] non-zero (the pixel itself and what lies left of it on its row); a sum of weights above divisor.  (So
+ * |acc| <= 255 * 64, and the kernel's floor(acc / divisor) is an exact multiply-and-shift.)  All-zero weights are legal: no
+ * diffusion.  {0,0,0,7,0, 0,3,5,1,0, 0,0,0,0,0} / 16 is Floyd-Steinberg and gives the bytes of IIV_DITHER_DIFFUSION, through
+ * another kernel (csrc/iiv_diffuse.hip): this entry point never runs iiv_frames_to_memory_maps' own.  The named kernels
+ * (Jarvis, Stucki, Atkinson, Burkes, Sierra ...) are a table of the Python layer, transcoder/frame_grabber.py:
+ * DIFFUSION_KERNELS.  Its "buckels" -- the D9 the reference asks bmp2dhr for (frame_grabber.py:80-82,106-108) -- is
+ * {0,0,0,2,1, 0,1,2,1,0, 0,0,1,0,0} / 8 AS REMEMBERED from bmp2dhr's source, which is not here to check: an assumption, and
+ * no equality with bmp2dhr's output is claimed for it or for anything else here. */
+int iiv_frames_to_memory_maps_diffused(int mode, const uint8_t palette_rgb[48], int n_frames, const uint8_t *d_rgb,
+                                       const uint8_t weights[15], int divisor,
+                                       uint8_t *d_main, uint8_t *d_aux, void *stream);
+
 /* The same bytes for a slice of the opcode stream, asynchronously (no host round trip, no
  * synchronisation): opcodes [first_op, first_op + n_ops) of every stream, so that a movie can
  * be emitted while it is being encoded (iiv_encode -> iiv_emit_chunk -> copy to the host).

@@ -48,7 +48,9 @@ def main():
     ap.add_argument("--mode", choices=["DHGR", "HGR"], default="DHGR")
     ap.add_argument("--palette", choices=["NTSC", "IIGS", "MONO"], default="NTSC",
                     help="MONO: a monochrome monitor -- one source pixel per dot (560x192 DHGR, 280x192 HGR), dot-level distances (DESIGN.md 12)")
-    ap.add_argument("--dither", default="diffusion", help='"diffusion" (Floyd-Steinberg) or the amplitude 0..255 of the ordered dither')
+    ap.add_argument("--dither", default="diffusion",
+                    help='"diffusion" (Floyd-Steinberg), the amplitude 0..255 of the ordered dither, or an error-diffusion kernel by name: '
+                         'floyd-steinberg, jarvis, stucki, atkinson, burkes, sierra, sierra-2, sierra-lite, buckels (frame_grabber.DIFFUSION_KERNELS)')
     ap.add_argument("--dbg", help="player/iivision.dbg (opcode entry points)")
     ap.add_argument("--tick", type=int, default=34, help="without audio: speaker duty cycle of every opcode (4..66, even)")
     ap.add_argument("--audio", help="16-bit PCM .wav: the clip's audio track")
@@ -83,7 +85,7 @@ def main():
     rgb = np.load(a.frames) if a.frames else test_card(a.synthetic, native.MONO_SIZE[mode][1] if pal_id == palette.Palette.MONO else 280)
     t0 = time.perf_counter()
     grab = frame_grabber.ArrayFrameGrabber(rgb, video_mode.VideoMode[a.mode], pal_id,
-                                           dither=a.dither if a.dither == "diffusion" else int(a.dither), resize=True)
+                                           dither=int(a.dither) if a.dither.isdigit() else a.dither, resize=True)
     main_maps, aux_maps = grab.memory_maps()                       # (n, 32, 256) on the device
     dm = palette.diff_matrix(pal_id)                               # CIE2000 of the palette's colours; MONO: the dot distance
     table = native.build_table(mode, dm, True)
