@@ -20,6 +20,8 @@ Recipe:
     while everything downstream of the tables is pinned.
 
 Usage: python tests/golden/make_golden.py [--scratch /tmp/iiv_ref]
+       python tests/golden/make_golden.py --asserts-only     (g10_asserts.npz alone: the reference on the clips of
+       tests/assert_inputs.py -- targets with bytes in the screen holes and with bit 7 set -- up to its AssertionError)
 """
 
 import argparse
@@ -206,6 +208,7 @@ def main():
     ap.add_argument("--a2m-only", action="store_true")
     ap.add_argument("--movie-only", action="store_true")
     ap.add_argument("--fourth-only", action="store_true")
+    ap.add_argument("--asserts-only", action="store_true")
     args = ap.parse_args()
 
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -355,7 +358,7 @@ def main():
     make_fourth_offset_golden(args.scratch)
 
 
-if __name__ == "__main__" and not {"--a2m-only", "--movie-only", "--fourth-only"} & set(sys.argv):
+if __name__ == "__main__" and not {"--a2m-only", "--movie-only", "--fourth-only", "--asserts-only"} & set(sys.argv):
     main()
 
 
@@ -564,3 +567,82 @@ if __name__ == "__main__" and "--fourth-only" in sys.argv:
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     setup_reference("/tmp/iiv_ref")
     make_fourth_offset_golden("/tmp/iiv_ref")
+
+
+def make_asserts_golden(scratch):
+    """g10: the reference on the clips of tests/assert_inputs.py -- the ones it accepts (bytes in the target's screen holes,
+    bit 7 on DHGR bytes it never pops or does not pop within the budget) run through; on the others the opcodes yielded
+    before its AssertionError, their count and the line of video.py that raised.  Schedules are (frame, is_aux, restart,
+    n_ops): restart = 0 goes on with the generator of the segment before."""
+    import contextlib
+    import io
+    import traceback
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import assert_inputs as A
+    import oracle as O
+    import palette
+    import screen
+    import video
+    import video_mode
+    import frame_grabber
+
+    def run(mode_name, frames, sched, seeds):
+        mode = video_mode.VideoMode[mode_name]
+        pal = palette.Palette(5)
+        random.seed(seeds[0])
+        np.random.seed(seeds[1])
+        v = video.Video(frame_grabber.FrameGrabber(mode), ticks_per_second=14700., mode=mode, palette=pal)
+        ops, line, gen = [], 0, None
+        try:
+            for (fi, is_aux, restart, n_ops) in sched:
+                if restart:
+                    main = screen.MemoryMap(screen_page=1, page_offset=frames[fi, 0].copy())
+                    if mode_name == "DHGR":
+                        aux = screen.MemoryMap(screen_page=1, page_offset=frames[fi, 1].copy())
+                        tgt = screen.DHGRBitmap(main_memory=main, aux_memory=aux, palette=pal)
+                    else:
+                        tgt = screen.HGRBitmap(main_memory=main, palette=pal)
+                    gen = v.encode_frame(tgt, is_aux=bool(is_aux))
+                with contextlib.redirect_stdout(io.StringIO()):
+                    for _ in range(n_ops):
+                        page, content, offsets = next(gen)
+                        ops.append([page, int(content)] + [int(o) for o in offsets])
+        except AssertionError as e:
+            tb = traceback.extract_tb(e.__traceback__)[-1]
+            assert os.path.basename(tb.filename) == "video.py"
+            line = tb.lineno
+        st = dict(ops=np.array(ops, dtype=np.uint8).reshape(-1, 6), n_ops=np.int32(len(ops)), assert_line=np.int32(line),
+                  mem_main=v.memory_map.page_offset.copy(), up_main=v.update_priority.copy(), packed=v.pixelmap.packed.copy())
+        if mode_name == "DHGR":
+            st["mem_aux"] = v.aux_memory_map.page_offset.copy()
+            st["up_aux"] = v.aux_update_priority.copy()
+        st["py_next"] = np.array([random.getrandbits(8) for _ in range(4)], dtype=np.uint8)
+        st["np_next"] = np.random.randint(0, 256, size=4).astype(np.uint8)
+        return st
+
+    dmo = O.cie2000_matrix(O.PALETTE_RGB[5])[1]
+    quiet, quiet_sched = A.quiet_palette_bit(O, O.build_table(O.DHGR, dmo, symmetric=True))
+    cases = [("dirty_holes_DHGR", "DHGR", A.dirty_holes(A.DHGR), A.dirty_holes_schedule(A.DHGR), A.SEEDS["dirty_holes"]),
+             ("dirty_holes_HGR", "HGR", A.dirty_holes(A.HGR), A.dirty_holes_schedule(A.HGR), A.SEEDS["dirty_holes"]),
+             ("quiet", "DHGR", quiet, quiet_sched, A.SEEDS["quiet"]),
+             ("late_short", "DHGR", A.late_palette_bit(), A.LATE_SHORT, A.SEEDS["late"]),
+             ("late_more", "DHGR", A.late_palette_bit(), A.LATE_SHORT + A.LATE_MORE, A.SEEDS["late"]),
+             ("early", "DHGR", A.early_palette_bit(), A.EARLY_SCHEDULE, A.SEEDS["early"])]
+    g10 = {}
+    for (tag, mode_name, frames, sched, seeds) in cases:
+        st = run(mode_name, frames, sched, seeds)
+        g10[tag + "/sha_frames"] = np.frombuffer(bytes.fromhex(sha(frames)), dtype=np.uint8)   # (the clip is rebuilt by the test)
+        g10[tag + "/schedule"] = np.array(sched, dtype=np.int32)
+        for k, val in st.items():
+            g10[tag + "/" + k] = val
+        print("%s: %d ops, assert at video.py:%d, sha %s" % (tag, len(st["ops"]), st["assert_line"], sha(st["ops"])[:16]))
+    np.savez_compressed(os.path.join(HERE, "g10_asserts.npz"), **g10)
+    print("g10 written")
+
+
+if __name__ == "__main__" and "--asserts-only" in sys.argv:
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    setup_reference("/tmp/iiv_ref")
+    import oracle as _O
+    write_reference_tables("/tmp/iiv_ref", _O)
+    make_asserts_golden("/tmp/iiv_ref")
