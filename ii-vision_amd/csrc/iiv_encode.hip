@@ -1217,6 +1217,18 @@ int iiv_encoder_get_video_brief_async(iiv_encoder *enc, int stream_index, iiv_vi
     return iiv::encoder_get_video_brief_async(enc, stream_index, host_out, (hipStream_t)stream);
 }
 
+int iiv_encoder_render(iiv_encoder *enc, int first_stream, int n_streams, const uint8_t palette_rgb[48], uint8_t *d_rgb, void *stream)
+{
+    if (!enc || !palette_rgb || !d_rgb || first_stream < 0 || n_streams < 0 || n_streams > enc->n_streams - first_stream)
+        return iiv::set_error(IIV_ERR_INVALID, "iiv_encoder_render: bad argument or stream range");
+    if ((uintptr_t)d_rgb & 15) return iiv::set_error(IIV_ERR_INVALID, "iiv_encoder_render: d_rgb must be 16-byte aligned");
+    if (n_streams == 0) return IIV_OK;
+    // (the maps of a stream are the first 16 KiB of its StreamState, main then aux; the states lie sizeof(StreamState) apart)
+    const uint8_t *base = reinterpret_cast<const uint8_t *>(enc->d_states + first_stream);
+    return iiv::render_rgb(enc->mode, palette_rgb, n_streams, base + offsetof(iiv::StreamState, mem[0]),
+                           base + offsetof(iiv::StreamState, mem[1]), sizeof(iiv::StreamState), d_rgb, (hipStream_t)stream);
+}
+
 int iiv_encoder_set_video_state(iiv_encoder *enc, int stream_index, const iiv_video_state *host_in)
 {
     return iiv::encoder_set_video_state(enc, stream_index, host_in);

@@ -142,4 +142,8 @@ int compute_delta_pages(int mode, const uint16_t *d_table, int n, const uint64_t
                         const int32_t *d_contents, const int32_t *d_dw_rows, int is_aux, int32_t *d_out,
                         hipStream_t st);
 
+// iiv_render.hip: frame f's memory maps at d_main / d_aux + f * in_stride bytes
+int render_rgb(int mode, const uint8_t palette_rgb[48], int n, const uint8_t *d_main, const uint8_t *d_aux, size_t in_stride,
+               uint8_t *d_rgb, hipStream_t st);
+
 }  // namespace iiv

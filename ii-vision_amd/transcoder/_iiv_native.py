@@ -136,6 +136,9 @@ _SIGNATURES = {
     "iiv_resize_frames": (_i32, [_i32, _i32, _i32, _vp, _sz, _sz, _i32, _i32, _vp, _vp]),
     # ---- f6: mono playback mode
     "iiv_frames_to_memory_maps_mono": (_i32, [_i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    # ---- f7: preview
+    "iiv_render_rgb": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "iiv_encoder_render": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
 }
 SYMBOLS = list(_SIGNATURES)
 
@@ -801,6 +804,51 @@ def frames_to_memory_maps_mono(mode, rgb, dither=0, out=None):
     main, aux = _memory_maps_out(mode, n, out)
     check(lib().iiv_frames_to_memory_maps_mono(mode, n, dptr(rgb), int(dither), dptr(main), dptr(aux), stream_ptr()))
     return main, aux
+
+
+# ---- f7: preview ----------------------------------------------------------------------
+
+RENDER_SIZE = (192, 560)   # (H, W) of a rendered screen, both modes
+
+
+def _render_out(n, out):
+    """The (n, 192, 560, 3) tensor a render call writes: new, or the caller's contiguous CUDA uint8 `out` of that many bytes."""
+    torch = _torch()
+    if out is None:
+        return torch.empty((n,) + RENDER_SIZE + (3,), dtype=torch.uint8, device="cuda")
+    _cuda_u8(out, "out")
+    if out.numel() != n * RENDER_SIZE[0] * RENDER_SIZE[1] * 3:
+        raise ValueError("out must hold n * 192 * 560 * 3 bytes")
+    return out
+
+
+def render_rgb(mode, palette_rgb, main, aux=None, out=None):
+    """main / aux: contiguous CUDA uint8 memory maps of n * 8192 bytes each ((n, 32, 256), or any shape that ends in (32, 256);
+    aux is ignored for HGR) -> CUDA uint8 (n, 192, 560, 3): the screen through the reference's colour model (include/iivision.h:
+    iiv_render_rgb).  Asynchronous on torch's current stream, as frames_to_memory_maps is."""
+    if mode not in (HGR, DHGR):
+        raise ValueError("mode must be HGR or DHGR")
+    for t, name in ((main, "main"), (aux, "aux")) if mode == DHGR else ((main, "main"),):
+        _cuda_u8(t, name)
+        if t.numel() % 8192 or t.numel() != main.numel():
+            raise ValueError("%s must hold n memory maps of 8192 bytes%s" % (name, "" if t is main else ", as many as main"))
+    n = main.numel() // 8192
+    pal = np.ascontiguousarray(palette_rgb, dtype=np.uint8).reshape(48)
+    out = _render_out(n, out)
+    check(lib().iiv_render_rgb(mode, hptr(pal), n, dptr(main), dptr(aux if mode == DHGR else None), dptr(out), stream_ptr()))
+    return out.view((n,) + RENDER_SIZE + (3,))
+
+
+def encoder_render(encoder, palette_rgb, first_stream=0, n_streams=None, out=None):
+    """The screens the streams first_stream .. of an Encoder hold right now (behind the launches already on torch's current
+    stream) -> CUDA uint8 (n_streams, 192, 560, 3), rendered from the encoder's own device state (iiv_encoder_render)."""
+    n = encoder.n_streams - int(first_stream) if n_streams is None else int(n_streams)
+    if first_stream < 0 or n < 0 or first_stream + n > encoder.n_streams:
+        raise ValueError("streams %d .. %d of an encoder of %d" % (first_stream, first_stream + n - 1, encoder.n_streams))
+    pal = np.ascontiguousarray(palette_rgb, dtype=np.uint8).reshape(48)
+    out = _render_out(n, out)
+    check(lib().iiv_encoder_render(encoder._h, int(first_stream), n, hptr(pal), dptr(out), stream_ptr()))
+    return out.view((n,) + RENDER_SIZE + (3,))
 
 
 # ---- f4: the audio track ------------------------------------------------------------

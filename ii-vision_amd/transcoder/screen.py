@@ -338,6 +338,16 @@ class Bitmap:
         return out[0]
 
 
+def render_rgb(main, aux, mode, palette):
+    """What memory maps put on the screen: main / aux torch uint8 device tensors of n memory maps ((n, 32, 256); aux None or
+    ignored for HGR), mode a VideoMode or native.HGR / native.DHGR, palette a pal.Palette or a (16, 3) uint8 array indexed by
+    colour value -> (n, 192, 560, 3) uint8 device tensor: every dot through the sliding-window colour model that prices the
+    encoder's stores (include/iivision.h: iiv_render_rgb; csrc/iiv_render.hip).  Not in the reference, which never draws."""
+    mode_id = {"HGR": native.HGR, "DHGR": native.DHGR}[mode.name] if hasattr(mode, "name") else int(mode)
+    rgb = pal.palette_class(palette).rgb_array() if isinstance(palette, pal.Palette) else palette
+    return native.render_rgb(mode_id, rgb, main, aux)
+
+
 def _double(int7: int) -> int:
     """Each of bits 0..6 lights two dots; bit 6 a third (screen.py:712-739)."""
     out = 0

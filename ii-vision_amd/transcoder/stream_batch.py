@@ -279,5 +279,14 @@ class StreamBatch:
             ops = self.enc.encode(frames_main, frames_aux, plan, ops_out)
         return ops, segs
 
+    def screens_rgb(self, palette=None):
+        """What every stream's screen shows right now -- behind the launches already enqueued -- as a (n_streams, 192, 560, 3)
+        uint8 device tensor, rendered from the encoder's own screen memory (iiv_encoder_render).  palette: a palette.Palette
+        or a (16, 3) uint8 array indexed by colour value; None: NTSC."""
+        import palette as pal
+        palette = pal.Palette.NTSC if palette is None else palette
+        rgb = pal.palette_class(palette).rgb_array() if isinstance(palette, pal.Palette) else palette
+        return native.encoder_render(self.enc, rgb)
+
     def close(self):
         self.enc.close()

@@ -295,6 +295,20 @@ class Video:
 
     del _settled
 
+    def screen_rgb(self):
+        """What the screen shows after the opcodes consumed so far: a (192, 560, 3) uint8 device tensor in this Video's
+        palette, rendered from the encoder's own screen memory (iiv_encoder_render).  Not in the reference.  Like reading
+        memory_map it settles any speculation first, but nothing travels to the host."""
+        from palette import palette_class
+        if self._touched:
+            # the caller may have changed the arrays it was handed, and the device's copy is what is drawn: what the next
+            # generator would do before its launch (_index_changes)
+            self._settle()
+            self._upload()
+        else:
+            self._settle(download=False)
+        return native.encoder_render(self._enc, palette_class(self.palette).rgb_array())[0]
+
     def tick(self, ticks: int) -> bool:
         """Keep track of when it is time for a new image frame (video.py:64-70)."""
         self._tick_now = ticks

@@ -627,6 +627,41 @@ int iiv_resize_frames(int n, int h, int w, const uint8_t *d_src, size_t frame_st
 int iiv_frames_to_memory_maps_mono(int mode, int n_frames, const uint8_t *d_rgb, int dither, uint8_t *d_main,
                                    uint8_t *d_aux, void *stream);
 
+/* ==== f7: preview ==========================================================
+ * Screen memory -> 560 x 192 RGB: what a memory map (an ingest's output, an encoder's screen after any number of opcodes)
+ * puts on the screen, through the reference's own colour model (colours.py:100-134, screen.py:743-789, 983-990) -- the model
+ * that prices every store, which iiv_pixel_strings evaluates per masked value -- stated per screen row instead of per packed
+ * value.  One difference from the reference: a row starts with no dots to its left (the reference's packed form leaks the
+ * previous row's last byte into the next row's header, which it marks as a TODO, screen.py:190).  Integer rules only, so
+ * every implementation agrees byte for byte (tests/render_model.py restates them and is held to the reference-recorded
+ * strings; csrc/iiv_render.hip computes them).  Output is 560 dots by 192 rows in both modes.
+ *   Dots of row y.  The 40 bytes of row y are at y_to_base_addr(y) in the memory map (screen.py:16-22).
+ *   - DHGR: the byte sequence is aux[0], main[0], aux[1], main[1], ... for 80 bytes.  Dot 7 i + j is bit j of byte i, for
+ *     j = 0..6.  Bit 7 is ignored.
+ *   - HGR: byte i has palette bit p_i (bit 7) and data bits 0..6.  For dot x, let i = x / 14 and r = x % 14.
+ *       If p_i = 0, the dot is bit r / 2.
+ *       If p_i = 1 and r > 0, the dot is bit (r - 1) / 2.
+ *       If p_i = 1 and r = 0, the dot is bit 6 of byte i - 1, or 0 for i = 0.
+ *       The 561st dot, which a shifted last byte would light, is dropped.
+ *   Colour of dot x.  Let w = d[x-3] | d[x-2] << 1 | d[x-1] << 2 | d[x] << 3, with dots left of the row taken as 0.  The
+ *   colour value is rol4(w, (x + 1) & 3), where rol4 is colours.py:87-97.  Pixel (y, x) is
+ *   palette_rgb[3 * value .. 3 * value + 2].  palette_rgb is the same 16 x 3 host array the ingest entry points take.
+ *   (So an aligned repeating quad P shows colour value P from dot 3 on: what iiv_frames_to_memory_maps promises.)
+ * Screen holes are never read.  In HGR, d_aux is ignored and may be NULL.
+ * d_main / d_aux: [n][32][256] u8 memory maps, 8-byte aligned; d_rgb: [n][192][560][3] u8, 16-byte aligned.  Asynchronous on
+ * `stream`; the palette is read before the call returns; nothing is allocated.  n == 0 succeeds and writes nothing.
+ * IIV_ERR_INVALID before anything is launched: a bad mode, n < 0, a NULL d_main or d_rgb, a NULL d_aux in DHGR, a bad
+ * alignment. */
+int iiv_render_rgb(int mode, const uint8_t palette_rgb[48], int n, const uint8_t *d_main, const uint8_t *d_aux, uint8_t *d_rgb,
+                   void *stream);
+
+/* The same rendering of the encoder's OWN device copy of IIV_STATE_MEM_MAIN / IIV_STATE_MEM_AUX, for streams
+ * first_stream .. first_stream + n_streams - 1 -> d_rgb [n_streams][192][560][3]: no host round trip.  Refusals as
+ * iiv_render_rgb's, and a stream range that is not inside the encoder's.  It changes nothing in the encoder; ordering
+ * against a running encode is by `stream`, as for iiv_encoder_get_video_brief_async (an encoder is a one-stream object). */
+int iiv_encoder_render(iiv_encoder *enc, int first_stream, int n_streams, const uint8_t palette_rgb[48], uint8_t *d_rgb,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

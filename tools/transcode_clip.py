@@ -17,7 +17,10 @@ palette.MonoPalette.diff_matrix().
 device, byte for byte as the reference's Image.resize((280, 192), LANCZOS) (frame_grabber.py:75,100; csrc/iiv_resize.hip);
 a (n, 192, 280, 3) array is taken as it is.  --dbg: the player's cc65 debug file, from which the opcode entry points are read exactly as
 opcodes._parse_symbol_table does (opcodes.py:168-185); without it the stream is written with placeholder addresses
-and is NOT playable (the tool says so).  --fourth / --joint: the two optional quality modes."""
+and is NOT playable (the tool says so).  --fourth / --joint: the two optional quality modes.
+--preview FILE.npy: also write what the stream puts on the screen, a uint8 array (frames, 192, 560, 3): the screen as it stands
+after each source frame's opcodes, drawn on the device from the encoder's own screen memory in the clip's palette
+(csrc/iiv_render.hip).  The .a2m bytes are the same with and without it."""
 import argparse
 import os
 import sys
@@ -60,6 +63,7 @@ def main():
                     help="Audio(normalization=); default: computed from the audio's first 10 MiB (audio.py:60-78)")
     ap.add_argument("--fourth", action="store_true", help="IIV_OPT_FOURTH_OFFSET (not the reference's stream)")
     ap.add_argument("--joint", action="store_true", help="IIV_CONTENT_JOINT (not the reference's stream)")
+    ap.add_argument("--preview", metavar="FILE.npy", help="also write the screen after each source frame's opcodes: uint8 (frames, 192, 560, 3)")
     ap.add_argument("--seed", type=int, default=1, help="random.seed / np.random.seed of the encoder's two nonce streams")
     a = ap.parse_args()
     if a.tick < 4 or a.tick > 66 or a.tick % 2:
@@ -105,8 +109,23 @@ def main():
         max_ticks = au.tick_count()
     else:
         max_ticks = None
-    ops, segs = batch.encode_frames(main_maps[None], aux_maps[None] if aux_maps is not None else None, n, max_ticks=max_ticks)
-    batch.enc.check()
+    frames_main, frames_aux = main_maps[None], aux_maps[None] if aux_maps is not None else None
+    if a.preview:
+        # the same schedule one source frame per call (MovieClock continues a movie across calls), the screen drawn behind each
+        parts, segs, shots, left = [], [], [], max_ticks
+        for _ in range(n):
+            if left is None or left > 0:
+                o, s = batch.encode_frames(frames_main, frames_aux, 1, max_ticks=left)
+                parts.append(o)
+                segs += s
+                left = None if left is None else left - int(o.shape[1])
+            shots.append(batch.screens_rgb(pal_id))     # (the audio has run out: the screen stays as it is)
+        ops = torch.cat(parts, dim=1)
+        batch.enc.check()
+        np.save(a.preview, torch.cat(shots).cpu().numpy())
+    else:
+        ops, segs = batch.encode_frames(frames_main, frames_aux, n, max_ticks=max_ticks)
+        batch.enc.check()
     if a.dbg:
         addr = a2m.OpcodeAddresses.from_debug_file(a.dbg)
     else:
