@@ -1229,6 +1229,22 @@ int iiv_encoder_render(iiv_encoder *enc, int first_stream, int n_streams, const 
                            base + offsetof(iiv::StreamState, mem[1]), sizeof(iiv::StreamState), d_rgb, (hipStream_t)stream);
 }
 
+int iiv_encoder_render_error(iiv_encoder *enc, int first_stream, int n_streams, const uint8_t palette_rgb[48], const uint8_t *d_ref,
+                             int ref_width, uint64_t *d_out, void *stream)
+{
+    if (!enc || !palette_rgb || !d_ref || !d_out || first_stream < 0 || n_streams < 0 || n_streams > enc->n_streams - first_stream)
+        return iiv::set_error(IIV_ERR_INVALID, "iiv_encoder_render_error: bad argument or stream range");
+    if (ref_width != 280 && ref_width != 560)
+        return iiv::set_error(IIV_ERR_INVALID, "iiv_encoder_render_error: ref_width must be 280 or 560");
+    if (((uintptr_t)d_ref & 15) || ((uintptr_t)d_out & 7))
+        return iiv::set_error(IIV_ERR_INVALID, "iiv_encoder_render_error: d_ref must be 16-byte aligned, d_out 8-byte aligned");
+    if (n_streams == 0) return IIV_OK;
+    const uint8_t *base = reinterpret_cast<const uint8_t *>(enc->d_states + first_stream);   // (as iiv_encoder_render)
+    return iiv::render_error(enc->mode, palette_rgb, n_streams, base + offsetof(iiv::StreamState, mem[0]),
+                             base + offsetof(iiv::StreamState, mem[1]), sizeof(iiv::StreamState), d_ref, ref_width, d_out,
+                             (hipStream_t)stream);
+}
+
 int iiv_encoder_set_video_state(iiv_encoder *enc, int stream_index, const iiv_video_state *host_in)
 {
     return iiv::encoder_set_video_state(enc, stream_index, host_in);

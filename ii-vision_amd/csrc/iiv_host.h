@@ -146,4 +146,8 @@ int compute_delta_pages(int mode, const uint16_t *d_table, int n, const uint64_t
 int render_rgb(int mode, const uint8_t palette_rgb[48], int n, const uint8_t *d_main, const uint8_t *d_aux, size_t in_stride,
                uint8_t *d_rgb, hipStream_t st);
 
+// iiv_render_error.hip: the same frames against d_ref [n][192][ref_width][3] -> d_out [n][3][3]
+int render_error(int mode, const uint8_t palette_rgb[48], int n, const uint8_t *d_main, const uint8_t *d_aux, size_t in_stride,
+                 const uint8_t *d_ref, int ref_width, uint64_t *d_out, hipStream_t st);
+
 }  // namespace iiv

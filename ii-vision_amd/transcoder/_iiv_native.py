@@ -139,6 +139,9 @@ _SIGNATURES = {
     # ---- f7: preview
     "iiv_render_rgb": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "iiv_encoder_render": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    # ---- f8: screen error
+    "iiv_render_error": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "iiv_encoder_render_error": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
 }
 SYMBOLS = list(_SIGNATURES)
 
@@ -849,6 +852,61 @@ def encoder_render(encoder, palette_rgb, first_stream=0, n_streams=None, out=Non
     out = _render_out(n, out)
     check(lib().iiv_encoder_render(encoder._h, int(first_stream), n, hptr(pal), dptr(out), stream_ptr()))
     return out.view((n,) + RENDER_SIZE + (3,))
+
+
+# ---- f8: screen error -----------------------------------------------------------------
+
+REF_WIDTHS = (280, 560)    # a reference picture has one pixel per two dots or one per dot
+
+
+def _error_args(n, ref, out):
+    """Checks the reference (n, 192, 280 or 560, 3) and the (n, 3, 3) uint64 tensor an error call writes (new, or the caller's
+    contiguous CUDA `out` of 8-byte elements and that many bytes) -> (ref_width, out)."""
+    torch = _torch()
+    _cuda_u8(ref, "ref")
+    if ref.dim() != 4 or int(ref.shape[0]) != n or int(ref.shape[1]) != 192 or int(ref.shape[2]) not in REF_WIDTHS or int(ref.shape[3]) != 3:
+        raise ValueError("ref has shape %s, not (%d, 192, 280 or 560, 3)" % (tuple(ref.shape), n))
+    if out is None:
+        return int(ref.shape[2]), torch.empty((n, 3, 3), dtype=torch.uint64, device="cuda")
+    if not out.is_cuda or not out.is_contiguous() or out.element_size() != 8 or out.numel() != n * 9:
+        raise ValueError("out must be a contiguous CUDA tensor of n * 9 eight-byte integers")
+    return int(ref.shape[2]), out
+
+
+def render_error(mode, palette_rgb, main, aux, ref, out=None):
+    """main / aux: memory maps as render_rgb takes them; ref: contiguous CUDA uint8 (n, 192, W, 3), W = 560 (one pixel per dot)
+    or 280 (one per two dots) -> CUDA uint64 (n, 3, 3), [frame][level][channel]: the exact sums of squared differences between
+    the screen render_rgb would draw and ref, per dot (level 0), per quad of four dots (1) and per unit of sixteen (2)
+    (include/iivision.h: iiv_render_error).  The rendering never leaves the chip.  Asynchronous on torch's current stream."""
+    if mode not in (HGR, DHGR):
+        raise ValueError("mode must be HGR or DHGR")
+    for t, name in ((main, "main"), (aux, "aux")) if mode == DHGR else ((main, "main"),):
+        _cuda_u8(t, name)
+        if t.numel() % 8192 or t.numel() != main.numel():
+            raise ValueError("%s must hold n memory maps of 8192 bytes%s" % (name, "" if t is main else ", as many as main"))
+    n = main.numel() // 8192
+    pal = np.ascontiguousarray(palette_rgb, dtype=np.uint8).reshape(48)
+    width, out = _error_args(n, ref, out)
+    if n == 0:   # (nothing to measure, nothing written: empty tensors have no address to hand over)
+        return out.view((0, 3, 3))
+    check(lib().iiv_render_error(mode, hptr(pal), n, dptr(main), dptr(aux if mode == DHGR else None), dptr(ref), width, dptr(out),
+                                 stream_ptr()))
+    return out.view((n, 3, 3))
+
+
+def encoder_render_error(encoder, palette_rgb, ref, first_stream=0, n_streams=None, out=None):
+    """The same sums for the screens the streams first_stream .. of an Encoder hold right now (behind the launches already on
+    torch's current stream), measured on the encoder's own device state (iiv_encoder_render_error): ref[i] belongs to stream
+    first_stream + i -> CUDA uint64 (n_streams, 3, 3)."""
+    n = encoder.n_streams - int(first_stream) if n_streams is None else int(n_streams)
+    if first_stream < 0 or n < 0 or first_stream + n > encoder.n_streams:
+        raise ValueError("streams %d .. %d of an encoder of %d" % (first_stream, first_stream + n - 1, encoder.n_streams))
+    pal = np.ascontiguousarray(palette_rgb, dtype=np.uint8).reshape(48)
+    width, out = _error_args(n, ref, out)
+    if n == 0:
+        return out.view((0, 3, 3))
+    check(lib().iiv_encoder_render_error(encoder._h, int(first_stream), n, hptr(pal), dptr(ref), width, dptr(out), stream_ptr()))
+    return out.view((n, 3, 3))
 
 
 # ---- f4: the audio track ------------------------------------------------------------

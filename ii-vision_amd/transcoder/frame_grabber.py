@@ -99,14 +99,20 @@ class ArrayFrameGrabber(FrameGrabber):
         self.input_frame_rate = input_frame_rate
         self.batch = int(batch)
 
-    def memory_maps(self, first=0, count=None):
-        """(main, aux) CUDA uint8 tensors (count, 32, 256) of frames first .. first + count - 1:
-        the form stream_batch.StreamBatch consumes, without a trip through host memory maps."""
+    def ingest_frames(self, first=0, count=None):
+        """CUDA uint8 (count, H, W, 3): frames first .. first + count - 1 as the conversion takes them, after any resize --
+        the reference picture screen.render_error measures a screen against."""
         import torch
         count = len(self._rgb) - first if count is None else count
         rgb = torch.from_numpy(np.ascontiguousarray(self._rgb[first:first + count])).cuda()
         if self.resize and tuple(rgb.shape[1:3]) != self.frame_size:
-            rgb = native.resize_frames(rgb, size=self.frame_size)   # on the same stream as the conversion below
+            rgb = native.resize_frames(rgb, size=self.frame_size)   # on the same stream as the conversion behind it
+        return rgb
+
+    def memory_maps(self, first=0, count=None):
+        """(main, aux) CUDA uint8 tensors (count, 32, 256) of frames first .. first + count - 1:
+        the form stream_batch.StreamBatch consumes, without a trip through host memory maps."""
+        rgb = self.ingest_frames(first, count)
         mode = native.DHGR if self.video_mode == VideoMode.DHGR else native.HGR
         if self.palette == Palette.MONO:
             return native.frames_to_memory_maps_mono(mode, rgb, self.dither)

@@ -348,6 +348,37 @@ def render_rgb(main, aux, mode, palette):
     return native.render_rgb(mode_id, rgb, main, aux)
 
 
+def render_error(main, aux, mode, palette, ref):
+    """How far what memory maps put on the screen is from a reference picture: main / aux / mode / palette as render_rgb takes
+    them, ref a torch uint8 device tensor (n, 192, 560, 3) (one pixel per dot) or (n, 192, 280, 3) (one per two dots) ->
+    (n, 3, 3) uint64 device tensor [frame][level][channel] of exact sums of squared differences: level 0 per dot, level 1 per
+    quad of four dots (the differences of a quad are added before squaring), level 2 per unit of sixteen dots (include/
+    iivision.h: iiv_render_error; csrc/iiv_render_error.hip).  psnr() turns them into decibels.  Not in the reference."""
+    mode_id = {"HGR": native.HGR, "DHGR": native.DHGR}[mode.name] if hasattr(mode, "name") else int(mode)
+    rgb = pal.palette_class(palette).rgb_array() if isinstance(palette, pal.Palette) else palette
+    return native.render_error(mode_id, rgb, main, aux, ref)
+
+
+ERROR_CELLS = (107520, 26880, 6720)    # blocks per frame and channel at level 0 / 1 / 2: 192 x 560, 192 x 140, 192 x 35
+ERROR_BLOCK = (1, 4, 16)               # dots per block
+
+
+def psnr(sums, level=0):
+    """render_error's sums -> decibels, host float64.  sums: (..., 3, 3) [level][channel] (a tensor or an array); returns
+    (per_channel (..., 3), overall (...)).  With cells = 107 520 / 26 880 / 6 720 blocks per frame and channel and k = 1 / 4 / 16
+    dots per block at level 0 / 1 / 2, a block's difference is at most 255 k, so
+        per channel:  10 log10(255^2 * cells * k^2 / sum[level][channel])
+        overall:      10 log10(255^2 * 3 * cells * k^2 / (sum[level][0] + sum[level][1] + sum[level][2]))
+    and inf where the sum is zero."""
+    a = sums.cpu().numpy() if hasattr(sums, "cpu") else np.asarray(sums)
+    e = a[..., level, :].astype(np.float64)
+    peak = 255.0 ** 2 * ERROR_CELLS[level] * ERROR_BLOCK[level] ** 2
+    total = e.sum(axis=-1)
+    with np.errstate(divide="ignore"):
+        return (np.where(e > 0, 10 * np.log10(peak / np.where(e > 0, e, 1)), np.inf),
+                np.where(total > 0, 10 * np.log10(3 * peak / np.where(total > 0, total, 1)), np.inf))
+
+
 def _double(int7: int) -> int:
     """Each of bits 0..6 lights two dots; bit 6 a third (screen.py:712-739)."""
     out = 0

@@ -288,5 +288,15 @@ class StreamBatch:
         rgb = pal.palette_class(palette).rgb_array() if isinstance(palette, pal.Palette) else palette
         return native.encoder_render(self.enc, rgb)
 
+    def screens_error(self, ref, palette=None):
+        """How far every stream's screen is right now -- behind the launches already enqueued -- from its reference picture:
+        ref a (n_streams, 192, 560 or 280, 3) uint8 device tensor -> (n_streams, 3, 3) uint64 device tensor of exact sums of
+        squared differences [stream][level][channel] (screen.render_error; iiv_encoder_render_error), measured on the
+        encoder's own screen memory.  palette: as screens_rgb."""
+        import palette as pal
+        palette = pal.Palette.NTSC if palette is None else palette
+        rgb = pal.palette_class(palette).rgb_array() if isinstance(palette, pal.Palette) else palette
+        return native.encoder_render_error(self.enc, rgb, ref)
+
     def close(self):
         self.enc.close()

@@ -309,6 +309,19 @@ class Video:
             self._settle(download=False)
         return native.encoder_render(self._enc, palette_class(self.palette).rgb_array())[0]
 
+    def screen_error(self, ref_rgb):
+        """How far the screen after the opcodes consumed so far is from ref_rgb, a (192, 560, 3) or (192, 280, 3) uint8 device
+        tensor: a (3, 3) uint64 device tensor [level][channel] of exact sums of squared differences in this Video's palette
+        (screen.render_error and screen.psnr say what they mean; iiv_encoder_render_error).  Not in the reference.  Settles
+        as screen_rgb does."""
+        from palette import palette_class
+        if self._touched:
+            self._settle()
+            self._upload()
+        else:
+            self._settle(download=False)
+        return native.encoder_render_error(self._enc, palette_class(self.palette).rgb_array(), ref_rgb[None].contiguous())[0]
+
     def tick(self, ticks: int) -> bool:
         """Keep track of when it is time for a new image frame (video.py:64-70)."""
         self._tick_now = ticks

@@ -662,6 +662,39 @@ int iiv_render_rgb(int mode, const uint8_t palette_rgb[48], int n, const uint8_t
 int iiv_encoder_render(iiv_encoder *enc, int first_stream, int n_streams, const uint8_t palette_rgb[48], uint8_t *d_rgb,
                        void *stream);
 
+/* ==== f8: screen error ======================================================
+ * How far is what the screen shows from a reference picture: exact integer sums of squared differences, per frame, per
+ * colour channel, at three block sizes, computed on the device without the rendered picture ever leaving the chip
+ * (csrc/iiv_render_error.hip; tests/render_error_model.py restates this section on top of tests/render_model.py).
+ *   S[f][y][x][c] is the byte iiv_render_rgb (f7) would write for frame f: 192 rows of 560 dots, 3 channels.
+ *   d_ref is [n][192][ref_width][3] u8, ref_width 560 (one reference pixel per dot: what the mono ingest takes) or 280 (one per
+ *   two dots: what the colour ingest and the resize deliver): R[f][y][x][c] = ref[f][y][x * ref_width / 560][c].
+ *   D = (int)S - (int)R.
+ *   d_out is [n][3][3] uint64, [frame][level][channel]:
+ *     level 0 (dot):                     sum over y, x of D[y][x]^2
+ *     level 1 (quad of four dots: the colour pixel of the 140-wide ingest):
+ *                                        sum over y, q < 140 of (D[y][4q] + D[y][4q+1] + D[y][4q+2] + D[y][4q+3])^2
+ *     level 2 (unit of sixteen dots):    sum over y, u < 35 of (sum over k < 16 of D[y][16u+k])^2
+ *   Levels 1 and 2 are low-passed errors: a dithered picture is meant to be wrong per dot and right on average, and level 0
+ *   alone would rank "no dither" first.  Every block lies in one row (there is no vertical low-pass).
+ * The call overwrites all 72 bytes of every frame; the caller need not zero d_out.  The sums are integers, so d_out is exact
+ * whatever the order of summation; the largest possible per frame are 107 520 * 255^2 (7.0e9), 26 880 * 1020^2 (2.8e10) and
+ * 6 720 * 4080^2 (1.1e11, with D = +-255 everywhere): none fits 32 bits.
+ * d_main / d_aux: [n][32][256] u8 memory maps, 8-byte aligned, as for f7 (screen holes are never read; d_aux is ignored and
+ * may be NULL in HGR); d_ref 16-byte aligned; d_out 8-byte aligned.  Asynchronous on `stream`; the palette is read before
+ * the call returns; nothing is allocated.  n == 0 succeeds and writes nothing.  IIV_ERR_INVALID before anything is launched,
+ * with nothing written: a bad mode, n < 0, a NULL palette_rgb, d_main, d_ref or d_out, a NULL d_aux in DHGR, ref_width not
+ * 280 or 560, a bad alignment. */
+int iiv_render_error(int mode, const uint8_t palette_rgb[48], int n, const uint8_t *d_main, const uint8_t *d_aux,
+                     const uint8_t *d_ref, int ref_width, uint64_t *d_out, void *stream);
+
+/* The same measurement of the encoder's OWN device copy of the maps, as iiv_encoder_render renders them, for streams
+ * first_stream .. first_stream + n_streams - 1: reference picture i of d_ref [n_streams][192][ref_width][3] belongs to
+ * stream first_stream + i, d_out is [n_streams][3][3].  Refusals as iiv_render_error's, and a stream range that is not inside
+ * the encoder's.  It changes nothing in the encoder; ordering against a running encode is by `stream`. */
+int iiv_encoder_render_error(iiv_encoder *enc, int first_stream, int n_streams, const uint8_t palette_rgb[48],
+                             const uint8_t *d_ref, int ref_width, uint64_t *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

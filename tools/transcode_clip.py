@@ -20,7 +20,11 @@ opcodes._parse_symbol_table does (opcodes.py:168-185); without it the stream is 
 and is NOT playable (the tool says so).  --fourth / --joint: the two optional quality modes.
 --preview FILE.npy: also write what the stream puts on the screen, a uint8 array (frames, 192, 560, 3): the screen as it stands
 after each source frame's opcodes, drawn on the device from the encoder's own screen memory in the clip's palette
-(csrc/iiv_render.hip).  The .a2m bytes are the same with and without it."""
+(csrc/iiv_render.hip).  The .a2m bytes are the same with and without it.
+--quality FILE.json: also measure that screen against the frame that went into the ingest (after any resize: 280 wide, 560
+for --palette MONO in DHGR), on the device (csrc/iiv_render_error.hip): per source frame the nine exact sums of
+squared differences [level][channel] -- per dot, per quad of four dots, per unit of sixteen -- and the overall PSNR of each
+level (screen.psnr).  The .a2m bytes and the --preview array are the same with and without it."""
 import argparse
 import os
 import sys
@@ -64,6 +68,8 @@ def main():
     ap.add_argument("--fourth", action="store_true", help="IIV_OPT_FOURTH_OFFSET (not the reference's stream)")
     ap.add_argument("--joint", action="store_true", help="IIV_CONTENT_JOINT (not the reference's stream)")
     ap.add_argument("--preview", metavar="FILE.npy", help="also write the screen after each source frame's opcodes: uint8 (frames, 192, 560, 3)")
+    ap.add_argument("--quality", metavar="FILE.json",
+                    help="also write, per source frame, the screen's squared error against the ingest's input frame (nine sums) and three PSNRs")
     ap.add_argument("--seed", type=int, default=1, help="random.seed / np.random.seed of the encoder's two nonce streams")
     a = ap.parse_args()
     if a.tick < 4 or a.tick > 66 or a.tick % 2:
@@ -110,19 +116,37 @@ def main():
     else:
         max_ticks = None
     frames_main, frames_aux = main_maps[None], aux_maps[None] if aux_maps is not None else None
-    if a.preview:
-        # the same schedule one source frame per call (MovieClock continues a movie across calls), the screen drawn behind each
-        parts, segs, shots, left = [], [], [], max_ticks
+    if a.preview or a.quality:
+        # the same schedule one source frame per call (MovieClock continues a movie across calls), the screen drawn and
+        # measured behind each
+        parts, segs, shots, sums, left = [], [], [], [], max_ticks
+        ref = grab.ingest_frames() if a.quality else None
         for _ in range(n):
             if left is None or left > 0:
                 o, s = batch.encode_frames(frames_main, frames_aux, 1, max_ticks=left)
                 parts.append(o)
                 segs += s
                 left = None if left is None else left - int(o.shape[1])
-            shots.append(batch.screens_rgb(pal_id))     # (the audio has run out: the screen stays as it is)
+            if a.preview:
+                shots.append(batch.screens_rgb(pal_id))     # (the audio has run out: the screen stays as it is)
+            if a.quality:
+                sums.append(batch.screens_error(ref[len(sums):len(sums) + 1], pal_id))
         ops = torch.cat(parts, dim=1)
         batch.enc.check()
-        np.save(a.preview, torch.cat(shots).cpu().numpy())
+        if a.preview:
+            np.save(a.preview, torch.cat(shots).cpu().numpy())
+        if a.quality:
+            import json
+            import screen
+            host = np.stack([t.cpu().numpy()[0] for t in sums])                   # (frames, 3, 3) uint64
+            db = [screen.psnr(host, level)[1] for level in range(3)]
+            with open(a.quality, "w") as f:
+                json.dump({"mode": a.mode, "palette": a.palette, "ref_width": int(ref.shape[2]), "levels": ["dot", "quad", "unit"],
+                           "channels": ["R", "G", "B"],
+                           "frames": [{"frame": i, "sums": [[int(v) for v in row] for row in host[i]],
+                                       "psnr_db": [float(db[level][i]) for level in range(3)]} for i in range(n)]}, f, indent=1)
+            print("screen against source, mean PSNR over %d frames: dot %.2f dB, quad %.2f dB, unit %.2f dB -> %s" % (
+                n, *(float(np.mean(d)) for d in db), a.quality))
     else:
         ops, segs = batch.encode_frames(frames_main, frames_aux, n, max_ticks=max_ticks)
         batch.enc.check()
