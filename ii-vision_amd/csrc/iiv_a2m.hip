@@ -9,16 +9,9 @@
 // (movie.py:139-148).  One thread per opcode writes its 7 bytes (and the ACK that
 // follows it, if any) straight to its final position.
 #include "iiv_host.h"
+#include "iiv_a2m_layout.h"
 
 namespace iiv {
-
-// stream position at which tick opcode k starts
-__host__ __device__ static inline size_t tick_offset(long k)
-{
-    if (k < 291) return 7 + 7 * (size_t)k;
-    long g = (k - 291) / 292, r = (k - 291) % 292;
-    return 2048 * (size_t)(1 + g) + 7 * (size_t)r;
-}
 
 // opcodes emitted before max_bytes_out stops the stream (movie.py:132-134)
 static long emitted_ops(long n_ops, long max_bytes_out)

@@ -142,6 +142,13 @@ _SIGNATURES = {
     # ---- f8: screen error
     "iiv_render_error": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "iiv_encoder_render_error": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
+    # ---- f9: reading an opcode stream
+    "iiv_a2m_reader_create": (_i32, [_vp, _u16, _u16, C.POINTER(_vp)]),
+    "iiv_a2m_reader_destroy": (None, [_vp]),
+    "iiv_a2m_max_ops": (_lg, [_sz]),
+    "iiv_a2m_scan": (_i32, [_vp, _i32, _vp, _sz, _vp, _vp, _vp]),
+    "iiv_a2m_decode": (_i32, [_vp, _i32, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "iiv_a2m_replay": (_i32, [_vp, _i32, _vp, _sz, _vp, _lg, _lg, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 SYMBOLS = list(_SIGNATURES)
 
@@ -907,6 +914,104 @@ def encoder_render_error(encoder, palette_rgb, ref, first_stream=0, n_streams=No
         return out.view((0, 3, 3))
     check(lib().iiv_encoder_render_error(encoder._h, int(first_stream), n, hptr(pal), dptr(ref), width, dptr(out), stream_ptr()))
     return out.view((n, 3, 3))
+
+
+# ---- f9: reading an opcode stream -------------------------------------------------------
+
+A2M_STATUS = ("OK", "BAD_LENGTH", "BAD_HEADER", "BAD_ACK", "BAD_ADDRESS", "NO_TERMINATE", "BAD_PADDING")   # IIV_A2M_*
+A2M_OK = 0
+
+
+def a2m_max_ops(length):
+    """Whole opcode slots in a stream of that many bytes (iiv_a2m_max_ops).  Host only."""
+    return int(lib().iiv_a2m_max_ops(int(length)))
+
+
+class A2mReaderHandle:
+    """An iiv_a2m_reader: the device copy of the address table the reading kernels look opcodes up in.  Creation raises
+    IIVError(ERR_INVALID), before the device is touched, unless the 1024 tick addresses, ack and terminate are pairwise distinct."""
+
+    def __init__(self, tick_addr, ack_addr, terminate_addr):
+        ta = np.ascontiguousarray(tick_addr, dtype=np.uint16).reshape(1024)
+        h = C.c_void_p()
+        check(lib().iiv_a2m_reader_create(hptr(ta), int(ack_addr), int(terminate_addr), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().iiv_a2m_reader_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _batch(data):
+        _cuda_u8(data, "data")
+        if data.dim() != 2 or int(data.shape[1]) < 2048:
+            raise ValueError("data has shape %s, not (n_streams, stride >= 2048)" % (tuple(data.shape),))
+        return int(data.shape[0]), int(data.shape[1])
+
+    @staticmethod
+    def _info(info, n):
+        torch = _torch()
+        if not (isinstance(info, torch.Tensor) and info.is_cuda and info.dtype == torch.int64 and info.is_contiguous()
+                and tuple(info.shape) == (n, 4)):
+            raise ValueError("info must be a contiguous CUDA int64 tensor (%d, 4), as scan returns it" % n)
+
+    def scan(self, data, lengths):
+        """data: CUDA uint8 (S, stride); lengths: CUDA int64 (S,) -> CUDA int64 (S, 4) {status, mode, n_ops, position}.
+        Asynchronous on torch's current stream."""
+        torch = _torch()
+        S, stride = self._batch(data)
+        if not (isinstance(lengths, torch.Tensor) and lengths.is_cuda and lengths.dtype == torch.int64 and lengths.is_contiguous()
+                and tuple(lengths.shape) == (S,)):
+            raise ValueError("lengths must be a contiguous CUDA int64 tensor (%d,)" % S)
+        info = torch.empty((S, 4), dtype=torch.int64, device="cuda")
+        if S:
+            check(lib().iiv_a2m_scan(self._h, S, dptr(data), stride, dptr(lengths), dptr(info), stream_ptr()))
+        return info
+
+    def decode(self, data, info):
+        """-> CUDA uint8 ops (S, max_ops, 6), ticks (S, max_ops), banks (S, max_ops), max_ops = a2m_max_ops(stride); row s is
+        written up to info[s, 2] and zero behind it.  Asynchronous."""
+        torch = _torch()
+        S, stride = self._batch(data)
+        self._info(info, S)
+        n = a2m_max_ops(stride)
+        ops = torch.zeros((S, n, 6), dtype=torch.uint8, device="cuda")
+        ticks = torch.zeros((S, n), dtype=torch.uint8, device="cuda")
+        banks = torch.zeros((S, n), dtype=torch.uint8, device="cuda")
+        if S:
+            check(lib().iiv_a2m_decode(self._h, S, dptr(data), stride, dptr(info), dptr(ops), n * 6, dptr(ticks), dptr(banks), n,
+                                       stream_ptr()))
+        return ops, ticks, banks
+
+    def replay(self, data, info, first, every, n, init=None):
+        """-> (main, aux) CUDA uint8 (S, n, 32, 256): snapshot j after the first min(first + j * every, n_ops) opcodes.
+        init: (main, aux) contiguous CUDA uint8 (S, 32, 256) starting state, None = zeros.  Asynchronous."""
+        torch = _torch()
+        S, stride = self._batch(data)
+        self._info(info, S)
+        first, every, n = int(first), int(every), int(n)
+        if first < 0 or every < 1 or n < 1:
+            raise ValueError("replay: first >= 0, every >= 1, n >= 1")
+        im = ia = None
+        if init is not None:
+            im, ia = init
+            for t in (im, ia):
+                _cuda_u8(t, "each init tensor")
+                if t.numel() != S * 8192:
+                    raise ValueError("each init tensor must hold n_streams * 8192 bytes")
+        main = torch.empty((S, n, 32, 256), dtype=torch.uint8, device="cuda")
+        aux = torch.empty((S, n, 32, 256), dtype=torch.uint8, device="cuda")
+        if S:
+            check(lib().iiv_a2m_replay(self._h, S, dptr(data), stride, dptr(info), min(first, 2 ** 62), min(every, 2 ** 62), n,
+                                       dptr(im), dptr(ia), dptr(main), dptr(aux), stream_ptr()))
+        return main, aux
 
 
 # ---- f4: the audio track ------------------------------------------------------------

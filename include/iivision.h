@@ -695,6 +695,75 @@ int iiv_render_error(int mode, const uint8_t palette_rgb[48], int n, const uint8
 int iiv_encoder_render_error(iiv_encoder *enc, int first_stream, int n_streams, const uint8_t palette_rgb[48],
                              const uint8_t *d_ref, int ref_width, uint64_t *d_out, void *stream);
 
+/* ==== f9: reading an opcode stream ==========================================
+ * The inverse of f2: a stream as written -- by iiv_emit_stream, by the reference's Movie, by an older build -- is checked,
+ * decoded back to the encoder's records, and replayed to the screen memory a player holds after k opcodes, which is what f7
+ * and f8 take (csrc/iiv_a2m_read.hip; tests/a2m_model.py restates this section in numpy).
+ *   Layout.  L is the stream's length.  Slot k is the 7 bytes at P(k): P(k) = 7 + 7 k for k < 291, and
+ *   2048 (1 + (k - 291) / 292) + 7 ((k - 291) % 292) from there on (the position f2 writes opcode k at).  A slot's address is
+ *   big-endian in its first two bytes.  T is the 1024-entry tick-address table [(tick - 4) / 2][page - 32].  n_ops is the
+ *   index of the first slot whose address is not in T, or the number of whole slots that fit (P(k) + 7 <= L) if there is no
+ *   such slot.  After a tick slot k with (P(k) + 7) % 2048 == 2044 comes an ACK: the ack address, a bank byte, 0xff.  The bank
+ *   of opcode k is bit 0 of the bank byte of the last ACK before it, 0 before the first ACK.  The stream's mode is byte 6.
+ *   Status.  Of several offences the one at the lowest byte position is reported; a stream with an offence still has a
+ *   well-defined n_ops and banks (BAD_LENGTH: n_ops = 0, mode = 0).
+ *     IIV_A2M_BAD_LENGTH    L <= 0, L % 2048 != 0, or L above the batch's stride; position 0, nothing else is examined
+ *     IIV_A2M_BAD_HEADER    a byte 0..5 is not 0xff, or byte 6 is not 0 or 1; that byte (mode reports byte 6 as it is)
+ *     IIV_A2M_BAD_ACK       an ACK before slot n_ops has a wrong address, a bank byte that is not 0x54 / 0x55, or a fourth byte
+ *                           that is not 0xff; the first wrong byte
+ *     IIV_A2M_BAD_ADDRESS   slot n_ops exists and its address is not the terminate address; P(n_ops)
+ *     IIV_A2M_NO_TERMINATE  no slot n_ops fits; P(n_ops)
+ *     IIV_A2M_BAD_PADDING   a non-zero byte behind Terminate (from P(n_ops) + 2 on): that byte; or L is not P(n_ops) + 2
+ *                           rounded up to a multiple of 2048: that rounded value
+ * The reader owns the device copy of the table the kernels look addresses up in (65 536 x u16); one owner, destroyed once,
+ * not while a call that uses it is in flight.  Creation refuses (IIV_ERR_INVALID, before the device is touched) addresses
+ * that are not pairwise distinct among the 1024 tick addresses, the ack and the terminate address. */
+#define IIV_A2M_OK 0
+#define IIV_A2M_BAD_LENGTH 1
+#define IIV_A2M_BAD_HEADER 2
+#define IIV_A2M_BAD_ACK 3
+#define IIV_A2M_BAD_ADDRESS 4
+#define IIV_A2M_NO_TERMINATE 5
+#define IIV_A2M_BAD_PADDING 6
+
+typedef struct iiv_a2m_reader iiv_a2m_reader;
+
+int iiv_a2m_reader_create(const uint16_t tick_addr[1024], uint16_t ack_addr, uint16_t terminate_addr, iiv_a2m_reader **out);
+void iiv_a2m_reader_destroy(iiv_a2m_reader *reader);
+
+/* Whole slots in a stream of `length` bytes: the largest n_ops a stream of that length can have.  Host only, closed form. */
+long iiv_a2m_max_ops(size_t length);
+
+/* The three calls below take n_streams streams at d_bytes + s * stride (stride >= 2048; every byte of a row up to its length is
+ * read, none behind it).  They are asynchronous on `stream` and allocate nothing.  IIV_ERR_INVALID before anything is launched,
+ * with nothing written: a NULL reader or pointer (d_init_main / d_init_aux may be NULL), n_streams < 0, stride < 2048, a bad
+ * alignment, a bad count.  n_streams == 0 succeeds and writes nothing.
+ *
+ * iiv_a2m_scan: d_lengths is int64 [n_streams], d_info int64 [n_streams][4] = {status, mode, n_ops, position}, both on the
+ * device and 8-byte aligned.  Slots and ACKs are checked one thread each; the lowest position is found by a minimum over
+ * values that depend on the bytes alone, so the result does not depend on scheduling. */
+int iiv_a2m_scan(const iiv_a2m_reader *reader, int n_streams, const uint8_t *d_bytes, size_t stride, const int64_t *d_lengths,
+                 int64_t *d_info, void *stream);
+
+/* The inverse of iiv_emit_stream.  For every stream the first n_ops (of d_info, a scan's output, whatever its status) opcodes as
+ * the encoder's 6-byte records {page, content, four offsets} at d_ops + s * ops_stride, their ticks (4..66) at
+ * d_ticks + s * ticks_stride and their banks (0 / 1) at d_banks + s * ticks_stride.  Bytes past n_ops are left alone.
+ * ops_stride >= 6 * iiv_a2m_max_ops(stride) and ticks_stride >= iiv_a2m_max_ops(stride), so that no d_info can take a write
+ * out of a row. */
+int iiv_a2m_decode(const iiv_a2m_reader *reader, int n_streams, const uint8_t *d_bytes, size_t stride, const int64_t *d_info,
+                   uint8_t *d_ops, size_t ops_stride, uint8_t *d_ticks, uint8_t *d_banks, size_t ticks_stride, void *stream);
+
+/* Snapshot j, j < n_snaps, is the 2 x 8 KiB of screen memory after the first min(first_snap + j * snap_every, n_ops) opcodes of
+ * the stream: opcodes apply in stream order, each storing its content byte at its four offsets of its page, in its bank --
+ * replay follows the bank bytes and does not read the mode, so d_aux is always written (all initial state for a well-formed
+ * HGR stream).  The starting state is d_init_main / d_init_aux [n_streams][32][256], NULL = zeros.  d_main / d_aux are
+ * [n_streams][n_snaps][32][256]; they and the initial maps are 8-byte aligned, so a snapshot tensor goes straight into
+ * iiv_render_rgb and iiv_render_error.  first_snap >= 0, snap_every >= 1, n_snaps >= 1.  An opcode takes 73 cycles whatever it
+ * does, so uniform sampling in opcodes is uniform sampling in time. */
+int iiv_a2m_replay(const iiv_a2m_reader *reader, int n_streams, const uint8_t *d_bytes, size_t stride, const int64_t *d_info,
+                   long first_snap, long snap_every, int n_snaps, const uint8_t *d_init_main, const uint8_t *d_init_aux,
+                   uint8_t *d_main, uint8_t *d_aux, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,7 +154,7 @@ def main():
         addr = a2m.OpcodeAddresses.from_debug_file(a.dbg)
     else:
         print("no --dbg: placeholder opcode addresses -- the stream has the right layout but is NOT playable", file=sys.stderr)
-        addr = a2m.OpcodeAddresses(0x8000 + 16 * np.arange(1024, dtype=np.uint16).reshape(32, 32), 0xc000, 0xc100)
+        addr = a2m.OpcodeAddresses.placeholder()
     if au is None:
         ticks = torch.full((1, ops.shape[1]), a.tick, dtype=torch.uint8, device="cuda")
     else:
