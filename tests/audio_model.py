@@ -105,3 +105,37 @@ def ticks_from_values(a, norm):
 
 def ticks(pcm, channels, rate, norm, bitrate=BITRATE, block_frames=BLOCK_FRAMES):
     return ticks_from_values(stream_values(pcm, channels, rate, bitrate, block_frames), norm)
+
+
+# ---- what the GPU tests and tests/stage_fuzz.py share: the test signals and the criterion for ticks --------------------
+
+SIGNAL_KINDS = ("sine", "chirp", "noise", "loud")
+
+
+def signal(kind, n, channels, seed):
+    """int16 (n, channels)"""
+    rng = np.random.default_rng(seed)
+    t = np.arange(n) / 44100.0
+    if kind == "sine":
+        x = 9000 * np.sin(2 * np.pi * 440 * t) + 4000 * np.sin(2 * np.pi * 3111 * t + 1)
+    elif kind == "chirp":
+        x = 12000 * np.sin(2 * np.pi * (50 * t + 4000 * t * t))
+    elif kind == "noise":
+        x = rng.normal(0, 6000, n)
+    elif kind == "loud":   # clipping-heavy: mostly beyond the 0.5 / 99.5 percentiles' range after normalisation
+        x = 32000 * np.sign(np.sin(2 * np.pi * 97 * t)) + rng.normal(0, 3000, n)
+    else:
+        raise ValueError(kind)
+    out = np.empty((n, channels))
+    for c in range(channels):
+        out[:, c] = x * (1.0 - 0.3 * c) + rng.normal(0, 200, n)
+    return np.clip(np.round(out), -32768, 32767).astype(np.int16)
+
+
+def check_ticks(got, want, v):
+    """equal, except within 1e-3 of an integer of the model's a * 16 (one level), fewer than 0.5 % of the samples"""
+    bad = got != want
+    near = np.abs(v - np.round(v)) < 1e-3
+    assert not (bad & ~near).any(), "ticks differ away from a level boundary at %s" % np.nonzero(bad & ~near)[0][:10]
+    assert (np.abs(got.astype(int) - want.astype(int))[bad] <= 2).all()
+    assert bad.sum() < 0.005 * max(len(want), 1)

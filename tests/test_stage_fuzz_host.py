@@ -1,0 +1,219 @@
+"""The generator of tests/stage_fuzz.py, without a device: a fuzz that draws the same case every round, or asks the library for
+a refusal by accident, proves nothing.  For the committed seed and round counts: every category the stages force occurs, every
+drawn case lies inside its entry point's documented preconditions (include/iivision.h), and no audio stream sits on the level
+boundaries often enough for check_ticks' 0.5 % allowance to matter."""
+import numpy as np
+import pytest
+
+import a2m_model
+import audio_model
+import diffusion_model
+import ingest_model
+import resize_model
+import stage_fuzz as F
+
+
+def _cases(stage, rounds=None):
+    return [F.DRAW[stage](F.stage_rng(F.SEED, r, stage), r) for r in range(rounds or F.ROUNDS[stage])]
+
+
+@pytest.fixture(scope="module")
+def cases():
+    return {stage: _cases(stage) for stage in F.STAGES}
+
+
+def test_round_counts():
+    assert F.ROUNDS == {"resize": 12, "ingest": 12, "mono": 12, "render": 12, "a2m": 12, "audio": 12, "chain": 4}
+
+
+def test_a_case_is_a_function_of_seed_round_and_stage(cases):
+    for stage in F.STAGES:
+        lines = [F.describe(c) for c in cases[stage]]
+        assert lines == [F.describe(c) for c in _cases(stage)], stage
+        assert len(set(lines)) == len(lines), stage                                   # no two rounds alike
+        other = F.DRAW[stage](F.stage_rng(F.SEED + 1, 0, stage), 0)
+        assert F.describe(other) != lines[0], stage
+    a, b = F.stage_rng(F.SEED, 3, "resize"), F.stage_rng(F.SEED, 3, "mono")
+    assert a.integers(1 << 30) != b.integers(1 << 30)
+
+
+def test_a_failure_names_seed_round_and_parameters():
+    case = F.draw_resize(F.stage_rng(F.SEED, 5, "resize"), 5)
+    case["seed"], case["round"] = F.SEED, 5
+    with pytest.raises(AssertionError) as e:
+        F._same(case, "resize_frames", np.zeros((1, 2)), np.ones((1, 2)))
+    msg = str(e.value)
+    assert "seed=%d round=5" % F.SEED in msg and "h=%d" % case["params"]["h"] in msg and "--stage resize --round 5" in msg
+
+
+def test_resize_draws(cases):
+    seen = set()
+    for c in cases["resize"]:
+        p = c["params"]
+        n, h, w, H, W = (p[k] for k in ("n", "h", "w", "H", "W"))
+        assert 1 <= n <= 5 and 1 <= h <= 8192 and 1 <= w <= 8192 and 1 <= H <= 1024 and 1 <= W <= 1024      # iiv_resize_frames
+        assert c["frames"].shape == (n, h, w, 3) and c["frames"].dtype == np.uint8
+        big = c["big"]
+        if p["view"] is None:
+            assert big is c["frames"]
+            seen.add("contiguous")
+        else:
+            f0, step, ro, co = p["view"]
+            v = big[f0:f0 + n * step:step, ro:ro + h, co:co + w]
+            assert v.shape == c["frames"].shape and np.array_equal(v, c["frames"])      # inside the allocation, rows do not overlap
+            assert p["align"] == (v.__array_interface__["data"][0] - big.__array_interface__["data"][0]) % 4
+            seen.add("view")
+            seen.add("step %d" % step)
+            if p["align"]:
+                seen.add("misaligned view")
+        seen.add(p["content"])
+        if H == h and W == w:
+            seen.add("copy")
+        elif H == h:
+            seen.add("horizontal pass only")
+        elif W == w:
+            seen.add("vertical pass only")
+        elif resize_model.vertical_first(h, w):
+            seen.add("vertical first")
+        else:
+            seen.add("horizontal first")
+        if (H, W) == (192, 280):
+            seen.add("192x280")
+    assert seen >= {"contiguous", "view", "step 1", "step 2", "misaligned view", "noise", "checker", "ramp", "copy", "horizontal pass only",
+                    "vertical pass only", "vertical first", "horizontal first", "192x280"}, seen
+    for first in (0, 8, 16):      # every 8 rounds, wherever they start
+        kinds = [(c["params"]["H"] == c["params"]["h"], c["params"]["W"] == c["params"]["w"],
+                  resize_model.vertical_first(c["params"]["h"], c["params"]["w"])) for c in _cases("resize", first + 8)[first:]]
+        assert (True, False, False) in kinds and (False, True, False) in kinds and any(k[:2] == (True, True) for k in kinds)
+        assert any(k[2] for k in kinds)
+
+
+def test_ingest_draws(cases):
+    import frame_grabber
+    families = set()
+    for c in cases["ingest"]:
+        p = c["params"]
+        assert p["mode"] in (0, 1) and p["palette"] in ingest_model.NAMES and 1 <= p["n"] <= 70
+        assert p["lead_main"] % 8 == 0 and p["lead_aux"] % 8 == 0 and (p["frame_offset"] * F.FRAME_BYTES) % 4 == 0
+        assert len(c["idx"]) == p["n"] and set(c["idx"].tolist()) == set(range(len(p["pool"]))) and len(p["pool"]) <= 3
+        families.add(c["family"])
+        if c["weights"] is None:
+            assert 0 <= c["divisor"] <= 255 or c["divisor"] == F.DIFFUSION
+        else:
+            w = diffusion_model.check_arguments(c["weights"], c["divisor"])        # the contract's refusals, as a ValueError
+            assert not w[0, :3].any() and w.sum() <= c["divisor"] <= 64
+            if c["family"] == "named":
+                assert (tuple(tuple(int(v) for v in r) for r in w), c["divisor"]) in [
+                    (tuple(tuple(r) for r in k), d) for k, d in frame_grabber.DIFFUSION_KERNELS.values()]
+    assert families == set(F.DITHER_FAMILIES)
+    # the random kernels stay inside the contract wherever they are drawn, and do not all look alike
+    rng = np.random.default_rng(5)
+    drawn = [F._random_kernel(rng) for _ in range(300)]
+    for w, d in drawn:
+        diffusion_model.check_arguments(w, d)
+    assert len(set(drawn)) > 250 and any(sum(w) == d for w, d in drawn) and any(np.count_nonzero(w) >= 6 for w, d in drawn)
+    frames = F.ingest_pool_frames([(k, 7) for k in range(7)], "ntsc")
+    assert frames.shape == (7, 192, 280, 3) and len({f.tobytes() for f in frames}) == 7
+    assert F.HOLES.sum() == 8192 - 192 * 40
+
+
+def test_mono_draws(cases):
+    families, modes = set(), set()
+    for c in cases["mono"]:
+        p = c["params"]
+        assert p["mode"] in (0, 1) and 1 <= p["n"] <= 70 and (0 <= p["dither"] <= 255 or p["dither"] == F.DIFFUSION)
+        assert p["lead_main"] % 8 == 0 and p["lead_aux"] % 8 == 0 and len(c["idx"]) == p["n"] and c["idx"].max() < 16
+        assert (p["frame_offset"] * 192 * (560 if p["mode"] else 280) * 3) % 4 == 0
+        families.add(c["family"])
+        modes.add(p["mode"])
+    assert families == {"ordered", "fs"} and modes == {0, 1}
+    for mode in (0, 1):
+        assert F.mono_pool_frames(mode, 3).shape == (16, 192, 560 if mode else 280, 3)
+
+
+def test_render_draws(cases):
+    seen = set()
+    for c in cases["render"]:
+        p = c["params"]
+        assert p["n"] in (1, 2, 3, 5, 17) and p["palette"] in F.RENDER_PALETTES and p["ref_width"] in (280, 560)
+        assert p["lead_main"] % 8 == 0 and p["lead_aux"] % 8 == 0 and p["lead_rgb"] % 16 == 0 and p["lead_ref"] % 16 == 0
+        assert min(p["lead_main"], p["lead_aux"]) >= 8 and min(p["lead_rgb"], p["lead_ref"]) >= 16 and p["lead_sums"] >= 1
+        assert p["ref"] == "noise" or p["ref_width"] == 560
+        seen |= {("mode", p["mode"]), p["ref"], p["ref_width"]}
+        if p["lead_main"] % 16 == 8 or p["lead_aux"] % 16 == 8:
+            seen.add("maps at 8 and no more")
+        if p["lead_rgb"] % 32 == 16:
+            seen.add("output at 16 and no more")
+    assert seen >= {("mode", 0), ("mode", 1), "own", "noise", 280, 560, "maps at 8 and no more", "output at 16 and no more"}, seen
+
+
+def test_a2m_draws(cases, O):
+    seen = set()
+    for c in cases["a2m"]:
+        p = c["params"]
+        S, n, kept, length = p["S"], p["n_ops"], p["kept"], p["length"]
+        assert 1 <= S <= 4 and c["ops"].shape == (S, n, 6) and c["ticks"].shape == (S, n)
+        assert ((c["ops"][:, :, 0] >= 32) & (c["ops"][:, :, 0] <= 63)).all()                         # iiv_emit_stream's refusals
+        assert ((c["ticks"] >= 4) & (c["ticks"] <= 66) & (c["ticks"] % 2 == 0)).all()
+        assert p["stride"] >= length >= 2048 and length % 2048 == 0
+        assert p["first"] >= 0 and p["every"] >= 1 and 1 <= p["n"] <= 5 and p["first"] + p["n"] * p["every"] < 1 << 62
+        # the prefix max_bytes_out keeps and the stream's length, as the oracle's emitter has them
+        addr = O.PALETTE_RGB and (0x8000 + 16 * np.arange(1024, dtype=np.uint16), 0xc000, 0xc100)
+        want = O.emit_stream(p["mode"], c["ops"][0], c["ticks"][0], addr[0], addr[1], addr[2], p["max_bytes_out"])
+        assert len(want) == length and a2m_model.scan(want, *addr) == (a2m_model.OK, p["mode"], kept, 0)
+        if p["corrupt"] is not None:
+            s, pos, x = p["corrupt"]
+            assert 0 <= s < S and 0 <= pos < length and 1 <= x <= 255
+            seen.add("corrupted")
+            bad = want.copy()
+            bad[pos] ^= x
+            seen.add(a2m_model.STATUS_NAMES[a2m_model.scan(bad, *addr)[0]])
+        seen.add("cut" if kept < n else "whole")
+        if p["first"] == kept:
+            seen.add("first == n_ops")
+        if p["every"] > kept:
+            seen.add("every > n_ops")
+        if p["stride"] > length:
+            seen.add("stride > length")
+        if kept > 291:
+            seen.add("an ACK")
+        seen.add(("init", p["init"]))
+        seen.add(p["addresses"])
+    assert seen >= {"corrupted", "cut", "whole", "first == n_ops", "every > n_ops", "stride > length", "an ACK", ("init", True),
+                    ("init", False), "placeholder", "golden"}, seen
+    assert len(seen & set(a2m_model.STATUS_NAMES[1:])) >= 1, seen                                      # a change the scan rejects
+    assert [F.a2m_kept(5, m) for m in (None, 1, 7, 8, 14, 15, 35, 36)] == [5, 0, 0, 1, 1, 2, 4, 5]
+
+
+def test_audio_draws_and_their_boundary_share(cases):
+    seen, worst = set(), 0.0
+    for c in cases["audio"]:
+        p = c["params"]
+        assert 1 <= p["S"] <= 4 and p["rate"] in F.AUDIO_RATES and p["block_frames"] in F.AUDIO_BLOCKS
+        seen.add("identity" if p["rate"] == audio_model.BITRATE else "resampled")
+        for s, (nf, ch, kind, seed, _) in enumerate(p["streams"]):
+            assert 1 <= nf <= 40000 and ch in (1, 2) and kind in audio_model.SIGNAL_KINDS
+            norm, own = c["norms"][s]
+            assert np.isfinite(norm) and norm != 0 and np.isfinite(own) and own != 0                  # iiv_audio_ticks refuses those
+            pcm = audio_model.signal(kind, nf, ch, seed)
+            assert np.array_equal(pcm, c["pcms"][s])
+            want, v = audio_model.ticks(pcm.reshape(-1), ch, p["rate"], norm, block_frames=p["block_frames"])
+            assert np.array_equal(want, c["wants"][s][0]) and len(want) == audio_model.tick_count(nf, p["rate"], block_frames=p["block_frames"])
+            share = float((np.abs(v - np.round(v)) < 1e-3).sum()) / len(v)
+            assert share < 0.0025, (p, s, share)        # half of what check_ticks allows: the model alone, before any device error
+            worst = max(worst, share)
+            seen.add("few frames" if nf < 100 else "many frames")
+            seen.add(ch)
+            if nf > p["block_frames"]:
+                seen.add("several blocks")
+    assert seen >= {"identity", "resampled", "few frames", "many frames", 1, 2, "several blocks"}, seen
+    assert worst <= 0.002457, worst                     # the figure tests/stage_fuzz.py's docstring states
+
+
+def test_chain_draws(cases):
+    for c in cases["chain"]:
+        p = c["params"]
+        assert p["n"] in (2, 3) and c["frames"].shape == (p["n"], p["h"], p["w"], 3) and 1 <= p["h"] <= 400 and 1 <= p["w"] <= 400
+        assert p["palette"] in ingest_model.NAMES
+        if c["weights"] is not None:
+            diffusion_model.check_arguments(c["weights"], c["divisor"])
