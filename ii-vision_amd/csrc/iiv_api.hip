@@ -1,5 +1,5 @@
 // iiv_api.hip -- extern "C" entry points of libiivision.so that are not tied to
-// the encoder object (those live in iiv_encode.hip), plus error plumbing.
+// the encoder object (those live in iiv_encoder.hip and iiv_encode.hip), plus error plumbing.
 #include "iiv_host.h"
 
 #include <stdarg.h>

@@ -1068,28 +1068,24 @@ template <int MODE, bool FOUR> static int launch_shared(const GreedyArgs &a, hip
     return IIV_OK;
 }
 
-int launch_greedy_wave(int mode, const GreedyArgs &a, hipStream_t st, int *form_out)
+// the plain form: one 64-lane workgroup per stream, no stream counter
+template <int MODE, bool FOUR> static int launch_plain(const GreedyArgs &a, hipStream_t st)
 {
-    // (the shared form needs every stream of the round on one bank -- always so in HGR -- and the host's stream counter)
-    const bool shared = a.shared && a.uniform_bank >= 0 && a.queue && a.lds_pad == 0;
-    if (form_out) *form_out = shared ? 1 : 0;
-    int rc = IIV_OK;
-    if (shared && a.fourth)
-        rc = mode == kDHGR ? launch_shared<kDHGR, true>(a, st) : launch_shared<kHGR, true>(a, st);
-    else if (a.fourth && mode == kDHGR)   // (f4: a real fourth offset per opcode -- the plain one-wave form only)
-        hipLaunchKernelGGL((greedy_wave_kernel<kDHGR, 1, true>), dim3(a.n_streams), dim3(64), (size_t)a.lds_pad, st, a.states, a.frames_main,
-                           a.frames_aux, a.n_frames, a.segs, a.seg_stride, a.nt, a.ops_out, a.ops_stride, a.n_streams, a.uniform_bank, (int *)nullptr, a.count_stats ? 1 : 0, a.perm, a.cost);
-    else if (a.fourth)
-        hipLaunchKernelGGL((greedy_wave_kernel<kHGR, 1, true>), dim3(a.n_streams), dim3(64), (size_t)a.lds_pad, st, a.states, a.frames_main,
-                           a.frames_aux, a.n_frames, a.segs, a.seg_stride, a.nt, a.ops_out, a.ops_stride, a.n_streams, a.uniform_bank, (int *)nullptr, a.count_stats ? 1 : 0, a.perm, a.cost);
-    else if (shared)
-        rc = mode == kDHGR ? launch_shared<kDHGR, false>(a, st) : launch_shared<kHGR, false>(a, st);
-    else if (mode == kDHGR)
-        hipLaunchKernelGGL((greedy_wave_kernel<kDHGR, 1>), dim3(a.n_streams), dim3(64), (size_t)a.lds_pad, st, a.states, a.frames_main,
-                           a.frames_aux, a.n_frames, a.segs, a.seg_stride, a.nt, a.ops_out, a.ops_stride, a.n_streams, a.uniform_bank, (int *)nullptr, a.count_stats ? 1 : 0, a.perm, a.cost);
+    hipLaunchKernelGGL((greedy_wave_kernel<MODE, 1, FOUR>), dim3(a.n_streams), dim3(64), (size_t)a.lds_pad, st, a.states, a.frames_main,
+                       a.frames_aux, a.n_frames, a.segs, a.seg_stride, a.nt, a.ops_out, a.ops_stride, a.n_streams, a.uniform_bank, (int *)nullptr, a.count_stats ? 1 : 0, a.perm, a.cost);
+    return IIV_OK;
+}
+
+// (which form: the caller's choice, iiv_launch_choice.h; f4's fourth offset exists in both)
+int launch_greedy_wave(int mode, const GreedyArgs &a, hipStream_t st)
+{
+    int rc;
+    if (mode == kDHGR)
+        rc = a.shared ? (a.fourth ? launch_shared<kDHGR, true>(a, st) : launch_shared<kDHGR, false>(a, st))
+                      : (a.fourth ? launch_plain<kDHGR, true>(a, st) : launch_plain<kDHGR, false>(a, st));
     else
-        hipLaunchKernelGGL((greedy_wave_kernel<kHGR, 1>), dim3(a.n_streams), dim3(64), (size_t)a.lds_pad, st, a.states, a.frames_main,
-                           a.frames_aux, a.n_frames, a.segs, a.seg_stride, a.nt, a.ops_out, a.ops_stride, a.n_streams, a.uniform_bank, (int *)nullptr, a.count_stats ? 1 : 0, a.perm, a.cost);
+        rc = a.shared ? (a.fourth ? launch_shared<kHGR, true>(a, st) : launch_shared<kHGR, false>(a, st))
+                      : (a.fourth ? launch_plain<kHGR, true>(a, st) : launch_plain<kHGR, false>(a, st));
     if (rc) return rc;
     return hip_check(hipGetLastError(), "greedy_wave_kernel launch");
 }

@@ -81,7 +81,7 @@ struct StreamState {
     int32_t pad_content;      // target[0,0] of the live generator's bank (video.py:249)
     int32_t truncated;        // order[] holds only the top of the list (prefix sort)
     unsigned long long draws_py, draws_np, ops, pad_ops;
-    // what the one-wave kernel saw of the input (iiv_encode.hip: kTieHeavyPercent), totals since creation: steps the nonces
+    // what the one-wave kernel saw of the input (iiv_launch_choice.h: tie_heavy_input), totals since creation: steps the nonces
     // decided, real (not padding) opcodes, launches that emitted something
     unsigned long long stat_exact, stat_ops, stat_runs;
     unsigned long long stamps[32];  // diagnostic builds only (-DIIV_STAMPS): prologue s_memtime stamps [0,16), greedy phase cycles [16,24)
@@ -89,7 +89,7 @@ struct StreamState {
     // >= 65535: priorities grow by a diff weight per call while a byte waits).  The prologue adds a diff weight to EVERY
     // priority in EVERY call (video.py:115-116): as int32 that is 64 of the ~142 KB a call moves through HBM, and the call is
     // within 15 % of what this box's HBM copies.  up[] is exact wherever up16 says kUpBig and is brought up to
-    // date everywhere before the host looks (iiv_encode.hip: materialise_up_kernel / compact_up_kernel).
+    // date everywhere before the host looks (iiv_encoder.hip: materialise_up_kernel / compact_up_kernel).
     uint16_t up16[2][8192];
 };
 constexpr uint32_t kUpBig = 0xffffu;
@@ -446,9 +446,9 @@ struct GreedyArgs {
     size_t ops_stride;       // bytes between the outputs of consecutive streams
     int lds_pad;             // extra dynamic LDS per stream (bytes): caps the streams resident per CU
     int uniform_bank;        // 0 / 1: every stream that emits opcodes in this round works on this bank; -1: they differ
-    bool shared;             // IIV_GREEDY_WAVE_SHARED: the LDS-shared form wherever it applies (DHGR, one bank per round)
+    bool shared;             // run the LDS-shared form; the caller guarantees uniform_bank >= 0, queue != NULL and lds_pad == 0 (iiv_launch_choice.h)
     int *queue;              // device: this launch's stream counter, zero (the LDS-shared form's persistent workgroups)
-    bool fourth;             // IIV_OPT_FOURTH_OFFSET: up to three extra offsets per opcode (the plain one-wave kernel only)
+    bool fourth;             // IIV_OPT_FOURTH_OFFSET: up to three extra offsets per opcode (both one-wave forms and the team kernel)
     bool count_stats;        // the one-wave kernel adds to the streams' stat_* fields
     // Longest first (round 5): streams differ by up to 2x in how long a launch takes them (picture-like input), and a launch
     // ends when its slowest stream does -- in its last fifth a third (S-iid) to three quarters (S-img) of the wave slots idle.
@@ -463,7 +463,7 @@ struct GreedyArgs {
     uint32_t live_tag = 0;
 };
 
-int launch_greedy_wave(int mode, const GreedyArgs &a, hipStream_t st, int *form_out = nullptr);   // iiv_greedy.hip; *form_out: 0 plain form launched, 1 LDS-shared
+int launch_greedy_wave(int mode, const GreedyArgs &a, hipStream_t st);   // iiv_greedy.hip: the plain or (a.shared) the LDS-shared form
 int launch_greedy_team(int mode, const GreedyArgs &a, hipStream_t st);   // iiv_team.hip
 
 

@@ -52,7 +52,7 @@ def frames(mode, n_streams, nframes, seed):
 class Enc:
     """An encoder of n seeded streams with its oracle twins, and the probe's pieces around it."""
 
-    def __init__(self, native, O, device_tables, oracle_tables, mode, n, seed0, kernel=None, joint=False, fourth=False):
+    def __init__(self, native, O, device_tables, oracle_tables, mode, n, seed0, kernel=None, joint=False, fourth=False, lds_pad=0):
         t, s = device_tables.get(mode, 5)
         self.native, self.O, self.mode, self.n = native, O, mode, n
         self.enc = native.Encoder(mode, t, s, n, dm=device_tables.dm[(mode, 5)])
@@ -62,6 +62,8 @@ class Enc:
             self.enc.set_content_choice(True)
         if fourth:
             self.enc.set_fourth_offset(True)
+        if lds_pad:
+            self.enc.set_greedy_lds_pad(lds_pad)
         self.seeds = [(seed0 + i, seed0 + 100 + i) for i in range(n)]
         py, npw = seed_words(O, self.seeds)
         self.enc.set_state_all(native.STATE_RNG_PY, py)

@@ -189,7 +189,10 @@ def _segment_arrays(native, segments, scribble):
 # every greedy launch line: name -> (encoder options, the kernel iiv_encoder_launch_forms must report, and no other)
 FORMS = {"plain": (dict(kernel="plain"), "plain"), "shared": (dict(kernel="shared"), "shared"), "team": (dict(kernel="team"), "team"),
          "workgroup-joint": (dict(joint=True), "workgroup"), "fourth-team": (dict(kernel="team", fourth=True), "team"),
-         "fourth-plain": (dict(kernel="plain", fourth=True), "plain"), "fourth-shared": (dict(kernel="shared", fourth=True), "shared")}
+         "fourth-plain": (dict(kernel="plain", fourth=True), "plain"), "fourth-shared": (dict(kernel="shared", fourth=True), "shared"),
+         # (csrc/iiv_launch_choice.h: the fourth offset overrides the kernel option; the LDS-shared form takes all of a CU's LDS)
+         "workgroup": (dict(kernel="workgroup"), "workgroup"), "fourth-workgroup": (dict(kernel="workgroup", fourth=True), "plain"),
+         "shared-lds-pad": (dict(kernel="shared", lds_pad=1024), "plain")}
 
 
 @pytest.mark.parametrize("form", list(FORMS))
@@ -223,18 +226,16 @@ def test_encode(native, O, device_tables, oracle_tables, mode, form):
     e.close()
 
 
-@pytest.mark.parametrize("mode", MODES)
-def test_encode_streams(native, O, device_tables, oracle_tables, mode):
+def _encode_streams(native, O, device_tables, oracle_tables, mode, scheds, seed0, options={}, kernel=None):
+    """iiv_encode_streams of four streams' schedules on the side stream; kernel: the one every greedy launch must have run"""
     L = native.lib()
     n = 4
-    b = 1 if mode == DHGR else 0
-    scheds = [[(0, 0, 1, 120), (1, b, 1, 90)], [], [(1, 0, 1, 70), (1, 0, 0, 30), (0, b, 1, 200)], [(0, b, 1, 33)]]
     flat = [g for s in scheds for g in s]
     begin_real = np.concatenate([[0], np.cumsum([len(s) for s in scheds])]).astype(np.int32)
     width = max(sum(g[3] for g in s) for s in scheds)
     fm, fa = _frames(mode, n, 2, 500 + mode)
     dm_, da_ = _frames(mode, n, 2, 600 + mode)
-    e = _Enc(native, O, device_tables, oracle_tables, mode, n, 31)
+    e = _Enc(native, O, device_tables, oracle_tables, mode, n, seed0, **options)
     p = Probe()
     d_main, d_aux = p.input(fm, dm_), p.input(fa, da_)
     ops = p.output((n, width, 6))
@@ -246,8 +247,11 @@ def test_encode_streams(native, O, device_tables, oracle_tables, mode):
         _ok(native, L.iiv_encode_streams(e.enc._h, _dp(d_main), _dp(d_aux if mode == DHGR else None), 2, segs,
                                         begin.ctypes.data_as(C.POINTER(C.c_int32)), _dp(ops), width * 6, st))
     e.warm(call)
+    e.enc.profile(kernel is not None)
     p.run(call)
     e.enc.check()
+    ran = e.enc.launch_forms()
+    assert kernel is None or (ran[kernel] > 0 and sum(ran.values()) == ran[kernel]), ran
     got = _np(ops)
     for i in range(n):
         exp = e.oracle(i, fm, fa, scheds[i])
@@ -255,6 +259,21 @@ def test_encode_streams(native, O, device_tables, oracle_tables, mode):
         assert (got[i, len(exp):] == 0x5B).all(), "stream %d wrote behind its own opcodes" % i
     e.check_state()
     e.close()
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_encode_streams(native, O, device_tables, oracle_tables, mode):
+    b = 1 if mode == DHGR else 0
+    _encode_streams(native, O, device_tables, oracle_tables, mode,
+                    [[(0, 0, 1, 120), (1, b, 1, 90)], [], [(1, 0, 1, 70), (1, 0, 0, 30), (0, b, 1, 200)], [(0, b, 1, 33)]], 31)
+
+
+def test_encode_streams_whose_rounds_mix_banks_run_the_plain_form(native, O, device_tables, oracle_tables):
+    """DHGR under kernel="shared": in both rounds some streams work on the main bank and some on aux, and the LDS-shared form
+    holds one bank's table per workgroup -- every launch is the plain form's (csrc/iiv_launch_choice.h), the bytes the oracle's"""
+    _encode_streams(native, O, device_tables, oracle_tables, DHGR,
+                    [[(0, 0, 1, 120), (1, 1, 1, 90)], [(0, 1, 1, 100), (1, 0, 1, 60)], [(1, 0, 1, 70)], [(0, 1, 1, 33)]], 35,
+                    dict(kernel="shared"), "plain")
 
 
 @pytest.mark.parametrize("mode", MODES)
