@@ -370,13 +370,20 @@ def pack(mode, main_mem, aux_mem=None):
 
 
 def diff_weights(mode, table, src_packed, tgt_packed, is_aux):
+    """src/tgt: uint64 arrays (..., 32, 128) on host, screen k against screen k -> int32 (..., 32, 256) on host."""
     torch = _torch()
-    src = torch.from_numpy(np.ascontiguousarray(src_packed, dtype=np.uint64).view(np.int64).reshape(1, 32, 128)).cuda()
-    tgt = torch.from_numpy(np.ascontiguousarray(tgt_packed, dtype=np.uint64).view(np.int64).reshape(1, 32, 128)).cuda()
-    out = torch.empty((32, 256), dtype=torch.int32, device="cuda")
-    check(lib().iiv_diff_weights(mode, dptr(table), 1, dptr(src), dptr(tgt), int(bool(is_aux)), dptr(out),
+    src_packed = np.ascontiguousarray(src_packed, dtype=np.uint64)
+    tgt_packed = np.ascontiguousarray(tgt_packed, dtype=np.uint64)
+    if src_packed.shape != tgt_packed.shape or src_packed.shape[-2:] != (32, 128):
+        raise ValueError("packed source %s and target %s must both be (..., 32, 128)" % (src_packed.shape, tgt_packed.shape))
+    lead = src_packed.shape[:-2]
+    n = int(np.prod(lead)) if lead else 1
+    src = torch.from_numpy(src_packed.view(np.int64).reshape(n, 32, 128)).cuda()
+    tgt = torch.from_numpy(tgt_packed.view(np.int64).reshape(n, 32, 128)).cuda()
+    out = torch.empty((n, 32, 256), dtype=torch.int32, device="cuda")
+    check(lib().iiv_diff_weights(mode, dptr(table), n, dptr(src), dptr(tgt), int(bool(is_aux)), dptr(out),
                                  stream_ptr()))
-    return out.cpu().numpy()
+    return out.cpu().numpy().reshape(lead + (32, 256))
 
 
 def compute_delta_pages(mode, table, tgt_packed, pages, contents, dw_rows, is_aux):

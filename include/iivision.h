@@ -100,18 +100,25 @@ int iiv_store_table_from_table(int mode, const uint16_t *d_table, uint16_t *d_st
 /* Memory maps are (32,256) u8 page/offset arrays (screen.MemoryMap,
  * screen.py:101-125); d_aux is ignored (may be NULL) for HGR. */
 
-/* Bitmap._pack (screen.py:207-226): d_packed [n][32][128] u64 */
+/* Bitmap._pack (screen.py:207-226): d_packed [n][32][128] u64.  d_main / d_aux [n][32][256] u8
+ * are read byte by byte and need no alignment; DHGR ignores bit 7 of every byte.  n == 0
+ * succeeds and writes nothing. */
 int iiv_pack(int mode, int n, const uint8_t *d_main, const uint8_t *d_aux, uint64_t *d_packed,
              void *stream);
 
-/* Bitmap.diff_weights (screen.py:400-449) from packed source/target:
- * d_out [n][32][256] i32. */
+/* Bitmap.diff_weights (screen.py:400-449) from packed source/target, [n][32][128] u64
+ * each, screen k of the one against screen k of the other: d_out [n][32][256] i32. */
 int iiv_diff_weights(int mode, const uint16_t *d_table, int n, const uint64_t *d_src_packed,
                      const uint64_t *d_tgt_packed, int is_aux, int32_t *d_out, void *stream);
 
 /* Bitmap.compute_delta_page (screen.py:525-547) for n (page, content) queries
  * against ONE target bitmap: d_pages[n], d_contents[n] i32, d_dw_rows [n][256]
- * i32 (the diff_weights row of each query's page), d_out [n][256] i32. */
+ * i32 (the diff_weights row of each query's page), d_out [n][256] i32.
+ * Precondition: every d_pages[q] is in 0..31.  The array lives on the device, so the
+ * host cannot check it; any other value reads outside d_tgt_packed.
+ * d_contents[q]: the byte is its low 8 bits (content & 0xff); bits 8..31 are ignored.
+ * d_dw_rows is only subtracted (out = new weight - d_dw_rows), never interpreted: any
+ * i32 rows may be passed, and queries may repeat a page or come in any order. */
 int iiv_compute_delta_pages(int mode, const uint16_t *d_table, int n, const uint64_t *d_tgt_packed,
                             const int32_t *d_pages, const int32_t *d_contents,
                             const int32_t *d_dw_rows, int is_aux, int32_t *d_out, void *stream);

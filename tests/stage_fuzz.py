@@ -1,6 +1,6 @@
 """Seeded differential fuzz of the kernels around the encoder against their numpy models: the generator that draws cases for
-resize_model, ingest_model / diffusion_model, mono_model, render_model / render_error_model, a2m_model and audio_model
-(tests/fuzz_parity.py does the same for the encoder against the oracle).
+resize_model, ingest_model / diffusion_model, mono_model, render_model / render_error_model, a2m_model, audio_model and
+bitmap_model (tests/fuzz_parity.py does the same for the encoder against the oracle).
 
     python tests/stage_fuzz.py [rounds] [seed] [--stage NAME] [--round K]     (on an MI355X; 200 rounds is the long run)
 
@@ -34,6 +34,10 @@ What a stage draws (sizes are the smallest at which each kernel can still go wro
     audio    S 1..4 streams (n_frames at the small-transform edges or 1..40000, 1 or 2 channels, a signal of
              audio_model.signal), one rate and one block size per call: ticks by audio_model.check_ticks, the resample within
              1e-5 max|y|, the normalisation within 1e-5 relative
+    bitmap   mode and bank, n 1..6 all-bit screens as source and as target (bit 7 set in DHGR too), the memory maps 0..3 bytes
+             into sentinel-filled buffers, pack / diff_weights / compute_delta_pages into guarded slices through the C ABI;
+             1..64 (page, content) queries with duplicates (pages 0 and 31 by turns), contents with junk above bit 7, random
+             rows to subtract in [-70000, 70000]; the table is the NTSC one, on the host from the oracle
     chain    2..3 frames of a random source size through resize -> ingest -> render_rgb -> render_error (against the resized
              frames), each stage handed the very tensor the one before returned; every arrow against the models' composition
 
@@ -57,6 +61,7 @@ for _p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "ii-vision_amd
 
 import a2m_model  # noqa: E402
 import audio_model  # noqa: E402
+import bitmap_model  # noqa: E402
 import diffusion_model  # noqa: E402
 import ingest_model  # noqa: E402
 import mono_model  # noqa: E402
@@ -65,10 +70,10 @@ import render_model  # noqa: E402
 import resize_model  # noqa: E402
 
 SEED = 2027
-STAGES = ("resize", "ingest", "mono", "render", "a2m", "audio", "chain")
+STAGES = ("resize", "ingest", "mono", "render", "a2m", "audio", "chain", "bitmap")
 STAGE_ID = {name: i for i, name in enumerate(STAGES)}
 # rounds of tests/test_gpu_stage_fuzz.py (the chain, four stages a round, runs 4)
-ROUNDS = {"resize": 12, "ingest": 12, "mono": 12, "render": 12, "a2m": 12, "audio": 12, "chain": 4}
+ROUNDS = {"resize": 12, "ingest": 12, "mono": 12, "render": 12, "a2m": 12, "audio": 12, "chain": 4, "bitmap": 12}
 
 HGR, DHGR = 0, 1
 DIFFUSION = 256
@@ -672,12 +677,102 @@ def check_chain(native, case):
           render_error_model.error_sums_of_screens(m_rgb, m_small))
 
 
+# ---- the stand-alone Bitmap kernels ----------------------------------------------------------------------------------------
+
+BITMAP_ROW_RANGE = 70000
+_ntsc_tables = {}
+
+
+def ntsc_table(mode):
+    """the NTSC edit-distance table on the host, from the oracle (tests/test_gpu_tables.py holds the device's to it entry by
+    entry); the device's own copy is built from the same matrix"""
+    if mode not in _ntsc_tables:
+        import oracle
+        oracle.build()
+        _ntsc_tables[mode] = oracle.build_table(mode, oracle.cie2000_matrix(oracle.PALETTE_RGB[5])[1], symmetric=True)
+    return _ntsc_tables[mode]
+
+
+def draw_bitmap(rng, round_index=0):
+    mode = (round_index + int(rng.integers(0, 2)) * (round_index >= 4)) % 2            # rounds 0..3: HGR, DHGR, HGR, DHGR
+    is_aux = 0 if mode == HGR else (round_index // 2 + (int(rng.integers(0, 2)) if round_index >= 4 else 0)) % 2
+    n = 1 if round_index % 4 == 0 else int(rng.integers(2, 7)) if round_index % 4 == 1 else int(rng.integers(1, 7))
+    screens = rng.integers(0, 256, (2, 2, n, 32, 256), dtype=np.uint8)                  # [source | target][main | aux]
+    k = int(rng.integers(1, 65))
+    pages = rng.integers(0, 32, k).astype(np.int32)
+    pages[int(rng.integers(0, k))] = (0, 31)[round_index % 2]
+    contents = rng.integers(0, 256, k).astype(np.int32)
+    if k > 1:                                                                           # a duplicate query, elsewhere in the list
+        a, b = rng.permutation(k)[:2]
+        pages[a], contents[a] = pages[b], contents[b]
+    junk = rng.integers(0, 1 << 23, k).astype(np.int32) << 8                            # bits 8..30 of a content: ignored
+    rows = rng.integers(-BITMAP_ROW_RANGE, BITMAP_ROW_RANGE + 1, (k, 256)).astype(np.int32)
+    params = dict(mode=mode, is_aux=is_aux, n=n, queries=k, which=int(rng.integers(0, n)), lead_main=int(rng.integers(0, 4)),
+                  lead_aux=int(rng.integers(0, 4)), lead_out=1 + int(rng.integers(0, 8)))
+    return dict(stage="bitmap", params=params, screens=screens, pages=pages, contents=contents, junk=junk, rows=rows)
+
+
+def _words(n, dtype, lead, trail=5):
+    import torch
+    fill = GUARD64 if dtype == torch.int64 else GUARD64 & 0xffffffff
+    buf = torch.full((lead + n + trail,), fill, dtype=dtype, device="cuda")
+    return buf, buf[lead:lead + n], fill
+
+
+def _words_kept(case, what, buf, lead, n, fill):
+    b = buf.cpu().numpy()
+    _require((b[:lead] == fill).all() and (b[lead + n:] == fill).all(), case, "%s: words outside the slice were written" % what)
+
+
+def check_bitmap(native, case):
+    import torch
+    p = case["params"]
+    mode, ia, n, k = p["mode"], p["is_aux"], p["n"], p["queries"]
+    L, dp, M = native.lib(), native.dptr, bitmap_model
+    otab = ntsc_table(mode)
+    import oracle
+    table = native.build_table(mode, oracle.cie2000_matrix(oracle.PALETTE_RGB[5])[1], True)      # (milliseconds; on this round's stream)
+    want_packed = []
+    dev_packed = []
+    for side in (0, 1):                                            # source, target
+        main, aux = case["screens"][side]
+        mbuf, mview = _guarded(n * 8192, p["lead_main"], 3)
+        abuf, aview = _guarded(n * 8192, p["lead_aux"], 3)
+        mview.copy_(torch.from_numpy(main).reshape(-1))
+        aview.copy_(torch.from_numpy(aux).reshape(-1))
+        obuf, oview, fill = _words(n * 4096, torch.int64, p["lead_out"])
+        native.check(L.iiv_pack(mode, n, dp(mview), dp(aview) if mode == DHGR or side else dp(None), dp(oview), native.stream_ptr()))
+        _sync()
+        want = M.pack(mode, main, aux)
+        _same(case, "pack (%s)" % ("source", "target")[side], oview.cpu().numpy().view(np.uint64).reshape(n, 32, 128), want)
+        _words_kept(case, "pack", obuf, p["lead_out"], n * 4096, fill)
+        _guards_kept(case, "pack: the main bank", mbuf, p["lead_main"], n * 8192)
+        _same(case, "the main bank after pack", mview.cpu().numpy(), main.reshape(-1))
+        want_packed.append(want)
+        dev_packed.append(oview)                                   # the device's own output goes on to the next kernel
+    wbuf, wview, fill = _words(n * 8192, torch.int32, p["lead_out"])
+    native.check(L.iiv_diff_weights(mode, dp(table), n, dp(dev_packed[0]), dp(dev_packed[1]), ia, dp(wview), native.stream_ptr()))
+    _sync()
+    want_dw = M.diff_weights(mode, otab, want_packed[0], want_packed[1], ia)
+    _same(case, "diff_weights", wview.cpu().numpy().reshape(n, 32, 256), want_dw)
+    _words_kept(case, "diff_weights", wbuf, p["lead_out"], n * 8192, fill)
+    tgt = dev_packed[1][p["which"] * 4096:(p["which"] + 1) * 4096]   # one screen of the batch is the queries' bitmap
+    pages, contents, rows = (torch.from_numpy(a).cuda() for a in (case["pages"], case["contents"] | case["junk"], case["rows"]))
+    dbuf, dview, fill = _words(k * 256, torch.int32, p["lead_out"])
+    native.check(L.iiv_compute_delta_pages(mode, dp(table), k, dp(tgt), dp(pages), dp(contents), dp(rows), ia, dp(dview), native.stream_ptr()))
+    _sync()
+    want_d = M.compute_delta_pages(mode, otab, want_packed[1][p["which"]], case["pages"], case["contents"], case["rows"], ia)
+    _same(case, "compute_delta_pages", dview.cpu().numpy().reshape(k, 256), want_d)
+    _words_kept(case, "compute_delta_pages", dbuf, p["lead_out"], k * 256, fill)
+    _same(case, "the rows after the call", rows.cpu().numpy(), case["rows"])
+
+
 # ---- the loop ---------------------------------------------------------------------------------------------------------
 
 DRAW = {"resize": draw_resize, "ingest": draw_ingest, "mono": draw_mono, "render": draw_render, "a2m": draw_a2m, "audio": draw_audio,
-        "chain": draw_chain}
+        "chain": draw_chain, "bitmap": draw_bitmap}
 CHECK = {"resize": check_resize, "ingest": check_ingest, "mono": check_mono, "render": check_render, "a2m": check_a2m,
-         "audio": check_audio, "chain": check_chain}
+         "audio": check_audio, "chain": check_chain, "bitmap": check_bitmap}
 
 
 def _fuzz(stage, native, rng, round_index, seed=None):
@@ -715,8 +810,12 @@ def fuzz_chain(native, rng, round_index, seed=None):
     return _fuzz("chain", native, rng, round_index, seed)
 
 
+def fuzz_bitmap(native, rng, round_index, seed=None):
+    return _fuzz("bitmap", native, rng, round_index, seed)
+
+
 FUZZ = {"resize": fuzz_resize, "ingest": fuzz_ingest, "mono": fuzz_mono, "render": fuzz_render, "a2m": fuzz_a2m, "audio": fuzz_audio,
-        "chain": fuzz_chain}
+        "chain": fuzz_chain, "bitmap": fuzz_bitmap}
 
 
 def run(rounds, seed=SEED, stages=None, side_stream=False, first_round=0, log=None):

@@ -7,6 +7,7 @@ import pytest
 
 import a2m_model
 import audio_model
+import bitmap_model
 import diffusion_model
 import ingest_model
 import resize_model
@@ -23,7 +24,7 @@ def cases():
 
 
 def test_round_counts():
-    assert F.ROUNDS == {"resize": 12, "ingest": 12, "mono": 12, "render": 12, "a2m": 12, "audio": 12, "chain": 4}
+    assert F.ROUNDS == {"resize": 12, "ingest": 12, "mono": 12, "render": 12, "a2m": 12, "audio": 12, "chain": 4, "bitmap": 12}
 
 
 def test_a_case_is_a_function_of_seed_round_and_stage(cases):
@@ -217,3 +218,40 @@ def test_chain_draws(cases):
         assert p["palette"] in ingest_model.NAMES
         if c["weights"] is not None:
             diffusion_model.check_arguments(c["weights"], c["divisor"])
+
+
+def test_bitmap_draws(cases):
+    seen = set()
+    for c in cases["bitmap"]:
+        p = c["params"]
+        mode, n, k = p["mode"], p["n"], p["queries"]
+        assert mode in (0, 1) and p["is_aux"] in ((0, 1) if mode == 1 else (0,)) and 1 <= n <= 6 and 1 <= k <= 64      # HGR has no aux bank
+        assert c["screens"].shape == (2, 2, n, 32, 256) and c["screens"].dtype == np.uint8
+        assert 0 <= p["which"] < n and 0 <= p["lead_main"] <= 3 and 0 <= p["lead_aux"] <= 3 and p["lead_out"] >= 1
+        # include/iivision.h: pages in 0..31 (the host cannot check them); a content's byte is its low 8 bits
+        assert c["pages"].shape == c["contents"].shape == c["junk"].shape == (k,) and c["pages"].dtype == np.int32
+        assert ((c["pages"] >= 0) & (c["pages"] <= 31)).all() and ((c["contents"] >= 0) & (c["contents"] <= 255)).all()
+        assert not (c["junk"] & 0xff).any() and (c["junk"] >= 0).all() and ((c["contents"] | c["junk"]) & 0xff == c["contents"]).all()
+        assert c["rows"].shape == (k, 256) and c["rows"].dtype == np.int32 and np.abs(c["rows"]).max() <= F.BITMAP_ROW_RANGE
+        seen |= {("mode", mode), ("bank", mode, p["is_aux"]), "n = 1" if n == 1 else "n > 1"}
+        if len(set(zip(c["pages"].tolist(), c["contents"].tolist()))) < k:
+            seen.add("a duplicate query")
+        if (np.diff(c["pages"]) < 0).any():
+            seen.add("unsorted pages")
+        seen |= {("page", int(v)) for v in c["pages"] if v in (0, 31)}
+        for bank in c["screens"].reshape(-1, n, 32, 256):
+            assert (bank >= 128).mean() > 0.25 and len({s.tobytes() for s in bank}) == n       # bit 7, every screen different
+        if (c["screens"] >= 128).any():
+            seen.add(("bit 7", mode))
+        if c["junk"].any():
+            seen.add("junk above bit 7")
+        if p["lead_main"] % 2 or p["lead_aux"] % 2:
+            seen.add("an odd first byte")
+        if (c["rows"] < 0).any() and (c["rows"] > 65535).any():
+            seen.add("rows no table holds")
+    assert seen >= {("mode", 0), ("mode", 1), ("bank", 1, 0), ("bank", 1, 1), "n = 1", "n > 1", "a duplicate query", "unsorted pages",
+                    ("page", 0), ("page", 31), ("bit 7", 0), ("bit 7", 1), "junk above bit 7", "an odd first byte", "rows no table holds"}, seen
+    # the first four rounds alone hold both modes, both DHGR banks, n = 1 and n > 1
+    first = [c["params"] for c in cases["bitmap"][:4]]
+    assert [(q["mode"], q["is_aux"]) for q in first] == [(0, 0), (1, 0), (0, 0), (1, 1)] and first[0]["n"] == 1 and first[1]["n"] > 1
+    assert bitmap_model.HGR == F.HGR and bitmap_model.DHGR == F.DHGR
