@@ -22,6 +22,8 @@ Recipe:
 Usage: python tests/golden/make_golden.py [--scratch /tmp/iiv_ref]
        python tests/golden/make_golden.py --asserts-only     (g10_asserts.npz alone: the reference on the clips of
        tests/assert_inputs.py -- targets with bytes in the screen holes and with bit 7 set -- up to its AssertionError)
+       python tests/golden/make_golden.py --corpus-only [--jobs N]   (g11_*.npz alone: the reference on the cases of
+       tests/reference_corpus.py -- picture-like and converging content; see make_corpus_golden)
 """
 
 import argparse
@@ -358,7 +360,7 @@ def main():
     make_fourth_offset_golden(args.scratch)
 
 
-if __name__ == "__main__" and not {"--a2m-only", "--movie-only", "--fourth-only", "--asserts-only"} & set(sys.argv):
+if __name__ == "__main__" and not {"--a2m-only", "--movie-only", "--fourth-only", "--asserts-only", "--corpus-only"} & set(sys.argv):
     main()
 
 
@@ -646,3 +648,118 @@ if __name__ == "__main__" and "--asserts-only" in sys.argv:
     import oracle as _O
     write_reference_tables("/tmp/iiv_ref", _O)
     make_asserts_golden("/tmp/iiv_ref")
+
+
+def _record_corpus_case(job):
+    """one case on the reference (in a worker process of make_corpus_golden, or in the parent for the first case)"""
+    tag, mode_name, pal, frames, sched, seed_py, seed_np, fourth = job
+    import inspect
+    import textwrap
+    import video
+    t = time.time()
+    original = video.Video._index_changes
+    if fourth:      # as make_fourth_offset_golden: the exit test of the extra-offset loop reads 4, built at recording time
+        src = textwrap.dedent(inspect.getsource(original))
+        old = "if len(offsets) == 3:"
+        assert src.count(old) == 1, "the reference's exit test moved"
+        ns = dict(vars(video))
+        exec(compile(src.replace(old, "if len(offsets) == 4:"), "<_index_changes, exit test at 4>", "exec"), ns)
+        video.Video._index_changes = ns["_index_changes"]
+    try:
+        st = run_reference(mode_name, pal, frames, sched, seed_py, seed_np)
+    finally:
+        video.Video._index_changes = original
+    return tag, st, time.time() - t
+
+
+def make_corpus_golden(scratch, jobs=None):
+    """g11: the reference on the cases of tests/reference_corpus.py -- picture-like content (img, dither, flat), where the
+    nonces decide most steps, and converging content (static), run through the bag to out-of-work and padding; four cases a
+    second time with the exit test of the extra-offset loop reading 4 (as make_fourth_offset_golden).  Per case: frames,
+    schedule, meta (mode, palette, seed_py, seed_np, fourth, exhaust) and everything run_reference returns.  Written to
+    g11_reference_corpus.npz, or, where that is larger than g3_encode_runs.npz (the largest fixture), split by mode into
+    g11_hgr.npz and g11_dhgr.npz.  The other fixtures are not touched.
+
+    The frames and the schedules (the oracle sizes the runs to padding) are made before the reference is imported: its
+    modules go by the same names as the project's.  The first case is recorded alone, to measure the reference's rate; the
+    others in `jobs` worker processes, one case each at a time.
+
+    Measured where this fixture was recorded (8 CPUs): the first case alone, HGR_img_movie, 1469 opcodes in 52.3 s = 28
+    opcodes/s -- nearly all of it the reference loading its 1 GiB HGR table file, which every process pays once per (mode,
+    palette): 13 s for a DHGR table, 39 s for an HGR one.  With the table in memory the reference makes 2600 - 3800 opcodes/s
+    (HGR_static_exhaust: 5579 in 2.1 s; HGR_img_exhaust: 6119 in 1.6 s).  The whole corpus, 24 recordings and 55 589 opcodes,
+    took 123 s of wall time with 7 workers and 361 s of reference time (154 opcodes/s, table loads included), after the 10 s
+    of write_reference_tables."""
+    import multiprocessing
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import reference_corpus as RC
+    work = []
+    for c in RC.cases():
+        frames, sched = c.frames(), c.schedule()
+        work.append((c, frames, sched))
+        print("%-28s %5d opcodes in %2d generators" % (c.tag, sum(s[2] for s in sched), len(sched)), flush=True)
+    assert RC.movie_schedule("DHGR", 3) == movie_schedule("DHGR", 3) and RC.movie_schedule("HGR", 3, 400) == movie_schedule("HGR", 3, 400)
+    # from here on `screen`, `video`, `palette` ... are the reference's
+    mine = os.path.join(ROOT, "ii-vision_amd", "transcoder")
+    for name, mod in list(sys.modules.items()):
+        if getattr(mod, "__file__", None) and os.path.dirname(os.path.abspath(mod.__file__)) == mine:
+            del sys.modules[name]
+    sys.path[:] = [p for p in sys.path if os.path.abspath(p) != mine]
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import oracle as O
+    setup_reference(scratch)
+    write_reference_tables(scratch, O)
+    import video
+    assert os.path.abspath(video.__file__).startswith(REF)
+
+    todo = [(c.tag, c.mode_name, c.palette, fr, sc, c.seed_py, c.seed_np, c.fourth) for (c, fr, sc) in work]
+    t0 = time.time()
+    done = {}
+    tag, st, dt = _record_corpus_case(todo[0])
+    done[tag] = st
+    print("%s: %d opcodes in %.1f s = %.1f opcodes/s (alone)" % (tag, len(st["ops"]), dt, len(st["ops"]) / dt), flush=True)
+    spent = dt
+    jobs = jobs or max(1, min(len(todo) - 1, (os.cpu_count() or 2) - 1))
+    rest = sorted(todo[1:], key=lambda j: -sum(s[2] for s in j[4]))       # longest first
+    with multiprocessing.get_context("fork").Pool(jobs, maxtasksperchild=1) as pool:
+        for tag, st, dt in pool.imap_unordered(_record_corpus_case, rest):
+            done[tag] = st
+            spent += dt
+            print("%s: %d opcodes, sha %s (%.1f s)" % (tag, len(st["ops"]), sha(st["ops"])[:16], dt), flush=True)
+    total = sum(len(st["ops"]) for st in done.values())
+    print("%d recordings, %d opcodes, %.0f s of wall time with %d workers, %.0f s of reference time (%.1f opcodes/s)" % (
+        len(done), total, time.time() - t0, jobs, spent, total / spent), flush=True)
+
+    files = {"g11_reference_corpus": {}, "g11_hgr": {}, "g11_dhgr": {}}
+    for (c, frames, sched) in work:
+        items = dict(frames=frames, schedule=np.array(sched, dtype=np.int32), meta=c.meta(), **done[c.tag])
+        for k, val in items.items():
+            files["g11_reference_corpus"][c.tag + "/" + k] = val
+            files["g11_dhgr" if c.mode_name == "DHGR" else "g11_hgr"][c.tag + "/" + k] = val
+    for name in files:
+        path = os.path.join(HERE, name + ".npz")
+        if os.path.exists(path):
+            os.remove(path)
+    limit = os.path.getsize(os.path.join(HERE, "g3_encode_runs.npz"))
+    one = os.path.join(HERE, "g11_reference_corpus.npz")
+    np.savez_compressed(one, **files["g11_reference_corpus"])
+    written = [one]
+    if os.path.getsize(one) > limit:
+        os.remove(one)
+        written = []
+        for name in ("g11_hgr", "g11_dhgr"):
+            written.append(os.path.join(HERE, name + ".npz"))
+            np.savez_compressed(written[-1], **files[name])
+    for path in written:
+        print("%s: %d bytes (largest fixture so far: %d)" % (os.path.basename(path), os.path.getsize(path), limit))
+        assert os.path.getsize(path) <= limit, "a g11 fixture is larger than the largest fixture committed"
+    print("g11 written")
+
+
+if __name__ == "__main__" and "--corpus-only" in sys.argv:
+    _ap = argparse.ArgumentParser()
+    _ap.add_argument("--corpus-only", action="store_true")
+    _ap.add_argument("--scratch", default="/tmp/iiv_ref")
+    _ap.add_argument("--jobs", type=int, default=0)
+    _args = _ap.parse_args()
+    make_corpus_golden(_args.scratch, _args.jobs or None)

@@ -26,6 +26,16 @@ rounds = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 40
 fourth = "--fourth" in sys.argv
 import oracle as O  # noqa: E402
 O.build()
+# the picture-like frames come from the corpus' builders, made before the reference is imported (its modules go by the
+# project's names): a pool of bar periods / speeds / slopes / phases per mode, three frames each
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import reference_corpus as RC  # noqa: E402
+IMG = {mode: [RC.img_frames(mode, 3, 1000 + 16 * mode + k) for k in range(16)] for mode in (0, 1)}
+_mine = os.path.join(ROOT, "ii-vision_amd", "transcoder")
+for _name, _mod in list(sys.modules.items()):
+    if getattr(_mod, "__file__", None) and os.path.dirname(os.path.abspath(_mod.__file__)) == _mine:
+        del sys.modules[_name]
+sys.path[:] = [p for p in sys.path if os.path.abspath(p) != _mine]
 MG.setup_reference("/tmp/iiv_ref")
 MG.write_reference_tables("/tmp/iiv_ref", O)
 import frame_grabber  # noqa: E402
@@ -53,22 +63,9 @@ for rnd in range(rounds):
     kind = ("iid", "coh", "static", "img")[int(rng.integers(0, 4))]
     nf = 3
     hi = 128 if mode else 256
-    if kind == "img":   # dithered moving bars, packed 7 dots per byte (as stream_batch.synth_frames_img)
+    if kind == "img":   # dithered moving bars: the builder of tests/reference_corpus.py (stream_batch.synth_frames_img), made above
         frames = np.zeros((nf, 2, 32, 256), np.uint8)
-        W = 560 if mode else 280
-        period, speed, slope, phase = int(rng.integers(24, 120)), int(rng.integers(1, 6)), int(rng.integers(-2, 3)), int(rng.integers(0, 120))
-        bayer = np.array([[0, 8, 2, 10], [12, 4, 14, 6], [3, 11, 1, 9], [15, 7, 13, 5]])
-        y, x = np.mgrid[0:192, 0:W]
-        for f in range(nf):
-            dots = (((x + slope * y + speed * f + phase) % period) * 17) // period > bayer[y % 4, x % 4]
-            by = (dots.reshape(192, W // 7, 7) * (1 << np.arange(7))).sum(-1).astype(np.uint8)
-            for yy in range(192):
-                for xx in range(40):
-                    p, o = int(screen.X_Y_TO_PAGE[yy, xx]), int(screen.X_Y_TO_OFFSET[yy, xx])
-                    if mode:
-                        frames[f, 1, p, o], frames[f, 0, p, o] = by[yy, 2 * xx], by[yy, 2 * xx + 1]
-                    else:
-                        frames[f, 0, p, o] = by[yy, xx]
+        frames[:, :2 if mode else 1] = IMG[mode][int(rng.integers(0, len(IMG[mode])))]
     else:
         frames = np.zeros((nf, 2, 32, 256), np.uint8)
         keep_p = {"iid": 0.0, "coh": 0.9, "static": 0.98}[kind]
