@@ -112,10 +112,9 @@ int emit_stream(int mode, int n_streams, long n_ops, const uint8_t *d_ops, const
     if (!rc) rc = hip_check(hipMemsetAsync(d_err, 0, sizeof(int), st), "clear flag");
     if (!rc) {
         dim3 grid((unsigned)((n_emit + 255) / 256 > 0 ? (n_emit + 255) / 256 : 1), (unsigned)n_streams);
-        hipLaunchKernelGGL(emit_kernel, grid, dim3(256), 0, st, mode, 0L, n_emit, d_ops, (size_t)n_ops * 6, d_ticks,
-                           (size_t)n_ops, 0u, d_addr, (uint32_t)ack_addr, (uint32_t)term_addr, d_out, out_stride, (size_t)0, 1,
-                           1, total, d_err);
-        rc = hip_check(hipGetLastError(), "emit_kernel launch");
+        rc = launch(emit_kernel, "emit_kernel launch", grid, dim3(256), 0, st, mode, 0L, n_emit, d_ops, (size_t)n_ops * 6, d_ticks,
+                    (size_t)n_ops, 0u, d_addr, (uint32_t)ack_addr, (uint32_t)term_addr, d_out, out_stride, (size_t)0, 1, 1, total,
+                    d_err);
     }
     if (!rc) rc = hip_check(hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, st), "read flag");
     if (!rc) rc = hip_check(hipStreamSynchronize(st), "emit sync");  // tick_addr is caller memory; d_addr is freed on return
@@ -141,10 +140,9 @@ int emit_chunk(int mode, int n_streams, long first_op, long n_ops, const uint8_t
     if (out_stride < nb) return set_error(IIV_ERR_INVALID, "iiv_emit_chunk: out_stride %zu < %zu", out_stride, nb);
     if (n_ops == 0 && first_op != 0) return IIV_OK;
     dim3 grid((unsigned)((n_ops + 255) / 256 > 0 ? (n_ops + 255) / 256 : 1), (unsigned)n_streams);
-    hipLaunchKernelGGL(emit_kernel, grid, dim3(256), 0, st, mode, first_op, n_ops, d_ops, ops_stride, d_ticks, ticks_stride,
-                       (uint32_t)const_tick, d_tick_addr, (uint32_t)ack_addr, 0u, d_out, out_stride, b0, first_op == 0 ? 1 : 0,
-                       0, (size_t)0, d_err);
-    return hip_check(hipGetLastError(), "emit_kernel launch");
+    return launch(emit_kernel, "emit_kernel launch", grid, dim3(256), 0, st, mode, first_op, n_ops, d_ops, ops_stride, d_ticks, ticks_stride,
+                  (uint32_t)const_tick, d_tick_addr, (uint32_t)ack_addr, 0u, d_out, out_stride, b0, first_op == 0 ? 1 : 0, 0, (size_t)0,
+                  d_err);
 }
 
 }  // namespace iiv

@@ -296,12 +296,14 @@ extern "C" int iiv_a2m_scan(const iiv_a2m_reader *reader, int n_streams, const u
     const long long *len = reinterpret_cast<const long long *>(d_lengths);
     long long *info = reinterpret_cast<long long *>(d_info);
     const unsigned per_stream = (unsigned)((n_streams + 255) / 256);
-    hipLaunchKernelGGL(scan_init_kernel, dim3(per_stream), dim3(256), 0, st, n_streams, d_bytes, stride, len, info);
-    hipLaunchKernelGGL(scan_slots_kernel, dim3(grid), dim3(256), 0, st, bps, d_bytes, stride, len, reader->inv.get(), info);
-    hipLaunchKernelGGL(scan_check_kernel, dim3(grid), dim3(256), 0, st, bps, d_bytes, stride, len, reader->inv.get(),
-                       (uint32_t)reader->ack, info);
-    hipLaunchKernelGGL(scan_finish_kernel, dim3(per_stream), dim3(256), 0, st, n_streams, info);
-    return hip_check(hipGetLastError(), "a2m scan launch");
+    if (int rc = launch(scan_init_kernel, "scan_init_kernel launch", dim3(per_stream), dim3(256), 0, st, n_streams, d_bytes, stride, len, info))
+        return rc;
+    if (int rc = launch(scan_slots_kernel, "scan_slots_kernel launch", dim3(grid), dim3(256), 0, st, bps, d_bytes, stride, len, reader->inv, info))
+        return rc;
+    if (int rc = launch(scan_check_kernel, "scan_check_kernel launch", dim3(grid), dim3(256), 0, st, bps, d_bytes, stride, len, reader->inv,
+                        (uint32_t)reader->ack, info))
+        return rc;
+    return launch(scan_finish_kernel, "scan_finish_kernel launch", dim3(per_stream), dim3(256), 0, st, n_streams, info);
 }
 
 extern "C" int iiv_a2m_decode(const iiv_a2m_reader *reader, int n_streams, const uint8_t *d_bytes, size_t stride, const int64_t *d_info,
@@ -316,9 +318,8 @@ extern "C" int iiv_a2m_decode(const iiv_a2m_reader *reader, int n_streams, const
         return set_error(IIV_ERR_INVALID, "iiv_a2m_decode: ops_stride %zu / ticks_stride %zu hold fewer than iiv_a2m_max_ops(stride) = %ld opcodes",
                          ops_stride, ticks_stride, max_slots);
     if (n_streams == 0) return IIV_OK;
-    hipLaunchKernelGGL(decode_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, bps, max_slots, d_bytes, stride,
-                       reinterpret_cast<const long long *>(d_info), reader->inv.get(), d_ops, ops_stride, d_ticks, d_banks, ticks_stride);
-    return hip_check(hipGetLastError(), "a2m decode launch");
+    return launch(decode_kernel, "a2m decode_kernel launch", dim3(grid), dim3(256), 0, (hipStream_t)stream, bps, max_slots, d_bytes, stride,
+                  reinterpret_cast<const long long *>(d_info), reader->inv, d_ops, ops_stride, d_ticks, d_banks, ticks_stride);
 }
 
 extern "C" int iiv_a2m_replay(const iiv_a2m_reader *reader, int n_streams, const uint8_t *d_bytes, size_t stride, const int64_t *d_info,
@@ -329,8 +330,7 @@ extern "C" int iiv_a2m_replay(const iiv_a2m_reader *reader, int n_streams, const
         n_snaps < 1 || !aligned8(d_info) || !aligned8(d_main) || !aligned8(d_aux) || !aligned8(d_init_main) || !aligned8(d_init_aux))
         return set_error(IIV_ERR_INVALID, "iiv_a2m_replay: bad argument");
     if (n_streams == 0) return IIV_OK;
-    hipLaunchKernelGGL(replay_kernel, dim3((unsigned)n_streams), dim3(kReplayThreads), 0, (hipStream_t)stream, slot_count(stride), d_bytes,
-                       stride, reinterpret_cast<const long long *>(d_info), reader->inv.get(), first_snap, snap_every, n_snaps, d_init_main,
-                       d_init_aux, d_main, d_aux);
-    return hip_check(hipGetLastError(), "a2m replay launch");
+    return launch(replay_kernel, "a2m replay_kernel launch", dim3((unsigned)n_streams), dim3(kReplayThreads), 0, (hipStream_t)stream,
+                  slot_count(stride), d_bytes, stride, reinterpret_cast<const long long *>(d_info), reader->inv, first_snap, snap_every,
+                  n_snaps, d_init_main, d_init_aux, d_main, d_aux);
 }

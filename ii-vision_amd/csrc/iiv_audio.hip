@@ -155,8 +155,7 @@ struct Scratch {
     int alloc(T **p, size_t count, const char *what)
     {
         void *v = nullptr;
-        int rc = hip_check(hipMallocAsync(&v, sizeof(T) * (count ? count : 1), st), what);
-        if (rc) return rc;
+        if (int rc = hip_check(hipMallocAsync(&v, sizeof(T) * (count ? count : 1), st), what)) return rc;
         mem.push_back(v);
         *p = (T *)v;
         return IIV_OK;
@@ -180,10 +179,8 @@ int twiddles(Scratch &call, int a, const float2 **out)
     }
     const long L = 1L << a;
     float2 *d = nullptr;
-    int rc = call.alloc(&d, (size_t)L, "hipMallocAsync(twiddles)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(twiddle_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, call.st, d, L);
-    IIV_HIP(hipGetLastError());
+    if (int rc = call.alloc(&d, (size_t)L, "hipMallocAsync(twiddles)")) return rc;
+    if (int rc = launch(twiddle_kernel, "twiddle_kernel launch", dim3((unsigned)((L + 255) / 256)), dim3(256), 0, call.st, d, L)) return rc;
     call.tw[a] = d;
     *out = d;
     return IIV_OK;
@@ -202,13 +199,12 @@ int fft(Scratch &call, float2 *buf, float2 *tmp, int a, long n_sig, int dir, con
     }
     if (a <= kFftMaxLog) {
         const float2 *tw;
-        int rc = twiddles(call, a, &tw);
-        if (rc) return rc;
+        if (int rc = twiddles(call, a, &tw)) return rc;
         int C = (1 << kFftMaxLog) >> a;
         long n_t = n_sig;
-        hipLaunchKernelGGL(fft_lds_kernel, dim3((unsigned)((n_t + C - 1) / C)), dim3(256), 0, st, buf, buf, a, C, n_t, 1L, L,
-                           0L, 1L, 0L, 1L, tw, dir, premul, (const float2 *)nullptr, 0L);
-        IIV_HIP(hipGetLastError());
+        if (int rc = launch(fft_lds_kernel, "fft_lds_kernel launch", dim3((unsigned)((n_t + C - 1) / C)), dim3(256), 0, st, buf, buf, a, C, n_t,
+                            1L, L, 0L, 1L, 0L, 1L, tw, dir, premul, (const float2 *)nullptr, 0L))
+            return rc;
         *result = buf;
         return IIV_OK;
     }
@@ -216,22 +212,21 @@ int fft(Scratch &call, float2 *buf, float2 *tmp, int a, long n_sig, int dir, con
     const int a2 = a / 2, a1 = a - a2;  // n = n1 * L2 + n2, k = k1 + L1 * k2
     const long L1 = 1L << a1, L2 = 1L << a2;
     const float2 *tw1, *tw2, *twt;
-    int rc = twiddles(call, a1, &tw1);
-    if (!rc) rc = twiddles(call, a2, &tw2);
-    if (!rc) rc = twiddles(call, a, &twt);
-    if (rc) return rc;
+    if (int rc = twiddles(call, a1, &tw1)) return rc;
+    if (int rc = twiddles(call, a2, &tw2)) return rc;
+    if (int rc = twiddles(call, a, &twt)) return rc;
     // columns: for each n2, L1 points n1 -> k1, times W_L^(n2 k1), in place at [k1 * L2 + n2]
     int C1 = (1 << kFftMaxLog) >> a1;
     long nt1 = n_sig * L2;
-    hipLaunchKernelGGL(fft_lds_kernel, dim3((unsigned)((nt1 + C1 - 1) / C1)), dim3(256), 0, st, buf, buf, a1, C1, nt1, L2, L,
-                       1L, L2, 1L, L2, tw1, dir, premul, twt, L - 1);
-    IIV_HIP(hipGetLastError());
+    if (int rc = launch(fft_lds_kernel, "fft_lds_kernel launch (columns)", dim3((unsigned)((nt1 + C1 - 1) / C1)), dim3(256), 0, st, buf, buf,
+                        a1, C1, nt1, L2, L, 1L, L2, 1L, L2, tw1, dir, premul, twt, L - 1))
+        return rc;
     // rows: for each k1, L2 points n2 -> k2, to [k1 + L1 * k2]
     int C2 = (1 << kFftMaxLog) >> a2;
     long nt2 = n_sig * L1;
-    hipLaunchKernelGGL(fft_lds_kernel, dim3((unsigned)((nt2 + C2 - 1) / C2)), dim3(256), 0, st, buf, tmp, a2, C2, nt2, L1, L,
-                       L2, 1L, 1L, L1, tw2, dir, (const float2 *)nullptr, (const float2 *)nullptr, 0L);
-    IIV_HIP(hipGetLastError());
+    if (int rc = launch(fft_lds_kernel, "fft_lds_kernel launch (rows)", dim3((unsigned)((nt2 + C2 - 1) / C2)), dim3(256), 0, st, buf, tmp, a2,
+                        C2, nt2, L1, L, L2, 1L, 1L, L1, tw2, dir, (const float2 *)nullptr, (const float2 *)nullptr, 0L))
+        return rc;
     *result = tmp;
     return IIV_OK;
 }
@@ -254,14 +249,13 @@ int bluestein_tables(Scratch &call, Scratch &group, long L, int dir, const float
 {
     const long M = bluestein_m(L);
     float2 *c = nullptr, *d = nullptr, *t = nullptr, *res = nullptr;
-    int rc = group.alloc(&c, (size_t)L, "hipMallocAsync(chirp)");
-    if (!rc) rc = group.alloc(&d, (size_t)M, "hipMallocAsync(chirp spectrum)");
-    if (!rc) rc = group.alloc(&t, (size_t)M, "hipMallocAsync(chirp spectrum)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(chirp_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, group.st, c, L, dir);
-    hipLaunchKernelGGL(bluestein_b_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, group.st, d, L, M, dir);
-    IIV_HIP(hipGetLastError());
-    if ((rc = fft(call, d, t, log2_exact(M), 1, -1, nullptr, &res))) return rc;
+    if (int rc = group.alloc(&c, (size_t)L, "hipMallocAsync(chirp)")) return rc;
+    if (int rc = group.alloc(&d, (size_t)M, "hipMallocAsync(chirp spectrum)")) return rc;
+    if (int rc = group.alloc(&t, (size_t)M, "hipMallocAsync(chirp spectrum)")) return rc;
+    if (int rc = launch(chirp_kernel, "chirp_kernel launch", dim3((unsigned)((L + 255) / 256)), dim3(256), 0, group.st, c, L, dir)) return rc;
+    if (int rc = launch(bluestein_b_kernel, "bluestein_b_kernel launch", dim3((unsigned)((M + 255) / 256)), dim3(256), 0, group.st, d, L, M, dir))
+        return rc;
+    if (int rc = fft(call, d, t, log2_exact(M), 1, -1, nullptr, &res)) return rc;
     *chirp = c;
     *bhat = res;
     return IIV_OK;
@@ -383,58 +377,59 @@ int run_group(Scratch &call, const int16_t *d_pcm, long nx, long num, bool ident
     Scratch group(st);
     const long J = (long)jobs.size();
     Job *d_jobs = nullptr;
-    int rc = group.alloc(&d_jobs, (size_t)J, "hipMallocAsync(jobs)");
-    if (rc) return rc;
+    if (int rc = group.alloc(&d_jobs, (size_t)J, "hipMallocAsync(jobs)")) return rc;
     IIV_HIP(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(Job) * J, hipMemcpyHostToDevice, st));
     if (identity) {
         for (long j0 = 0; j0 < J; j0 += 65535) {
             long jc = J - j0 < 65535 ? J - j0 : 65535;
-            hipLaunchKernelGGL(identity_kernel, dim3((unsigned)((nx + 255) / 256), (unsigned)jc), dim3(256), 0, st, d_pcm,
-                               d_jobs + j0, nx, d_ticks, d_fout);
-            if ((rc = hip_check(hipGetLastError(), "identity_kernel"))) break;
+            if (int rc = launch(identity_kernel, "identity_kernel launch", dim3((unsigned)((nx + 255) / 256), (unsigned)jc), dim3(256), 0, st,
+                                d_pcm, d_jobs + j0, nx, d_ticks, d_fout))
+                return rc;
         }
-        return rc;
+        return IIV_OK;
     }
     const bool fb = !is_pow2(nx), ib = !is_pow2(num);
     const long lf = transform_points(nx), li = transform_points(num);
     const long lmax = lf > li ? lf : li;
     const float2 *fchirp = nullptr, *fbhat = nullptr, *ichirp = nullptr, *ibhat = nullptr;
-    if (fb && (rc = bluestein_tables(call, group, nx, -1, &fchirp, &fbhat))) return rc;
-    if (ib && (rc = bluestein_tables(call, group, num, +1, &ichirp, &ibhat))) return rc;
+    if (fb)
+        if (int rc = bluestein_tables(call, group, nx, -1, &fchirp, &fbhat)) return rc;
+    if (ib)
+        if (int rc = bluestein_tables(call, group, num, +1, &ichirp, &ibhat)) return rc;
     long jc = (long)(kWorkspaceBytes / (sizeof(float2) * (size_t)lmax));
     jc = jc < 1 ? 1 : (jc > 65535 ? 65535 : jc);
     jc = jc > J ? J : jc;
     float2 *w0 = nullptr, *w1 = nullptr;
-    if ((rc = group.alloc(&w0, (size_t)lmax * jc, "hipMallocAsync(work)")) || (rc = group.alloc(&w1, (size_t)lmax * jc, "hipMallocAsync(work)")))
-        return rc;
+    if (int rc = group.alloc(&w0, (size_t)lmax * jc, "hipMallocAsync(work)")) return rc;
+    if (int rc = group.alloc(&w1, (size_t)lmax * jc, "hipMallocAsync(work)")) return rc;
     const int af = log2_exact(lf), ai = log2_exact(li);
-    for (long j0 = 0; j0 < J && !rc; j0 += jc) {
+    for (long j0 = 0; j0 < J; j0 += jc) {
         const long n = J - j0 < jc ? J - j0 : jc;
         float2 *r = nullptr, *other;
-        hipLaunchKernelGGL(mono_kernel, dim3((unsigned)((lf + 255) / 256), (unsigned)n), dim3(256), 0, st, d_pcm, d_jobs + j0, nx,
-                           lf, fchirp, w0);
-        if ((rc = hip_check(hipGetLastError(), "mono_kernel"))) break;
-        if ((rc = fft(call, w0, w1, af, n, -1, nullptr, &r))) break;
+        if (int rc = launch(mono_kernel, "mono_kernel launch", dim3((unsigned)((lf + 255) / 256), (unsigned)n), dim3(256), 0, st, d_pcm,
+                            d_jobs + j0, nx, lf, fchirp, w0))
+            return rc;
+        if (int rc = fft(call, w0, w1, af, n, -1, nullptr, &r)) return rc;
         if (fb) {   // Bluestein: the convolution with the chirp, the inverse FFT of the product with the filter's spectrum
             other = r == w0 ? w1 : w0;
-            if ((rc = fft(call, r, other, af, n, +1, fbhat, &r))) break;
+            if (int rc = fft(call, r, other, af, n, +1, fbhat, &r)) return rc;
         }
         other = r == w0 ? w1 : w0;
-        hipLaunchKernelGGL(spectrum_kernel, dim3((unsigned)((li + 255) / 256), (unsigned)n), dim3(256), 0, st, r, lf, fchirp, nx,
-                           num, li, ichirp, other);
-        if ((rc = hip_check(hipGetLastError(), "spectrum_kernel"))) break;
+        if (int rc = launch(spectrum_kernel, "spectrum_kernel launch", dim3((unsigned)((li + 255) / 256), (unsigned)n), dim3(256), 0, st, r, lf,
+                            fchirp, nx, num, li, ichirp, other))
+            return rc;
         r = other;
         other = r == w0 ? w1 : w0;
-        if ((rc = fft(call, r, other, ai, n, ib ? -1 : +1, nullptr, &r))) break;
+        if (int rc = fft(call, r, other, ai, n, ib ? -1 : +1, nullptr, &r)) return rc;
         if (ib) {
             other = r == w0 ? w1 : w0;
-            if ((rc = fft(call, r, other, ai, n, +1, ibhat, &r))) break;
+            if (int rc = fft(call, r, other, ai, n, +1, ibhat, &r)) return rc;
         }
-        hipLaunchKernelGGL(finish_kernel, dim3((unsigned)((num + 255) / 256), (unsigned)n), dim3(256), 0, st, r, li, ichirp, num,
-                           d_jobs + j0, d_ticks, d_fout);
-        rc = hip_check(hipGetLastError(), "finish_kernel");
+        if (int rc = launch(finish_kernel, "finish_kernel launch", dim3((unsigned)((num + 255) / 256), (unsigned)n), dim3(256), 0, st, r, li, ichirp,
+                            num, d_jobs + j0, d_ticks, d_fout))
+            return rc;
     }
-    return rc;
+    return IIV_OK;
 }
 
 // the jobs of one call, grouped by (nx, num); identity: rate == bitrate, grouped by length.  Every transform size is
@@ -449,11 +444,10 @@ int run_jobs(const int16_t *d_pcm, const std::map<std::pair<long, long>, std::ve
                                  "library runs (DESIGN.md 10: shorter decode blocks, or a shorter normalisation prefix)",
                                  L, transform_points(L), kFftMaxLogTotal);
     Scratch call(st);
-    int rc;
     for (auto &g : identity)
-        if ((rc = run_group(call, d_pcm, g.first, g.first, true, g.second, d_ticks, d_fout))) return rc;
+        if (int rc = run_group(call, d_pcm, g.first, g.first, true, g.second, d_ticks, d_fout)) return rc;
     for (auto &g : groups)
-        if ((rc = run_group(call, d_pcm, g.first.first, g.first.second, false, g.second, d_ticks, d_fout))) return rc;
+        if (int rc = run_group(call, d_pcm, g.first.first, g.first.second, false, g.second, d_ticks, d_fout)) return rc;
     return IIV_OK;
 }
 
@@ -571,8 +565,7 @@ int iiv_audio_ticks(int n_streams, const int16_t *d_pcm, size_t pcm_stride, cons
                     const int *rate, int bitrate, long block_frames, const double *normalization, uint8_t *d_ticks,
                     size_t ticks_stride, long *n_ticks, void *stream)
 {
-    int rc = check_streams(n_streams, d_pcm, pcm_stride, n_frames, channels, rate, bitrate);
-    if (rc) return rc;
+    if (int rc = check_streams(n_streams, d_pcm, pcm_stride, n_frames, channels, rate, bitrate)) return rc;
     if (block_frames <= 0) return set_error(IIV_ERR_INVALID, "audio_ticks: block_frames must be > 0");
     if (n_streams > 0 && (!normalization || !d_ticks)) return set_error(IIV_ERR_INVALID, "audio_ticks: normalization / d_ticks NULL");
     IIV_HIP(have_device());
@@ -608,8 +601,7 @@ int iiv_audio_ticks(int n_streams, const int16_t *d_pcm, size_t pcm_stride, cons
 int iiv_audio_resample(int n_streams, const int16_t *d_pcm, size_t pcm_stride, const long *n_frames, const int *channels,
                        const int *rate, int bitrate, float *d_out, size_t out_stride, long *n_out_samples, void *stream)
 {
-    int rc = check_streams(n_streams, d_pcm, pcm_stride, n_frames, channels, rate, bitrate);
-    if (rc) return rc;
+    if (int rc = check_streams(n_streams, d_pcm, pcm_stride, n_frames, channels, rate, bitrate)) return rc;
     if (n_streams > 0 && !d_out) return set_error(IIV_ERR_INVALID, "audio_resample: d_out NULL");
     IIV_HIP(have_device());
     std::map<std::pair<long, long>, std::vector<Job>> groups;
@@ -634,8 +626,7 @@ int iiv_audio_resample(int n_streams, const int16_t *d_pcm, size_t pcm_stride, c
 int iiv_audio_normalization(int n_streams, const int16_t *d_pcm, size_t pcm_stride, const long *n_frames, const int *channels,
                             const int *rate, int bitrate, double *normalization, void *stream)
 {
-    int rc = check_streams(n_streams, d_pcm, pcm_stride, n_frames, channels, rate, bitrate);
-    if (rc) return rc;
+    if (int rc = check_streams(n_streams, d_pcm, pcm_stride, n_frames, channels, rate, bitrate)) return rc;
     if (n_streams > 0 && !normalization) return set_error(IIV_ERR_INVALID, "audio_normalization: normalization NULL");
     IIV_HIP(have_device());
     if (n_streams == 0) return IIV_OK;
@@ -652,7 +643,7 @@ int iiv_audio_normalization(int n_streams, const int16_t *d_pcm, size_t pcm_stri
     }
     // the prefixes, decoded as one block each (audio.py:67), side by side: stream s at y + off[s]
     DeviceBuf<float> d_y;
-    if ((rc = d_y.alloc((size_t)total, "hipMalloc(prefixes)"))) return rc;
+    if (int rc = d_y.alloc((size_t)total, "hipMalloc(prefixes)")) return rc;
     std::map<std::pair<long, long>, std::vector<Job>> groups;
     std::map<long, std::vector<Job>> identity;
     for (int s = 0; s < n_streams; s++) {
@@ -664,7 +655,7 @@ int iiv_audio_normalization(int n_streams, const int16_t *d_pcm, size_t pcm_stri
             groups[{pf[s], ns[s]}].push_back(jb);
         }
     }
-    rc = run_jobs(d_pcm, groups, identity, nullptr, d_y, st);
+    if (int rc = run_jobs(d_pcm, groups, identity, nullptr, d_y, st)) return rc;
     // np.percentile(a, [0.5, 99.5]) (linear): ranks floor(q (n-1)) and the next one, for both q
     std::vector<uint32_t> rank(4 * (size_t)n_streams);
     std::vector<double> frac(2 * (size_t)n_streams);
@@ -682,29 +673,30 @@ int iiv_audio_normalization(int n_streams, const int16_t *d_pcm, size_t pcm_stri
     DeviceBuf<float> d_val;
     DeviceBuf<long> d_meta;      // [off n][len n]
     std::vector<float> val(4 * (size_t)n_streams);
-    if (rc) return rc;
-    if ((rc = d_sel.alloc((size_t)n_streams * 1032, "hipMalloc(select)"))) return rc;
-    if ((rc = d_val.alloc(4 * (size_t)n_streams, "hipMalloc(select values)"))) return rc;
+    if (int rc = d_sel.alloc((size_t)n_streams * 1032, "hipMalloc(select)")) return rc;
+    if (int rc = d_val.alloc(4 * (size_t)n_streams, "hipMalloc(select values)")) return rc;
     std::vector<long> meta(2 * (size_t)n_streams);
     for (int s = 0; s < n_streams; s++) meta[s] = off[s], meta[n_streams + s] = ns[s];
-    if ((rc = d_meta.alloc(2 * (size_t)n_streams, "hipMalloc(select meta)"))) return rc;
+    if (int rc = d_meta.alloc(2 * (size_t)n_streams, "hipMalloc(select meta)")) return rc;
     uint32_t *hist = d_sel, *prefix = d_sel + (size_t)n_streams * 1024, *drank = prefix + (size_t)n_streams * 4;
-    if ((rc = hip_check(hipMemsetAsync(d_sel, 0, sizeof(uint32_t) * (size_t)n_streams * 1028, st), "hipMemsetAsync"))) return rc;
-    if ((rc = hip_check(hipMemcpyAsync(drank, rank.data(), sizeof(uint32_t) * 4 * n_streams, hipMemcpyHostToDevice, st), "copy ranks"))) return rc;
-    if ((rc = hip_check(hipMemcpyAsync(d_meta, meta.data(), sizeof(long) * 2 * n_streams, hipMemcpyHostToDevice, st), "copy meta"))) return rc;
+    IIV_HIP(hipMemsetAsync(d_sel, 0, sizeof(uint32_t) * (size_t)n_streams * 1028, st));
+    IIV_HIP(hipMemcpyAsync(drank, rank.data(), sizeof(uint32_t) * 4 * n_streams, hipMemcpyHostToDevice, st));
+    IIV_HIP(hipMemcpyAsync(d_meta, meta.data(), sizeof(long) * 2 * n_streams, hipMemcpyHostToDevice, st));
     unsigned gx = (unsigned)((mx + 255) / 256);
     gx = gx > 1024 ? 1024 : gx;
     for (int shift = 24; shift >= 0; shift -= 8) {
-        hipLaunchKernelGGL(select_hist_kernel, dim3(gx, (unsigned)n_streams), dim3(256), 0, st, d_y.get(), d_meta.get(), d_meta + n_streams,
-                           prefix, shift, hist);
-        hipLaunchKernelGGL(select_pick_kernel, dim3((unsigned)((4 * n_streams + 63) / 64)), dim3(64), 0, st, n_streams, shift,
-                           hist, prefix, drank);
-        if ((rc = hip_check(hipGetLastError(), "select kernels"))) return rc;
+        if (int rc = launch(select_hist_kernel, "select_hist_kernel launch", dim3(gx, (unsigned)n_streams), dim3(256), 0, st, d_y, d_meta,
+                         d_meta + n_streams, prefix, shift, hist))
+            return rc;
+        if (int rc = launch(select_pick_kernel, "select_pick_kernel launch", dim3((unsigned)((4 * n_streams + 63) / 64)), dim3(64), 0, st, n_streams,
+                         shift, hist, prefix, drank))
+            return rc;
     }
-    hipLaunchKernelGGL(select_values_kernel, dim3((unsigned)((4 * n_streams + 63) / 64)), dim3(64), 0, st, 4 * n_streams, prefix, d_val.get());
-    if ((rc = hip_check(hipGetLastError(), "select_values_kernel"))) return rc;
-    if ((rc = hip_check(hipMemcpyAsync(val.data(), d_val, sizeof(float) * 4 * n_streams, hipMemcpyDeviceToHost, st), "copy values"))) return rc;
-    if ((rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize"))) return rc;   // (the owners free behind it)
+    if (int rc = launch(select_values_kernel, "select_values_kernel launch", dim3((unsigned)((4 * n_streams + 63) / 64)), dim3(64), 0, st,
+                     4 * n_streams, prefix, d_val))
+        return rc;
+    IIV_HIP(hipMemcpyAsync(val.data(), d_val, sizeof(float) * 4 * n_streams, hipMemcpyDeviceToHost, st));
+    IIV_HIP(hipStreamSynchronize(st));   // (the owners free behind it)
     for (int s = 0; s < n_streams; s++) {
         double m = 0.0;
         for (int h = 0; h < 2; h++) {

@@ -119,20 +119,12 @@ __global__ __launch_bounds__(256) void delta_pages_kernel(const uint16_t *__rest
     out[q * 256 + y] = nd - dw_rows[q * 256 + y];  // screen.py:547
 }
 
-#define IIV_DISPATCH(mode, KERNEL, grid, block, st, ...)                                   \
-    do {                                                                                   \
-        if ((mode) == kDHGR)                                                               \
-            hipLaunchKernelGGL(KERNEL<kDHGR>, grid, block, 0, st, __VA_ARGS__);            \
-        else                                                                               \
-            hipLaunchKernelGGL(KERNEL<kHGR>, grid, block, 0, st, __VA_ARGS__);             \
-    } while (0)
-
 int pack(int mode, int n, const uint8_t *d_main, const uint8_t *d_aux, uint64_t *d_packed, hipStream_t st)
 {
     if (n <= 0) return IIV_OK;
     dim3 grid((unsigned)(((size_t)n * 4096 + 255) / 256));
-    IIV_DISPATCH(mode, pack_kernel, grid, dim3(256), st, n, d_main, d_aux, d_packed);
-    return hip_check(hipGetLastError(), "pack_kernel launch");
+    return launch(by_mode(mode, pack_kernel<kDHGR>, pack_kernel<kHGR>), "pack_kernel launch", grid, dim3(256), 0, st, n, d_main, d_aux,
+                  d_packed);
 }
 
 int diff_weights(int mode, const uint16_t *d_table, int n, const uint64_t *d_src, const uint64_t *d_tgt,
@@ -140,8 +132,8 @@ int diff_weights(int mode, const uint16_t *d_table, int n, const uint64_t *d_src
 {
     if (n <= 0) return IIV_OK;
     dim3 grid((unsigned)(((size_t)n * 8192 + 255) / 256));
-    IIV_DISPATCH(mode, diff_weights_kernel, grid, dim3(256), st, d_table, n, d_src, d_tgt, is_aux, d_out);
-    return hip_check(hipGetLastError(), "diff_weights_kernel launch");
+    return launch(by_mode(mode, diff_weights_kernel<kDHGR>, diff_weights_kernel<kHGR>), "diff_weights_kernel launch", grid, dim3(256), 0, st,
+                  d_table, n, d_src, d_tgt, is_aux, d_out);
 }
 
 int compute_delta_pages(int mode, const uint16_t *d_table, int n, const uint64_t *d_tgt, const int32_t *d_pages,
@@ -149,9 +141,8 @@ int compute_delta_pages(int mode, const uint16_t *d_table, int n, const uint64_t
                         hipStream_t st)
 {
     if (n <= 0) return IIV_OK;
-    IIV_DISPATCH(mode, delta_pages_kernel, dim3(n), dim3(256), st, d_table, d_tgt, d_pages, d_contents, d_dw_rows,
-                 is_aux, d_out);
-    return hip_check(hipGetLastError(), "delta_pages_kernel launch");
+    return launch(by_mode(mode, delta_pages_kernel<kDHGR>, delta_pages_kernel<kHGR>), "delta_pages_kernel launch", dim3(n), dim3(256), 0, st,
+                  d_table, d_tgt, d_pages, d_contents, d_dw_rows, is_aux, d_out);
 }
 
 }  // namespace iiv

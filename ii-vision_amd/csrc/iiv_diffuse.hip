@@ -456,16 +456,12 @@ static int frames_to_memory_maps_diffused(int mode, const uint8_t palette_rgb[48
 {
     const Palette P = make_palette(palette_rgb);
     const int n_banks = mode == kDHGR ? 2 * n : n;
-    hipLaunchKernelGGL(holes_kernel, dim3((unsigned)(((size_t)n_banks * 64 + 255) / 256)), dim3(256), 0, st, n_banks, d_main,
-                       mode == kDHGR ? d_aux : (uint8_t *)nullptr);
-    int rc = hip_check(hipGetLastError(), "diffuse holes_kernel launch");
-    if (rc) return rc;
+    if (int rc = launch(holes_kernel, "diffuse holes_kernel launch", dim3((unsigned)(((size_t)n_banks * 64 + 255) / 256)), dim3(256), 0, st,
+                        n_banks, d_main, mode == kDHGR ? d_aux : (uint8_t *)nullptr))
+        return rc;
     const dim3 grid((unsigned)((n + kFrames * kWaves - 1) / (kFrames * kWaves)));
-    if (mode == kDHGR)
-        hipLaunchKernelGGL(ingest_diffused_kernel<kDHGR>, grid, dim3(64 * kWaves), 0, st, n, d_rgb, P, W, d_main, d_aux);
-    else
-        hipLaunchKernelGGL(ingest_diffused_kernel<kHGR>, grid, dim3(64 * kWaves), 0, st, n, d_rgb, P, W, d_main, d_aux);
-    return hip_check(hipGetLastError(), "ingest_diffused_kernel launch");
+    return launch(by_mode(mode, ingest_diffused_kernel<kDHGR>, ingest_diffused_kernel<kHGR>), "ingest_diffused_kernel launch", grid,
+                  dim3(64 * kWaves), 0, st, n, d_rgb, P, W, d_main, d_aux);
 }
 
 }  // namespace diffuse

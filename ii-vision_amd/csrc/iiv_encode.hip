@@ -70,8 +70,7 @@ __global__ __launch_bounds__(1024) void order_streams_kernel(const uint32_t *__r
 }
 int launch_order_streams(const uint32_t *d_cost, int n, int *d_perm, int identity, hipStream_t st)
 {
-    hipLaunchKernelGGL(order_streams_kernel, dim3(1), dim3(1024), 0, st, d_cost, n, d_perm, identity);
-    return hip_check(hipGetLastError(), "order_streams_kernel launch");
+    return launch(order_streams_kernel, "order_streams_kernel launch", dim3(1), dim3(1024), 0, st, d_cost, n, d_perm, identity);
 }
 
 static int prof_begin(Encoder *e, int cls, hipStream_t st, size_t &slot)
@@ -223,8 +222,8 @@ static int tie_stats_request(Encoder *e, hipStream_t st)
     if (!e->d_tie_stats || e->tie_copy_pending || !choose_launch(launch_inputs(*e), -1).count_stats) return IIV_OK;
     IIV_HIP(hipMemsetAsync(e->d_tie_stats, 0, 3 * sizeof(unsigned long long), st));
     const int blocks = e->n_streams < 64 * 256 ? (e->n_streams + 255) / 256 : 64;
-    hipLaunchKernelGGL(tie_stats_kernel, dim3(blocks), dim3(256), 0, st, e->d_states, e->n_streams, e->d_tie_stats);
-    IIV_HIP(hipGetLastError());
+    if (int rc = launch(tie_stats_kernel, "tie_stats_kernel launch", dim3(blocks), dim3(256), 0, st, e->d_states, e->n_streams, e->d_tie_stats))
+        return rc;
     IIV_HIP(hipMemcpyAsync(e->h_tie_stats, e->d_tie_stats, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     IIV_HIP(hipEventRecord(e->tie_ev, st));
     e->tie_copy_pending = true;
@@ -258,7 +257,7 @@ static int launch_round(Encoder *e, const uint8_t *d_main, const uint8_t *d_aux,
         // longest first: every kOrderEvery launches the streams are sorted by what their latest launch cost them (d_perm holds
         // the identity until the first sort)
         if (c.ordered && --e->order_countdown <= 0) {
-            if ((rc = launch_order_streams(e->d_cost, e->n_streams, e->d_perm, 0, st))) return rc;
+            if (int rc = launch_order_streams(e->d_cost, e->n_streams, e->d_perm, 0, st)) return rc;
             e->order_countdown = kOrderEvery;
         }
         GreedyArgs a{e->d_states, d_main, d_aux, n_frames, e->n_streams, d_round, seg_stride, e->d_left, e->d_right, e->nt, d_ops,
@@ -286,17 +285,16 @@ int encode(Encoder *e, const uint8_t *d_main, const uint8_t *d_aux, int n_frames
     GenState gs = e->gens[0];
     std::vector<LaunchSeg> rounds;
     size_t total = 0;
-    int rc = plan_stream(e, 0, segs, n_segs, n_frames, gs, rounds, total);
-    if (rc) return rc;
+    if (int rc = plan_stream(e, 0, segs, n_segs, n_frames, gs, rounds, total)) return rc;
     e->gens[0] = gs;
     if (rounds.empty()) return IIV_OK;
-    if ((rc = upload_segs(e, rounds, st))) return rc;
+    if (int rc = upload_segs(e, rounds, st)) return rc;
     // (the stream counters are the LDS-shared form's: the team kernel's launches -- few streams, the drop-in Video's path,
     // where a 4 us memset in front of every generator is felt -- do without)
-    if ((rc = reset_queues(e, rounds.size(), st))) return rc;
+    if (int rc = reset_queues(e, rounds.size(), st)) return rc;
     tie_stats_poll(e);
     for (size_t r = 0; r < rounds.size(); r++)
-        if ((rc = launch_round(e, d_main, d_aux, n_frames, r, e->d_segs + r, 0, rounds[r].need >= 0, rounds[r].is_aux, d_ops, total * 6, st)))
+        if (int rc = launch_round(e, d_main, d_aux, n_frames, r, e->d_segs + r, 0, rounds[r].need >= 0, rounds[r].is_aux, d_ops, total * 6, st))
             return rc;
     return tie_stats_request(e, st);
 }
@@ -377,12 +375,11 @@ int encode_streams(Encoder *e, const uint8_t *d_main, const uint8_t *d_aux, int 
             if (g.need >= 0) any_pro[r] = 1;
             if (g.n_ops > 0) bank[r] = bank[r] == -2 ? g.is_aux : (bank[r] == g.is_aux ? bank[r] : -1);
         }
-    int rc = upload_segs(e, table, st);
-    if (rc) return rc;
-    if ((rc = reset_queues(e, n_rounds, st))) return rc;
+    if (int rc = upload_segs(e, table, st)) return rc;
+    if (int rc = reset_queues(e, n_rounds, st)) return rc;
     tie_stats_poll(e);
     for (size_t r = 0; r < n_rounds; r++)
-        if ((rc = launch_round(e, d_main, d_aux, n_frames, r, e->d_segs + r * (size_t)S, 1, any_pro[r] != 0, bank[r] < 0 ? -1 : bank[r], d_ops, ops_stride, st)))
+        if (int rc = launch_round(e, d_main, d_aux, n_frames, r, e->d_segs + r * (size_t)S, 1, any_pro[r] != 0, bank[r] < 0 ? -1 : bank[r], d_ops, ops_stride, st))
             return rc;
     return tie_stats_request(e, st);
 }

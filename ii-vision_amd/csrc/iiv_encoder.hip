@@ -72,9 +72,8 @@ __global__ __launch_bounds__(256) void compact_up_kernel(StreamState *__restrict
 }
 static int materialise_up(Encoder *e, int s0, int n)
 {
-    hipLaunchKernelGGL(materialise_up_kernel, dim3(n), dim3(256), 0, 0, e->d_states + s0);
-    int rc = hip_check(hipGetLastError(), "materialise_up_kernel launch");
-    return rc ? rc : hip_check(hipDeviceSynchronize(), "materialise_up sync");
+    if (int rc = launch(materialise_up_kernel, "materialise_up_kernel launch", dim3(n), dim3(256), 0, 0, e->d_states + s0)) return rc;
+    return hip_check(hipDeviceSynchronize(), "materialise_up sync");
 }
 
 __global__ __launch_bounds__(256) void max_u16_kernel(const uint16_t *__restrict__ v, size_t n, uint32_t *__restrict__ result)
@@ -112,56 +111,58 @@ int encoder_create(int mode, const uint16_t *d_table, const uint16_t *d_store, c
     e->d_table = d_table;
     e->d_store = d_store;
     e->dw_mode = dm ? IIV_DW_RECURRENCE : IIV_DW_TABLE;
-    int rc = IIV_OK;
-    if ((rc = e->d_states.alloc((size_t)n_streams, "hipMalloc(stream states)"))) return rc;
-    if ((rc = e->d_result.alloc(2, "hipMalloc(result)"))) return rc;
+    if (int rc = e->d_states.alloc((size_t)n_streams, "hipMalloc(stream states)")) return rc;
+    if (int rc = e->d_result.alloc(2, "hipMalloc(result)")) return rc;
     if (n_streams >= kOrderMinStreams) {
-        if ((rc = e->d_cost.alloc((size_t)n_streams, "hipMalloc(stream costs)"))) return rc;
-        if ((rc = hip_check(hipMemset(e->d_cost, 0, sizeof(uint32_t) * (size_t)n_streams), "memset"))) return rc;
-        if ((rc = e->d_perm.alloc((size_t)n_streams, "hipMalloc(stream order)"))) return rc;
+        if (int rc = e->d_cost.alloc((size_t)n_streams, "hipMalloc(stream costs)")) return rc;
+        IIV_HIP(hipMemset(e->d_cost, 0, sizeof(uint32_t) * (size_t)n_streams));
+        if (int rc = e->d_perm.alloc((size_t)n_streams, "hipMalloc(stream order)")) return rc;
     }
-    if ((rc = e->d_packed.alloc(4096, "hipMalloc(packed)"))) return rc;
+    if (int rc = e->d_packed.alloc(4096, "hipMalloc(packed)")) return rc;
     // (the brief's staging struct: here, not on first use -- an allocation inside the asynchronous entry point would synchronise)
-    if ((rc = e->d_brief.alloc(1, "hipMalloc(brief)"))) return rc;
-    if ((rc = e->seg_ev[0].create(hipEventDisableTiming, "event"))) return rc;
-    if ((rc = e->seg_ev[1].create(hipEventDisableTiming, "event"))) return rc;
-    if ((rc = e->d_tie_stats.alloc(3, "hipMalloc(tie statistics)"))) return rc;
-    if ((rc = hip_check(hipMemset(e->d_tie_stats, 0, 3 * sizeof(unsigned long long)), "memset"))) return rc;
-    if ((rc = e->h_tie_stats.alloc(3, hipHostMallocDefault, "hipHostMalloc(tie statistics)"))) return rc;
+    if (int rc = e->d_brief.alloc(1, "hipMalloc(brief)")) return rc;
+    if (int rc = e->seg_ev[0].create(hipEventDisableTiming, "event")) return rc;
+    if (int rc = e->seg_ev[1].create(hipEventDisableTiming, "event")) return rc;
+    if (int rc = e->d_tie_stats.alloc(3, "hipMalloc(tie statistics)")) return rc;
+    IIV_HIP(hipMemset(e->d_tie_stats, 0, 3 * sizeof(unsigned long long)));
+    if (int rc = e->h_tie_stats.alloc(3, hipHostMallocDefault, "hipHostMalloc(tie statistics)")) return rc;
     e->h_tie_stats[0] = e->h_tie_stats[1] = e->h_tie_stats[2] = 0;
-    if ((rc = e->tie_ev.create(hipEventDisableTiming, "event"))) return rc;
+    if (int rc = e->tie_ev.create(hipEventDisableTiming, "event")) return rc;
     // the table values must fit the 11-bit fields too (a caller-made table may not come from dm)
     uint32_t h_max = 0;
-    if ((rc = hip_check(hipMemset(e->d_result, 0, 8), "memset"))) return rc;
+    IIV_HIP(hipMemset(e->d_result, 0, 8));
     const size_t n_store = (size_t)num_offsets(mode) << (content_bits(mode) + masked_bits(mode));
-    hipLaunchKernelGGL(max_u16_kernel, dim3(1024), dim3(256), 0, 0, d_store, n_store, (uint32_t *)e->d_result.get());
+    uint32_t *d_max = (uint32_t *)e->d_result.get();
+    if (int rc = launch(max_u16_kernel, "max_u16_kernel launch", dim3(1024), dim3(256), 0, 0, d_store, n_store, d_max)) return rc;
     if (!dm && d_table)
-        hipLaunchKernelGGL(max_u16_kernel, dim3(4096), dim3(256), 0, 0, d_table,
-                           (size_t)num_offsets(mode) << (2 * masked_bits(mode)), (uint32_t *)e->d_result.get());
-    if ((rc = hip_check(hipMemcpy(&h_max, e->d_result, 4, hipMemcpyDeviceToHost), "read max"))) return rc;
+        if (int rc = launch(max_u16_kernel, "max_u16_kernel launch", dim3(4096), dim3(256), 0, 0, d_table,
+                            (size_t)num_offsets(mode) << (2 * masked_bits(mode)), d_max))
+            return rc;
+    IIV_HIP(hipMemcpy(&h_max, e->d_result, 4, hipMemcpyDeviceToHost));
     if (h_max > (uint32_t)kMaxValue)
         return set_error(IIV_ERR_INVALID, "iiv_encoder_create: table value %u exceeds %d", h_max, kMaxValue);
     if (dm) {
-        if ((rc = build_strings(mode, dm, e->d_strings, e->d_sub, 0))) return rc;
-        if (mode == kHGR && (rc = build_hgr_dot_lut(e->d_hgr_dots, 0))) return rc;
-        if ((rc = build_dw_piece_table(mode, e->d_sub, e->d_dw_pieces, 0))) return rc;
-        if ((rc = e->d_left.alloc(split_entries(mode, 0), "hipMalloc(split left)"))) return rc;
-        if ((rc = e->d_right.alloc(split_entries(mode, 1), "hipMalloc(split right)"))) return rc;
-        if ((rc = build_split_tables(mode, e->d_strings, e->d_sub, e->d_left, e->d_right, 0))) return rc;
+        if (int rc = build_strings(mode, dm, e->d_strings, e->d_sub, 0)) return rc;
+        if (mode == kHGR)
+            if (int rc = build_hgr_dot_lut(e->d_hgr_dots, 0)) return rc;
+        if (int rc = build_dw_piece_table(mode, e->d_sub, e->d_dw_pieces, 0)) return rc;
+        if (int rc = e->d_left.alloc(split_entries(mode, 0), "hipMalloc(split left)")) return rc;
+        if (int rc = e->d_right.alloc(split_entries(mode, 1), "hipMalloc(split right)")) return rc;
+        if (int rc = build_split_tables(mode, e->d_strings, e->d_sub, e->d_left, e->d_right, 0)) return rc;
         // (the folded narrow form is compared with the caller's store table entry by entry: e->nt.exact)
-        if ((rc = build_narrow_tables(mode, e->d_strings, e->d_sub, e->d_left, d_store, &e->nt, e->nt_storage, 0))) return rc;
+        if (int rc = build_narrow_tables(mode, e->d_strings, e->d_sub, e->d_left, d_store, &e->nt, e->nt_storage, 0)) return rc;
     }
     // Video.__init__ (video.py:21-62); RNG streams default to random.seed(0) / np.random.seed(0)
     uint32_t rng0[1248], key0 = 0;
     seed_by_array(rng0, &key0, 1);
     seed_genrand(rng0 + 624, 0);
     DeviceBuf<uint32_t> d_rng0;
-    if ((rc = d_rng0.alloc(1248, "hipMalloc(rng0)"))) return rc;
-    if ((rc = hip_check(hipMemcpy(d_rng0, rng0, sizeof(rng0), hipMemcpyHostToDevice), "copy rng0"))) return rc;
-    if (e->d_perm && (rc = launch_order_streams(e->d_cost, n_streams, e->d_perm, 1, 0))) return rc;
-    hipLaunchKernelGGL(init_states_kernel, dim3(n_streams), dim3(256), 0, 0, e->d_states.get(), d_rng0.get());
-    if ((rc = hip_check(hipGetLastError(), "init_states launch"))) return rc;
-    if ((rc = hip_check(hipDeviceSynchronize(), "init sync"))) return rc;
+    if (int rc = d_rng0.alloc(1248, "hipMalloc(rng0)")) return rc;
+    IIV_HIP(hipMemcpy(d_rng0, rng0, sizeof(rng0), hipMemcpyHostToDevice));
+    if (e->d_perm)
+        if (int rc = launch_order_streams(e->d_cost, n_streams, e->d_perm, 1, 0)) return rc;
+    if (int rc = launch(init_states_kernel, "init_states_kernel launch", dim3(n_streams), dim3(256), 0, 0, e->d_states, d_rng0)) return rc;
+    IIV_HIP(hipDeviceSynchronize());
     *out = e.release();
     return IIV_OK;
 }
@@ -242,8 +243,7 @@ int encoder_set_option(Encoder *e, int option, int value)
         if (value == IIV_CONTENT_JOINT && !e->nt.exact) value = IIV_CONTENT_JOINT_SPLIT;
         if (value == IIV_CONTENT_JOINT && !e->d_joint_l) {
             DeviceBuf<uint32_t> l, r;
-            int rc = build_joint_tables(e->mode, e->nt, l, r, 0);
-            if (rc) return rc;
+            if (int rc = build_joint_tables(e->mode, e->nt, l, r, 0)) return rc;
             IIV_HIP(hipDeviceSynchronize());
             e->d_joint_l = std::move(l);
             e->d_joint_r = std::move(r);
@@ -359,8 +359,7 @@ int encoder_set_state(Encoder *e, int s0, int n, int what, const void *buf, size
         if (int rc = materialise_up(e, s0, n)) return rc;
     IIV_HIP(hipMemcpy2D(base + off, pitch, buf, bytes, bytes, (size_t)n, hipMemcpyHostToDevice));
     if (what == IIV_STATE_UP_MAIN || what == IIV_STATE_UP_AUX) {
-        hipLaunchKernelGGL(compact_up_kernel, dim3(n), dim3(256), 0, 0, e->d_states + s0);
-        if (int rc = hip_check(hipGetLastError(), "compact_up_kernel launch")) return rc;
+        if (int rc = launch(compact_up_kernel, "compact_up_kernel launch", dim3(n), dim3(256), 0, 0, e->d_states + s0)) return rc;
         return hip_check(hipDeviceSynchronize(), "compact_up sync");
     }
     return IIV_OK;
@@ -470,8 +469,7 @@ int encoder_get_video_brief(Encoder *e, int s, iiv_video_brief *out)
 {
     if (!e || !out || s < 0 || s >= e->n_streams) return set_error(IIV_ERR_INVALID, "get_video_brief: bad argument");
     IIV_HIP(hipDeviceSynchronize());
-    hipLaunchKernelGGL(brief_kernel, dim3(1), dim3(256), 0, 0, e->d_states + s, e->d_brief.get());
-    IIV_HIP(hipGetLastError());
+    if (int rc = launch(brief_kernel, "brief_kernel launch", dim3(1), dim3(256), 0, 0, e->d_states + s, e->d_brief)) return rc;
     IIV_HIP(hipMemcpy(out, e->d_brief, sizeof(iiv_video_brief), hipMemcpyDeviceToHost));
     return IIV_OK;
 }
@@ -481,8 +479,7 @@ int encoder_get_video_brief(Encoder *e, int s, iiv_video_brief *out)
 int encoder_get_video_brief_async(Encoder *e, int s, iiv_video_brief *out, hipStream_t st)
 {
     if (!e || !out || s < 0 || s >= e->n_streams) return set_error(IIV_ERR_INVALID, "get_video_brief_async: bad argument");
-    hipLaunchKernelGGL(brief_kernel, dim3(1), dim3(256), 0, st, e->d_states + s, e->d_brief.get());
-    IIV_HIP(hipGetLastError());
+    if (int rc = launch(brief_kernel, "brief_kernel launch", dim3(1), dim3(256), 0, st, e->d_states + s, e->d_brief)) return rc;
     IIV_HIP(hipMemcpyAsync(out, e->d_brief, sizeof(iiv_video_brief), hipMemcpyDeviceToHost, st));
     return IIV_OK;
 }
@@ -501,8 +498,8 @@ int encoder_set_video_state(Encoder *e, int s, const iiv_video_state *in)
     rng[1249] = in->rng_np[624];
     IIV_HIP(hipMemcpy(base + offsetof(StreamState, mt_py), rng, sizeof(rng), hipMemcpyHostToDevice));
     IIV_HIP(hipMemcpy(base + offsetof(StreamState, out_of_work), in->out_of_work, 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(compact_up_kernel, dim3(1), dim3(256), 0, 0, e->d_states + s);   // (both banks' priorities were just written)
-    if (int rc = hip_check(hipGetLastError(), "compact_up_kernel launch")) return rc;
+    // (both banks' priorities were just written)
+    if (int rc = launch(compact_up_kernel, "compact_up_kernel launch", dim3(1), dim3(256), 0, 0, e->d_states + s)) return rc;
     return hip_check(hipDeviceSynchronize(), "compact_up sync");
 }
 
@@ -571,9 +568,8 @@ int encoder_check(Encoder *e, int *bad_stream, hipStream_t st)
     int init = 0x7fffffff;
     int rc = hip_check(hipMemcpyAsync(d_res, &init, sizeof(int), hipMemcpyHostToDevice, st), "check init");
     if (!rc) {
-        hipLaunchKernelGGL(error_scan_kernel, dim3((e->n_streams + 255) / 256), dim3(256), 0, st, e->d_states,
-                           e->n_streams, d_res);
-        rc = hip_check(hipGetLastError(), "error_scan launch");
+        rc = launch(error_scan_kernel, "error_scan_kernel launch", dim3((e->n_streams + 255) / 256), dim3(256), 0, st, e->d_states, e->n_streams,
+                    d_res);
     }
     int first = 0x7fffffff;
     if (!rc) rc = hip_check(hipMemcpyAsync(&first, d_res, sizeof(int), hipMemcpyDeviceToHost, st), "check read");

@@ -1,5 +1,6 @@
-// iiv_host.h -- host-side declarations shared by the translation units of
-// libiivision.so (the C ABI itself is include/iivision.h).
+// iiv_host.h -- what the translation units of libiivision.so share on the host side (the C ABI itself is include/iivision.h):
+// the error idioms, the checked kernel launch, the owners of device memory, pinned memory and events, and the prototypes of
+// the functions one file calls in another.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,6 +22,24 @@ int hip_check(hipError_t e, const char *what);
         int _rc = ::iiv::hip_check((expr), #expr);       \
         if (_rc) return _rc;                             \
     } while (0)
+
+// ---- how a kernel is launched: launch() enqueues it and returns hip_check of the launch under `label` ("table_kernel launch":
+// the label names the kernel, iiv_last_error() quotes it), so every launch is checked on its own --
+//     if (int rc = launch(by_mode(mode, k<kDHGR>, k<kHGR>), "k launch", grid, dim3(256), 0, st, args...)) return rc;
+// P... comes from the kernel alone and the arguments convert to it as in a direct call: a literal, a size_t or a struct
+// by reference at the call site reaches the kernel as the type the kernel declares.
+template <typename T> struct KernelParam { using type = T; };
+template <typename... P>
+int launch(void (*kernel)(P...), const char *label, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st,
+           typename KernelParam<P>::type... args)
+{
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, st, args...);
+    return hip_check(hipGetLastError(), label);
+}
+
+// a kernel template's instance for `mode` (k<kDHGR> and k<kHGR> have one function type).  DHGR is named first: the device
+// code of a file's instances is emitted in the order the host code first names them.
+template <typename K> K by_mode(int mode, K dhgr, K hgr) { return mode == kDHGR ? dhgr : hgr; }
 
 // ---- owners of the synchronous HIP resources (host-only).  Each is move-only (a declared move makes the copies deleted),
 // empty when default-constructed, and releases what it holds in its destructor, ignoring the status.  Stream-ordered memory
@@ -52,6 +71,27 @@ private:
     void swap(DeviceBuf &o) { std::swap(p_, o.p_), std::swap(n_, o.n_); }
     T *p_ = nullptr;
     size_t n_ = 0;
+};
+
+// one counter on the device for the kernels that count mismatches: zero() on `st` before they are launched, read() after
+class DeviceCounter {
+public:
+    int zero(hipStream_t st)
+    {
+        if (int rc = d_.alloc(1, "hipMalloc(count)")) return rc;
+        IIV_HIP(hipMemsetAsync(d_, 0, sizeof(unsigned long long), st));
+        return IIV_OK;
+    }
+    int read(unsigned long long *out, hipStream_t st)   // synchronises `st`
+    {
+        IIV_HIP(hipMemcpyAsync(out, d_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        IIV_HIP(hipStreamSynchronize(st));
+        return IIV_OK;
+    }
+    operator unsigned long long *() const { return d_; }
+
+private:
+    DeviceBuf<unsigned long long> d_;
 };
 
 // the same from hipHostMalloc(flags): pinned / coherent host memory

@@ -574,27 +574,20 @@ int frames_to_memory_maps(int mode, const uint8_t palette_rgb[48], int n, const 
 {
     const IngestPalette P = make_palette(palette_rgb, dither);
     const int n_banks = mode == kDHGR ? 2 * n : n;
-    hipLaunchKernelGGL(ingest_holes_kernel, dim3((unsigned)(((size_t)n_banks * 64 + 255) / 256)), dim3(256), 0, st, n_banks, d_main,
-                       mode == kDHGR ? d_aux : (uint8_t *)nullptr);
-    int rc = hip_check(hipGetLastError(), "ingest_holes_kernel launch");
-    if (rc) return rc;
+    if (int rc = launch(ingest_holes_kernel, "ingest_holes_kernel launch", dim3((unsigned)(((size_t)n_banks * 64 + 255) / 256)), dim3(256), 0, st,
+                        n_banks, d_main, mode == kDHGR ? d_aux : (uint8_t *)nullptr))
+        return rc;
     if (dither == IIV_DITHER_DIFFUSION) {
         const dim3 grid((unsigned)((n + 3 * kDiffWaves - 1) / (3 * kDiffWaves)));
         // (IIV_EXP_DIFF_LDS_PAD: timing experiments only -- extra dynamic LDS per workgroup caps the waves resident per CU)
         static const int lds_pad = getenv("IIV_EXP_DIFF_LDS_PAD") ? atoi(getenv("IIV_EXP_DIFF_LDS_PAD")) : 0;
-        if (mode == kDHGR)
-            hipLaunchKernelGGL(ingest_diffusion_kernel<kDHGR>, grid, dim3(64 * kDiffWaves), (size_t)lds_pad, st, n, d_rgb, P, d_main, d_aux);
-        else
-            hipLaunchKernelGGL(ingest_diffusion_kernel<kHGR>, grid, dim3(64 * kDiffWaves), (size_t)lds_pad, st, n, d_rgb, P, d_main, d_aux);
-        return hip_check(hipGetLastError(), "ingest diffusion kernel launch");
+        return launch(by_mode(mode, ingest_diffusion_kernel<kDHGR>, ingest_diffusion_kernel<kHGR>), "ingest_diffusion_kernel launch", grid,
+                      dim3(64 * kDiffWaves), (size_t)lds_pad, st, n, d_rgb, P, d_main, d_aux);
     }
     const size_t total = (size_t)n * 3840;
     dim3 grid((unsigned)((total + 255) / 256));
-    if (mode == kDHGR)
-        hipLaunchKernelGGL(ingest_kernel<kDHGR>, grid, dim3(256), 0, st, n, d_rgb, P, d_main, d_aux);
-    else
-        hipLaunchKernelGGL(ingest_kernel<kHGR>, grid, dim3(256), 0, st, n, d_rgb, P, d_main, d_aux);
-    return hip_check(hipGetLastError(), "ingest_kernel launch");
+    return launch(by_mode(mode, ingest_kernel<kDHGR>, ingest_kernel<kHGR>), "ingest_kernel launch", grid, dim3(256), 0, st, n, d_rgb, P, d_main,
+                  d_aux);
 }
 
 }  // namespace iiv

@@ -247,8 +247,8 @@ int mono_frames(int n, const uint8_t *d_rgb, int dither, uint8_t *d_main, uint8_
     if (dither != IIV_DITHER_DIFFUSION) {
         const MonoDither P = make_dither(dither);
         const size_t total = (size_t)n * 192 * (G::W / 14);
-        hipLaunchKernelGGL(mono_ordered_kernel<MODE>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, n, d_rgb, P, d_main, d_aux);
-        return hip_check(hipGetLastError(), "mono_ordered_kernel launch");
+        return launch(mono_ordered_kernel<MODE>, "mono_ordered_kernel launch", dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, n,
+                      d_rgb, P, d_main, d_aux);
     }
     // A wave is a frame and one wave alone issues an instruction every four cycles, so a chunk should put two waves on
     // each of the 1024 SIMDs -- and its luma, written and read once, should still be in the 256 MiB Infinity Cache when
@@ -264,13 +264,12 @@ int mono_frames(int n, const uint8_t *d_rgb, int dither, uint8_t *d_main, uint8_
     for (int f0 = 0; f0 < n && !rc; f0 += chunk) {
         const int fn = n - f0 < chunk ? n - f0 : chunk;
         const size_t items = (size_t)fn * G::kGroups * 64;
-        hipLaunchKernelGGL(mono_luma_skew_kernel<MODE>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, fn,
-                           d_rgb + (size_t)f0 * G::kFrameBytes, skew);
-        rc = hip_check(hipGetLastError(), "mono_luma_skew_kernel launch");
+        rc = launch(mono_luma_skew_kernel<MODE>, "mono_luma_skew_kernel launch", dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, fn,
+                    d_rgb + (size_t)f0 * G::kFrameBytes, skew);
         if (rc) break;
-        hipLaunchKernelGGL(mono_diffusion_kernel<MODE>, dim3((unsigned)((fn + kMonoWaves - 1) / kMonoWaves)), dim3(64 * kMonoWaves), 0, st,
-                           fn, skew, d_main + (size_t)f0 * 8192, MODE == kDHGR ? d_aux + (size_t)f0 * 8192 : (uint8_t *)nullptr);
-        rc = hip_check(hipGetLastError(), "mono_diffusion_kernel launch");
+        rc = launch(mono_diffusion_kernel<MODE>, "mono_diffusion_kernel launch", dim3((unsigned)((fn + kMonoWaves - 1) / kMonoWaves)),
+                    dim3(64 * kMonoWaves), 0, st, fn, skew, d_main + (size_t)f0 * 8192,
+                    MODE == kDHGR ? d_aux + (size_t)f0 * 8192 : (uint8_t *)nullptr);
     }
     const int rc_free = hip_check(hipFreeAsync(skew, st), "hipFreeAsync(mono luma scratch)");
     return rc ? rc : rc_free;
@@ -290,10 +289,9 @@ extern "C" int iiv_frames_to_memory_maps_mono(int mode, int n_frames, const uint
     if (n_frames == 0) return IIV_OK;
     hipStream_t st = (hipStream_t)stream;
     const int n_banks = mode == IIV_DHGR ? 2 * n_frames : n_frames;
-    hipLaunchKernelGGL(iiv::mono_holes_kernel, dim3((unsigned)(((size_t)n_banks * 64 + 255) / 256)), dim3(256), 0, st, n_banks, d_main,
-                       mode == IIV_DHGR ? d_aux : (uint8_t *)nullptr);
-    const int rc = iiv::hip_check(hipGetLastError(), "mono_holes_kernel launch");
-    if (rc) return rc;
+    if (int rc = iiv::launch(iiv::mono_holes_kernel, "mono_holes_kernel launch", dim3((unsigned)(((size_t)n_banks * 64 + 255) / 256)), dim3(256),
+                             0, st, n_banks, d_main, mode == IIV_DHGR ? d_aux : (uint8_t *)nullptr))
+        return rc;
     return mode == IIV_DHGR ? iiv::mono_frames<iiv::kDHGR>(n_frames, d_rgb, dither, d_main, d_aux, st)
                             : iiv::mono_frames<iiv::kHGR>(n_frames, d_rgb, dither, d_main, d_aux, st);
 }

@@ -73,11 +73,8 @@ int render_rgb(int mode, const uint8_t palette_rgb[48], int n, const uint8_t *d_
     const RenderPalette P = make_render_palette(palette_rgb);
     const size_t n_runs = (size_t)n * kRenderRunsPerFrame;
     const dim3 grid(render_grid(n_runs));
-    if (mode == kDHGR)
-        hipLaunchKernelGGL(render_kernel<kDHGR>, grid, dim3(64 * kRenderWaves), 0, st, n_runs, d_main, d_aux, in_stride, P, d_rgb);
-    else
-        hipLaunchKernelGGL(render_kernel<kHGR>, grid, dim3(64 * kRenderWaves), 0, st, n_runs, d_main, d_aux, in_stride, P, d_rgb);
-    return hip_check(hipGetLastError(), "render_kernel launch");
+    return launch(by_mode(mode, render_kernel<kDHGR>, render_kernel<kHGR>), "render_kernel launch", grid, dim3(64 * kRenderWaves), 0, st, n_runs,
+                  d_main, d_aux, in_stride, P, d_rgb);
 }
 
 }  // namespace iiv

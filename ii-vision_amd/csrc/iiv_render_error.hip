@@ -139,15 +139,10 @@ int render_error(int mode, const uint8_t palette_rgb[48], int n, const uint8_t *
     const dim3 grid(render_grid(n_runs)), block(64 * kRenderWaves);
     unsigned long long *out = reinterpret_cast<unsigned long long *>(d_out);
     IIV_HIP(hipMemsetAsync(d_out, 0, (size_t)n * 72, st));
-    if (mode == kDHGR && ref_width == 560)
-        hipLaunchKernelGGL((render_error_kernel<kDHGR, 560>), grid, block, 0, st, n_runs, d_main, d_aux, in_stride, P, d_ref, out);
-    else if (mode == kDHGR)
-        hipLaunchKernelGGL((render_error_kernel<kDHGR, 280>), grid, block, 0, st, n_runs, d_main, d_aux, in_stride, P, d_ref, out);
-    else if (ref_width == 560)
-        hipLaunchKernelGGL((render_error_kernel<kHGR, 560>), grid, block, 0, st, n_runs, d_main, d_aux, in_stride, P, d_ref, out);
-    else
-        hipLaunchKernelGGL((render_error_kernel<kHGR, 280>), grid, block, 0, st, n_runs, d_main, d_aux, in_stride, P, d_ref, out);
-    return hip_check(hipGetLastError(), "render_error_kernel launch");
+    const bool wide = ref_width == 560;
+    const auto kernel = by_mode(mode, wide ? render_error_kernel<kDHGR, 560> : render_error_kernel<kDHGR, 280>,
+                                wide ? render_error_kernel<kHGR, 560> : render_error_kernel<kHGR, 280>);
+    return launch(kernel, "render_error_kernel launch", grid, block, 0, st, n_runs, d_main, d_aux, in_stride, P, d_ref, out);
 }
 
 }  // namespace iiv

@@ -262,13 +262,9 @@ int launch_h(const uint8_t *src, size_t src_fs, size_t src_rs, int frames, int r
         const int fn = frames - f0 < step ? frames - f0 : step;
         const uint8_t *s = src + (size_t)f0 * src_fs;
         uint8_t *d = dst + (size_t)f0 * dst_fs;
-        if (R == 2)
-            hipLaunchKernelGGL(resize_h_kernel<2>, dim3((unsigned)fn * bpf), dim3(threads), (size_t)2 * w_pad * 4, st, s, src_fs,
-                               src_rs, rows, w, W, t.bounds, t.k_taps, d, dst_fs, dst_rs);
-        else
-            hipLaunchKernelGGL(resize_h_kernel<1>, dim3((unsigned)fn * bpf), dim3(threads), (size_t)w_pad * 4, st, s, src_fs,
-                               src_rs, rows, w, W, t.bounds, t.k_taps, d, dst_fs, dst_rs);
-        if (int rc = hip_check(hipGetLastError(), "resize_h_kernel launch")) return rc;
+        if (int rc = launch(R == 2 ? resize_h_kernel<2> : resize_h_kernel<1>, "resize_h_kernel launch", dim3((unsigned)fn * bpf), dim3(threads),
+                            (size_t)R * w_pad * 4, st, s, src_fs, src_rs, rows, w, W, t.bounds, t.k_taps, d, dst_fs, dst_rs))
+            return rc;
     }
     return IIV_OK;
 }
@@ -281,9 +277,9 @@ int launch_v(const uint8_t *src, size_t src_fs, size_t src_rs, int frames, int r
     const int step = frames_per_launch(bpf, 256);
     for (int f0 = 0; f0 < frames; f0 += step) {
         const int fn = frames - f0 < step ? frames - f0 : step;
-        hipLaunchKernelGGL(resize_v_kernel, dim3((unsigned)fn * bpf), dim3(256), 0, st, src + (size_t)f0 * src_fs, src_fs, src_rs,
-                           row_bytes, H, bpr, t.bounds, t.k_rows, t.ksize, dst + (size_t)f0 * dst_fs, dst_fs, dst_rs);
-        if (int rc = hip_check(hipGetLastError(), "resize_v_kernel launch")) return rc;
+        if (int rc = launch(resize_v_kernel, "resize_v_kernel launch", dim3((unsigned)fn * bpf), dim3(256), 0, st, src + (size_t)f0 * src_fs,
+                            src_fs, src_rs, row_bytes, H, bpr, t.bounds, t.k_rows, t.ksize, dst + (size_t)f0 * dst_fs, dst_fs, dst_rs))
+            return rc;
     }
     return IIV_OK;
 }

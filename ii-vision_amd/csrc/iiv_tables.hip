@@ -374,15 +374,13 @@ int expand_narrow_tables(int mode, const NarrowTables &nt, const uint16_t *d_sto
                          hipStream_t st)
 {
     const size_t n = (size_t)num_offsets(mode) << (content_bits(mode) + masked_bits(mode));
-    DeviceBuf<unsigned long long> d_cnt;
-    if (int rc = d_cnt.alloc(1, "hipMalloc(count)")) return rc;
-    IIV_HIP(hipMemsetAsync(d_cnt, 0, 8, st));
+    DeviceCounter d_cnt;
+    if (int rc = d_cnt.zero(st)) return rc;
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (mode == kDHGR) hipLaunchKernelGGL(narrow_expand_kernel<kDHGR>, grid, dim3(256), 0, st, nt, d_store, d_out, d_cnt.get());
-    else hipLaunchKernelGGL(narrow_expand_kernel<kHGR>, grid, dim3(256), 0, st, nt, d_store, d_out, d_cnt.get());
-    if (int rc = hip_check(hipGetLastError(), "narrow_expand_kernel launch")) return rc;
-    IIV_HIP(hipMemcpyAsync(n_mismatch, d_cnt, 8, hipMemcpyDeviceToHost, st));
-    return hip_check(hipStreamSynchronize(st), "sync");
+    if (int rc = launch(by_mode(mode, narrow_expand_kernel<kDHGR>, narrow_expand_kernel<kHGR>), "narrow_expand_kernel launch", grid, dim3(256), 0,
+                        st, nt, d_store, d_out, d_cnt))
+        return rc;
+    return d_cnt.read(n_mismatch, st);
 }
 
 // d_strings / d_sub: build_strings; d_left: the u32 left half (build_split_tables); d_store: the dense store table the
@@ -395,11 +393,9 @@ int build_narrow_tables(int mode, const ulonglong2 *d_strings, const uint16_t *d
     const size_t n_fill = split_entries(mode, 0) + split_entries(mode, 1);
     DeviceBuf<uint8_t> buf;
     if (int rc = buf.alloc(total, "hipMalloc(narrow tables)")) return rc;
-    if (mode == kDHGR)
-        hipLaunchKernelGGL(narrow_fold_kernel<kDHGR>, dim3((unsigned)((n_fill + 255) / 256)), dim3(256), 0, st, d_strings, d_sub, d_left, buf.get());
-    else
-        hipLaunchKernelGGL(narrow_fold_kernel<kHGR>, dim3((unsigned)((n_fill + 255) / 256)), dim3(256), 0, st, d_strings, d_sub, d_left, buf.get());
-    if (int rc = hip_check(hipGetLastError(), "narrow_fold_kernel launch")) return rc;
+    if (int rc = launch(by_mode(mode, narrow_fold_kernel<kDHGR>, narrow_fold_kernel<kHGR>), "narrow_fold_kernel launch",
+                        dim3((unsigned)((n_fill + 255) / 256)), dim3(256), 0, st, d_strings, d_sub, d_left, buf))
+        return rc;
     NarrowTables nt{buf, mode == kDHGR ? narrow_right_off<kDHGR>() : narrow_right_off<kHGR>(), 0};
     unsigned long long bad = 0;
     if (int rc = expand_narrow_tables(mode, nt, d_store, nullptr, &bad, st)) return rc;
@@ -435,11 +431,8 @@ int transpose_split_tables(int mode, const uint32_t *d_left, const uint32_t *d_r
     const size_t n = mode == kDHGR ? split_left_entries<kDHGR>() + split_right_entries<kDHGR>()
                                    : split_left_entries<kHGR>() + split_right_entries<kHGR>();
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (mode == kDHGR)
-        hipLaunchKernelGGL(split_transpose_kernel<kDHGR>, grid, dim3(256), 0, st, d_left, d_right, d_left_t, d_right_t);
-    else
-        hipLaunchKernelGGL(split_transpose_kernel<kHGR>, grid, dim3(256), 0, st, d_left, d_right, d_left_t, d_right_t);
-    return hip_check(hipGetLastError(), "split_transpose_kernel launch");
+    return launch(by_mode(mode, split_transpose_kernel<kDHGR>, split_transpose_kernel<kHGR>), "split_transpose_kernel launch", grid, dim3(256),
+                  0, st, d_left, d_right, d_left_t, d_right_t);
 }
 
 // The narrow form with content innermost and two byte values per word, for the joint content choice's packed scoring
@@ -481,11 +474,8 @@ int build_joint_tables(int mode, const NarrowTables &nt, DeviceBuf<uint32_t> &d_
     if (int rc = d_jl.alloc(nl, "hipMalloc(joint left)")) return rc;
     if (int rc = d_jr.alloc(nr, "hipMalloc(joint right)")) return rc;
     const dim3 grid((unsigned)((nl + nr + 255) / 256));
-    if (mode == kDHGR)
-        hipLaunchKernelGGL(joint_pack_kernel<kDHGR>, grid, dim3(256), 0, st, nt.base, nt.right_off, d_jl.get(), d_jr.get());
-    else
-        hipLaunchKernelGGL(joint_pack_kernel<kHGR>, grid, dim3(256), 0, st, nt.base, nt.right_off, d_jl.get(), d_jr.get());
-    return hip_check(hipGetLastError(), "joint_pack_kernel launch");
+    return launch(by_mode(mode, joint_pack_kernel<kDHGR>, joint_pack_kernel<kHGR>), "joint_pack_kernel launch", grid, dim3(256), 0, st,
+                  nt.base, nt.right_off, d_jl, d_jr);
 }
 
 // The halves of the diff-weight table (iiv_stream.h): the same recurrence between two arbitrary
@@ -575,8 +565,7 @@ static void substitute_costs(const int32_t dm[256], uint16_t sub[256])
 template <int MODE> static int pixel_strings_impl(uint32_t *d_dots, uint8_t *d_pixels, ulonglong2 *d_strings, hipStream_t st)
 {
     int n = ModeTraits<MODE>::kOffsets << ModeTraits<MODE>::kBits;
-    hipLaunchKernelGGL(pixel_kernel<MODE>, dim3((n + 255) / 256), dim3(256), 0, st, d_dots, d_pixels, d_strings);
-    return hip_check(hipGetLastError(), "pixel_kernel launch");
+    return launch(pixel_kernel<MODE>, "pixel_kernel launch", dim3((n + 255) / 256), dim3(256), 0, st, d_dots, d_pixels, d_strings);
 }
 
 int pixel_strings(int mode, uint32_t *d_dots, uint8_t *d_pixels, ulonglong2 *d_strings, hipStream_t st)
@@ -608,8 +597,7 @@ __global__ __launch_bounds__(256) void hgr_dot_lut_check_kernel(const uint32_t *
 int build_hgr_dot_lut(DeviceBuf<uint32_t> &d_out, hipStream_t st)
 {
     if (int rc = d_out.alloc(kHgrDotLutEntries, "hipMalloc(HGR dot lookups)")) return rc;
-    hipLaunchKernelGGL(hgr_dot_lut_kernel, dim3((kHgrDotLutEntries + 63) / 64), dim3(64), 0, st, d_out.get());
-    return hip_check(hipGetLastError(), "hgr_dot_lut_kernel launch");
+    return launch(hgr_dot_lut_kernel, "hgr_dot_lut_kernel launch", dim3((kHgrDotLutEntries + 63) / 64), dim3(64), 0, st, d_out);
 }
 
 // ------------------------------------------------------------------ diff weights as a sum of local terms (the prologue's default)
@@ -668,8 +656,7 @@ int build_dw_piece_table(int mode, const uint16_t *d_sub, DeviceBuf<uint32_t> &d
     const size_t words = mode == kDHGR ? (size_t)n : (size_t)kHgrPieceWords;
     if (int rc = d_out.alloc(words, "hipMalloc(diff-weight pieces)")) return rc;
     IIV_HIP(hipMemsetAsync(d_out, 0, words * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(dw_piece_kernel, dim3(n / 256), dim3(256), 0, st, mode, d_sub, d_out.get());
-    return hip_check(hipGetLastError(), "dw_piece_kernel launch");
+    return launch(dw_piece_kernel, "dw_piece_kernel launch", dim3(n / 256), dim3(256), 0, st, mode, d_sub, d_out);
 }
 
 // every entry of the full symmetric DHGR table against the sum of its five pair terms, read the way the prologue reads them
@@ -708,23 +695,25 @@ int check_dw_piece_table(int mode, const int32_t dm[256], const uint16_t *d_tabl
     uint16_t sub[256];
     DeviceBuf<uint16_t> d_sub;
     DeviceBuf<uint32_t> d_p, d_dots;
-    DeviceBuf<unsigned long long> d_cnt;
+    DeviceCounter d_cnt;
     substitute_costs(dm, sub);
     if (int rc = d_sub.alloc(256, "hipMalloc(sub)")) return rc;
-    if (int rc = hip_check(hipMemcpy(d_sub, sub, sizeof(sub), hipMemcpyHostToDevice), "copy sub")) return rc;
-    if (int rc = d_cnt.alloc(1, "hipMalloc(count)")) return rc;
-    IIV_HIP(hipMemsetAsync(d_cnt, 0, 8, st));
+    IIV_HIP(hipMemcpy(d_sub, sub, sizeof(sub), hipMemcpyHostToDevice));
+    if (int rc = d_cnt.zero(st)) return rc;
     if (int rc = build_dw_piece_table(mode, d_sub, d_p, st)) return rc;
     if (mode == kDHGR) {
-        hipLaunchKernelGGL(dw_piece_check_kernel, dim3((unsigned)(((size_t)4 << 26) / 256)), dim3(256), 0, st, d_p.get(), d_table, d_cnt.get());
+        if (int rc = launch(dw_piece_check_kernel, "dw_piece_check_kernel launch", dim3((unsigned)(((size_t)4 << 26) / 256)), dim3(256), 0, st,
+                            d_p, d_table, d_cnt))
+            return rc;
     } else {
         if (int rc = build_hgr_dot_lut(d_dots, st)) return rc;
-        hipLaunchKernelGGL(hgr_dot_lut_check_kernel, dim3((2 << 14) / 256), dim3(256), 0, st, d_dots.get(), d_cnt.get());
-        hipLaunchKernelGGL(dw_piece_check_hgr_kernel, dim3((unsigned)(((size_t)2 << 28) / 256)), dim3(256), 0, st, d_p.get(), d_dots.get(), d_table, d_cnt.get());
+        if (int rc = launch(hgr_dot_lut_check_kernel, "hgr_dot_lut_check_kernel launch", dim3((2 << 14) / 256), dim3(256), 0, st, d_dots, d_cnt))
+            return rc;
+        if (int rc = launch(dw_piece_check_hgr_kernel, "dw_piece_check_hgr_kernel launch", dim3((unsigned)(((size_t)2 << 28) / 256)), dim3(256), 0,
+                            st, d_p, d_dots, d_table, d_cnt))
+            return rc;
     }
-    if (int rc = hip_check(hipGetLastError(), "dw_piece_check_kernel launch")) return rc;
-    if (int rc = hip_check(hipMemcpyAsync(mismatches, d_cnt, 8, hipMemcpyDeviceToHost, st), "copy count")) return rc;
-    return hip_check(hipStreamSynchronize(st), "sync");   // (the scratch is freed on return)
+    return d_cnt.read(mismatches, st);   // (synchronises `st`; the scratch is freed on return)
 }
 
 // the colour strings and substitute costs of dm, what every builder below starts from (the strings are enqueued on `st`)
@@ -744,8 +733,7 @@ int build_strings(int mode, const int32_t dm[256], DeviceBuf<ulonglong2> &d_stri
 {
     DeviceBuf<ulonglong2> strings;
     DeviceBuf<uint16_t> sub;
-    int rc = prepare_strings(mode, dm, strings, sub, st);
-    if (rc) return rc;
+    if (int rc = prepare_strings(mode, dm, strings, sub, st)) return rc;
     IIV_HIP(hipStreamSynchronize(st));
     d_strings = std::move(strings);
     d_sub = std::move(sub);
@@ -756,16 +744,12 @@ int build_table(int mode, const int32_t dm[256], uint16_t *d_out, int symmetric,
 {
     DeviceBuf<ulonglong2> strings;
     DeviceBuf<uint16_t> sub;
-    int rc = prepare_strings(mode, dm, strings, sub, st);
-    if (rc) return rc;
+    if (int rc = prepare_strings(mode, dm, strings, sub, st)) return rc;
     int bits = masked_bits(mode);
     dim3 grid((1u << bits) / (256 * kTableColsPerThread), (1u << bits) / kTableRowsPerBlock, num_offsets(mode));
-    if (mode == kDHGR)
-        hipLaunchKernelGGL(table_kernel<kDHGR>, grid, dim3(256), 0, st, strings.get(), sub.get(), d_out, symmetric);
-    else
-        hipLaunchKernelGGL(table_kernel<kHGR>, grid, dim3(256), 0, st, strings.get(), sub.get(), d_out, symmetric);
-    rc = hip_check(hipGetLastError(), "table_kernel launch");
-    if (rc) return rc;
+    if (int rc = launch(by_mode(mode, table_kernel<kDHGR>, table_kernel<kHGR>), "table_kernel launch", grid, dim3(256), 0, st, strings, sub,
+                        d_out, symmetric))
+        return rc;
     IIV_HIP(hipStreamSynchronize(st));  // scratch is freed on return
     return IIV_OK;
 }
@@ -774,16 +758,12 @@ int build_store_table(int mode, const int32_t dm[256], uint16_t *d_out, hipStrea
 {
     DeviceBuf<ulonglong2> strings;
     DeviceBuf<uint16_t> sub;
-    int rc = prepare_strings(mode, dm, strings, sub, st);
-    if (rc) return rc;
+    if (int rc = prepare_strings(mode, dm, strings, sub, st)) return rc;
     size_t n = (size_t)num_offsets(mode) << (content_bits(mode) + masked_bits(mode));
     dim3 grid((unsigned)((n + 255) / 256));
-    if (mode == kDHGR)
-        hipLaunchKernelGGL(store_kernel<kDHGR>, grid, dim3(256), 0, st, strings.get(), sub.get(), d_out);
-    else
-        hipLaunchKernelGGL(store_kernel<kHGR>, grid, dim3(256), 0, st, strings.get(), sub.get(), d_out);
-    rc = hip_check(hipGetLastError(), "store_kernel launch");
-    if (rc) return rc;
+    if (int rc = launch(by_mode(mode, store_kernel<kDHGR>, store_kernel<kHGR>), "store_kernel launch", grid, dim3(256), 0, st, strings, sub,
+                        d_out))
+        return rc;
     IIV_HIP(hipStreamSynchronize(st));
     return IIV_OK;
 }
@@ -795,11 +775,8 @@ int build_split_tables(int mode, const ulonglong2 *d_strings, const uint16_t *d_
     const size_t n = mode == kDHGR ? split_left_entries<kDHGR>() + split_right_entries<kDHGR>()
                                    : split_left_entries<kHGR>() + split_right_entries<kHGR>();
     dim3 grid((unsigned)((n + 255) / 256));
-    if (mode == kDHGR)
-        hipLaunchKernelGGL(split_kernel<kDHGR>, grid, dim3(256), 0, st, d_strings, d_sub, d_left, d_right);
-    else
-        hipLaunchKernelGGL(split_kernel<kHGR>, grid, dim3(256), 0, st, d_strings, d_sub, d_left, d_right);
-    return hip_check(hipGetLastError(), "split_kernel launch");
+    return launch(by_mode(mode, split_kernel<kDHGR>, split_kernel<kHGR>), "split_kernel launch", grid, dim3(256), 0, st, d_strings, d_sub,
+                  d_left, d_right);
 }
 
 size_t split_dw_entries(int mode, int right)
@@ -813,11 +790,8 @@ int build_split_dw_tables(int mode, const ulonglong2 *d_strings, const uint16_t 
 {
     const size_t n = split_dw_entries(mode, 0) + split_dw_entries(mode, 1);
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (mode == kDHGR)
-        hipLaunchKernelGGL(split_dw_kernel<kDHGR>, grid, dim3(256), 0, st, d_strings, d_sub, d_left, d_right);
-    else
-        hipLaunchKernelGGL(split_dw_kernel<kHGR>, grid, dim3(256), 0, st, d_strings, d_sub, d_left, d_right);
-    return hip_check(hipGetLastError(), "split_dw_kernel launch");
+    return launch(by_mode(mode, split_dw_kernel<kDHGR>, split_dw_kernel<kHGR>), "split_dw_kernel launch", grid, dim3(256), 0, st, d_strings,
+                  d_sub, d_left, d_right);
 }
 
 // every entry of the full symmetric table against the combination of the two halves
@@ -845,24 +819,19 @@ int check_split_dw_table(int mode, const int32_t dm[256], const uint16_t *d_tabl
 {
     DeviceBuf<ulonglong2> strings;
     DeviceBuf<uint16_t> sub;
-    int rc = prepare_strings(mode, dm, strings, sub, st);
-    if (rc) return rc;
+    if (int rc = prepare_strings(mode, dm, strings, sub, st)) return rc;
     DeviceBuf<uint32_t> d_l, d_r;
-    DeviceBuf<unsigned long long> d_cnt;
-    if ((rc = d_l.alloc(split_dw_entries(mode, 0), "hipMalloc(dw left)"))) return rc;
-    if ((rc = d_r.alloc(split_dw_entries(mode, 1), "hipMalloc(dw right)"))) return rc;
-    if ((rc = d_cnt.alloc(1, "hipMalloc(count)"))) return rc;
-    IIV_HIP(hipMemsetAsync(d_cnt, 0, 8, st));
-    if ((rc = build_split_dw_tables(mode, strings.get(), sub.get(), d_l, d_r, st))) return rc;
+    DeviceCounter d_cnt;
+    if (int rc = d_l.alloc(split_dw_entries(mode, 0), "hipMalloc(dw left)")) return rc;
+    if (int rc = d_r.alloc(split_dw_entries(mode, 1), "hipMalloc(dw right)")) return rc;
+    if (int rc = d_cnt.zero(st)) return rc;
+    if (int rc = build_split_dw_tables(mode, strings, sub, d_l, d_r, st)) return rc;
     const size_t n = (size_t)num_offsets(mode) << (2 * masked_bits(mode));
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (mode == kDHGR)
-        hipLaunchKernelGGL(split_dw_check_kernel<kDHGR>, grid, dim3(256), 0, st, d_l.get(), d_r.get(), d_table, d_cnt.get());
-    else
-        hipLaunchKernelGGL(split_dw_check_kernel<kHGR>, grid, dim3(256), 0, st, d_l.get(), d_r.get(), d_table, d_cnt.get());
-    if ((rc = hip_check(hipGetLastError(), "split_dw_check_kernel launch"))) return rc;
-    if ((rc = hip_check(hipMemcpyAsync(mismatches, d_cnt, 8, hipMemcpyDeviceToHost, st), "copy count"))) return rc;
-    return hip_check(hipStreamSynchronize(st), "sync");   // (the scratch is freed on return)
+    if (int rc = launch(by_mode(mode, split_dw_check_kernel<kDHGR>, split_dw_check_kernel<kHGR>), "split_dw_check_kernel launch", grid,
+                        dim3(256), 0, st, d_l, d_r, d_table, d_cnt))
+        return rc;
+    return d_cnt.read(mismatches, st);   // (synchronises `st`; the scratch is freed on return)
 }
 
 size_t split_entries(int mode, int right)
@@ -891,11 +860,8 @@ int build_split_store_table(int mode, const int32_t dm[256], uint32_t *d_left, u
     if (!rc && d_expanded) {
         size_t n = (size_t)num_offsets(mode) << (content_bits(mode) + masked_bits(mode));
         dim3 grid((unsigned)((n + 255) / 256));
-        if (mode == kDHGR)
-            hipLaunchKernelGGL(split_expand_kernel<kDHGR>, grid, dim3(256), 0, st, d_left, d_right, d_expanded);
-        else
-            hipLaunchKernelGGL(split_expand_kernel<kHGR>, grid, dim3(256), 0, st, d_left, d_right, d_expanded);
-        rc = hip_check(hipGetLastError(), "split_expand_kernel launch");
+        rc = launch(by_mode(mode, split_expand_kernel<kDHGR>, split_expand_kernel<kHGR>), "split_expand_kernel launch", grid, dim3(256), 0, st,
+                    d_left, d_right, d_expanded);
     }
     hipError_t he = hipStreamSynchronize(st);  // scratch is freed on return
     if (rc) return rc;
@@ -909,15 +875,14 @@ int build_narrow_store_table(int mode, const int32_t dm[256], const uint16_t *d_
 {
     DeviceBuf<ulonglong2> strings;
     DeviceBuf<uint16_t> sub;
-    int rc = prepare_strings(mode, dm, strings, sub, st);
-    if (rc) return rc;
+    if (int rc = prepare_strings(mode, dm, strings, sub, st)) return rc;
     DeviceBuf<uint32_t> d_l, d_r;
     DeviceBuf<uint8_t> nt_storage;
     NarrowTables nt{};
-    if ((rc = d_l.alloc(split_entries(mode, 0), "hipMalloc(split left)"))) return rc;
-    if ((rc = d_r.alloc(split_entries(mode, 1), "hipMalloc(split right)"))) return rc;
-    if ((rc = build_split_tables(mode, strings.get(), sub.get(), d_l, d_r, st))) return rc;
-    if ((rc = build_narrow_tables(mode, strings.get(), sub.get(), d_l, d_store, &nt, nt_storage, st))) return rc;
+    if (int rc = d_l.alloc(split_entries(mode, 0), "hipMalloc(split left)")) return rc;
+    if (int rc = d_r.alloc(split_entries(mode, 1), "hipMalloc(split right)")) return rc;
+    if (int rc = build_split_tables(mode, strings, sub, d_l, d_r, st)) return rc;
+    if (int rc = build_narrow_tables(mode, strings, sub, d_l, d_store, &nt, nt_storage, st)) return rc;
     return expand_narrow_tables(mode, nt, d_store, d_expanded, n_mismatch, st);   // (synchronises `st`)
 }
 
@@ -925,18 +890,15 @@ int symmetrise_table(int mode, uint16_t *d_table, hipStream_t st)
 {
     const size_t n = (size_t)num_offsets(mode) << (2 * masked_bits(mode));
     dim3 grid((unsigned)((n + 255) / 256));
-    if (mode == kDHGR) hipLaunchKernelGGL(symmetrise_kernel<kDHGR>, grid, dim3(256), 0, st, d_table);
-    else hipLaunchKernelGGL(symmetrise_kernel<kHGR>, grid, dim3(256), 0, st, d_table);
-    return hip_check(hipGetLastError(), "symmetrise_kernel launch");
+    return launch(by_mode(mode, symmetrise_kernel<kDHGR>, symmetrise_kernel<kHGR>), "symmetrise_kernel launch", grid, dim3(256), 0, st, d_table);
 }
 
 int store_table_from_table(int mode, const uint16_t *d_table, uint16_t *d_store, hipStream_t st)
 {
     const size_t n = (size_t)num_offsets(mode) << (content_bits(mode) + masked_bits(mode));
     dim3 grid((unsigned)((n + 255) / 256));
-    if (mode == kDHGR) hipLaunchKernelGGL(store_from_table_kernel<kDHGR>, grid, dim3(256), 0, st, d_table, d_store);
-    else hipLaunchKernelGGL(store_from_table_kernel<kHGR>, grid, dim3(256), 0, st, d_table, d_store);
-    return hip_check(hipGetLastError(), "store_from_table_kernel launch");
+    return launch(by_mode(mode, store_from_table_kernel<kDHGR>, store_from_table_kernel<kHGR>), "store_from_table_kernel launch", grid,
+                  dim3(256), 0, st, d_table, d_store);
 }
 
 int delta_e_pairs(int n, const double *lab1, const double *lab2, double *out, hipStream_t st)
@@ -946,8 +908,8 @@ int delta_e_pairs(int n, const double *lab1, const double *lab2, double *out, hi
     double *d = buf;
     if (int rc = hip_check(hipMemcpyAsync(d, lab1, (size_t)n * 24, hipMemcpyHostToDevice, st), "copy lab1")) return rc;
     if (int rc = hip_check(hipMemcpyAsync(d + 3 * (size_t)n, lab2, (size_t)n * 24, hipMemcpyHostToDevice, st), "copy lab2")) return rc;
-    hipLaunchKernelGGL(delta_e_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, d, d + 3 * (size_t)n, d + 6 * (size_t)n);
-    if (int rc = hip_check(hipGetLastError(), "delta_e_kernel launch")) return rc;
+    if (int rc = launch(delta_e_kernel, "delta_e_kernel launch", dim3((n + 63) / 64), dim3(64), 0, st, n, d, d + 3 * (size_t)n, d + 6 * (size_t)n))
+        return rc;
     if (int rc = hip_check(hipMemcpyAsync(out, d + 6 * (size_t)n, (size_t)n * 8, hipMemcpyDeviceToHost, st), "copy out")) return rc;
     return hip_check(hipStreamSynchronize(st), "sync");
 }
@@ -961,8 +923,7 @@ int cie2000_matrix(const uint8_t rgb[48], double out_f[256], int32_t out_i[256],
     if (int rc = d_f.alloc(256, "hipMalloc(delta-E)")) return rc;
     if (int rc = d_i.alloc(256, "hipMalloc(delta-E, int)")) return rc;
     if (int rc = hip_check(hipMemcpyAsync(d_rgb, rgb, 48, hipMemcpyHostToDevice, st), "copy rgb")) return rc;
-    hipLaunchKernelGGL(cie2000_kernel, dim3(1), dim3(256), 0, st, d_rgb.get(), d_f.get(), d_i.get());
-    if (int rc = hip_check(hipGetLastError(), "cie2000_kernel launch")) return rc;
+    if (int rc = launch(cie2000_kernel, "cie2000_kernel launch", dim3(1), dim3(256), 0, st, d_rgb, d_f, d_i)) return rc;
     double f[256];
     int32_t iv[256];
     if (int rc = hip_check(hipMemcpyAsync(f, d_f, sizeof(f), hipMemcpyDeviceToHost, st), "copy f")) return rc;
