@@ -126,3 +126,13 @@ def replay(stream, tick_addr, ack_addr, terminate_addr, first, every, n, init=No
             k += 1
         out[j] = mem
     return out[:, 0].copy(), out[:, 1].copy()
+
+
+def random_ops(rng, n, pages=(32, 64), offsets=None):
+    """n opcodes of random bytes on pages[0] .. pages[1] - 1 (offsets: drawn from these only), and their tick bytes"""
+    ops = rng.integers(0, 256, (n, 6), dtype=np.uint8)
+    ops[:, 0] = rng.integers(pages[0], pages[1], n)
+    if offsets is not None:
+        ops[:, 2:] = rng.choice(np.asarray(offsets, dtype=np.uint8), (n, 4))
+    ticks = (rng.integers(0, 32, n) * 2 + 4).astype(np.uint8)
+    return ops, ticks

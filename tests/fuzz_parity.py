@@ -16,6 +16,7 @@ import torch  # noqa: E402
 import oracle as O  # noqa: E402
 import _iiv_native as native  # noqa: E402
 import stream_batch  # noqa: E402
+import encode_harness  # noqa: E402
 
 rounds = int(os.environ.get("IIV_FUZZ_ROUNDS", sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].isdigit() else 12))
 rng = np.random.default_rng(int(os.environ.get("IIV_FUZZ_SEED", "2026")))
@@ -72,16 +73,14 @@ for rnd in range(rounds):
         # one round in five: a real fourth offset per opcode (IIV_OPT_FOURTH_OFFSET), against the oracle's flag -- also together
         # with the joint choice (round 6)
         fourth = bool(rng.random() < 0.2)
-        enc = native.Encoder(mode, dtab[key][0], dtab[key][1], n, dm=dms[pal])
-        enc.set_content_choice("split" if joint and rng.random() < 0.3 else joint)   # (both implementations of the joint choice)
-        enc.set_fourth_offset(fourth)
-        enc.set_diff_weights_mode(recurrence)
-        enc.set_greedy_kernel(wave)
-        enc.set_prefix_sort(prefix)
+        enc = encode_harness.make_encoder(native, (dtab[key][0], dtab[key][1], dms[pal]), mode, n_streams=n, dw=recurrence, kernel=wave,
+                                          prefix=prefix, fourth=fourth,
+                                          joint="split" if joint and rng.random() < 0.3 else joint)   # (both implementations of the joint choice)
         seeds = [(int(rng.integers(1 << 20)), int(rng.integers(1 << 20))) for _ in range(n)]
-        for i, (sp, sn) in enumerate(seeds):
-            enc.set_state(native.STATE_RNG_PY, O.mt_seed_py(sp).state_words(), i)
-            enc.set_state(native.STATE_RNG_NP, O.mt_seed_np(sn).state_words(), i)
+        for i, (sp, sn) in enumerate(seeds):      # (one set_state per stream, on purpose: that binding path is fuzzed here too)
+            py, npw = encode_harness.seed_states(O, sp, sn)
+            enc.set_state(native.STATE_RNG_PY, py, i)
+            enc.set_state(native.STATE_RNG_NP, npw, i)
         # one round in four (of the short ones): every stream its own schedule (iiv_encode_streams: streams on different banks
         # in the same launch round, streams that idle while others still work, a stream with nothing to do at all)
         per_stream = bool(not marathon and not joint and rng.random() < 0.25)

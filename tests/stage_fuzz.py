@@ -62,6 +62,7 @@ for _p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "ii-vision_amd
 import a2m_model  # noqa: E402
 import audio_model  # noqa: E402
 import bitmap_model  # noqa: E402
+import device_guards  # noqa: E402
 import diffusion_model  # noqa: E402
 import ingest_model  # noqa: E402
 import mono_model  # noqa: E402
@@ -124,15 +125,11 @@ def _sync():
 
 
 def _guarded(n_bytes, lead, trail):
-    """a device buffer of GUARD bytes and the view of n_bytes that starts `lead` bytes into it"""
-    import torch
-    buf = torch.full((lead + n_bytes + trail,), GUARD, dtype=torch.uint8, device="cuda")
-    return buf, buf[lead:lead + n_bytes]
+    return device_guards.guarded(n_bytes, lead, trail, GUARD)
 
 
 def _guards_kept(case, what, buf, lead, n_bytes):
-    b = buf.cpu().numpy()
-    _require((b[:lead] == GUARD).all() and (b[lead + n_bytes:] == GUARD).all(), case, "%s: bytes outside the slice were written" % what)
+    _require(device_guards.guards_kept(buf, lead, n_bytes, GUARD), case, "%s: bytes outside the slice were written" % what)
 
 
 def _palette(name):

@@ -5,6 +5,9 @@ import ctypes as C
 
 import numpy as np
 
+import encode_harness
+from encode_harness import next_draws
+
 HGR, DHGR = 0, 1
 
 
@@ -25,17 +28,6 @@ def maps(rng, n, mode):
     return m
 
 
-def seed_words(O, seeds):
-    return (np.stack([O.mt_seed_py(a).state_words() for a, _ in seeds]), np.stack([O.mt_seed_np(b).state_words() for _, b in seeds]))
-
-
-def next_draws(O, words, n, high):
-    m = O.MT()
-    m.set_state_words(words)
-    f = O.lib().orc_py_getrandbits8 if high else O.lib().orc_np_randint256
-    return [f(C.byref(m)) for _ in range(n)]
-
-
 def frames(mode, n_streams, nframes, seed):
     """(main, aux) (n_streams, nframes, 32, 256), coherent from frame to frame"""
     rng = np.random.default_rng(seed)
@@ -53,21 +45,12 @@ class Enc:
     """An encoder of n seeded streams with its oracle twins, and the probe's pieces around it."""
 
     def __init__(self, native, O, device_tables, oracle_tables, mode, n, seed0, kernel=None, joint=False, fourth=False, lds_pad=0):
-        t, s = device_tables.get(mode, 5)
         self.native, self.O, self.mode, self.n = native, O, mode, n
-        self.enc = native.Encoder(mode, t, s, n, dm=device_tables.dm[(mode, 5)])
-        if kernel is not None:
-            self.enc.set_greedy_kernel(kernel)
-        if joint:
-            self.enc.set_content_choice(True)
-        if fourth:
-            self.enc.set_fourth_offset(True)
+        self.seeds = [(seed0 + i, seed0 + 100 + i) for i in range(n)]
+        named = {k: v for k, v in (("kernel", kernel), ("joint", joint or None), ("fourth", fourth or None)) if v is not None}
+        self.enc = encode_harness.make_encoder(native, device_tables, mode, 5, n, rng=self.seeds, O=O, **named)
         if lds_pad:
             self.enc.set_greedy_lds_pad(lds_pad)
-        self.seeds = [(seed0 + i, seed0 + 100 + i) for i in range(n)]
-        py, npw = seed_words(O, self.seeds)
-        self.enc.set_state_all(native.STATE_RNG_PY, py)
-        self.enc.set_state_all(native.STATE_RNG_NP, npw)
         self.videos = [O.Video(mode, oracle_tables.get(mode, 5), seed_py=a, seed_np=b) for a, b in self.seeds]
         for v in self.videos:
             v.set_joint(joint)

@@ -39,15 +39,6 @@ def _model_args(addr):
     return addr.tick, addr.ack, addr.terminate
 
 
-def _random_ops(rng, n, pages=(32, 64), offsets=None):
-    ops = rng.integers(0, 256, (n, 6), dtype=np.uint8)
-    ops[:, 0] = rng.integers(pages[0], pages[1], n)
-    if offsets is not None:
-        ops[:, 2:] = rng.choice(np.asarray(offsets, dtype=np.uint8), (n, 4))
-    ticks = (rng.integers(0, 32, n) * 2 + 4).astype(np.uint8)
-    return ops, ticks
-
-
 def _emit(mode, ops, ticks, addr):
     import torch
     import a2m
@@ -110,7 +101,7 @@ def test_collisions_keep_stream_order(reader, addr):
     """5 000 opcodes on one page whose offsets come from three values: every byte is hit thousands of times and most opcodes
     name an offset more than once -- the shape at which a store that is not ordered goes wrong"""
     rng = np.random.default_rng(3)
-    ops, ticks = _random_ops(rng, 5000, pages=(40, 41), offsets=(7, 8, 200))
+    ops, ticks = M.random_ops(rng, 5000, pages=(40, 41), offsets=(7, 8, 200))
     for mode in (0, 1):
         stream = _emit(mode, ops, ticks, addr)
         main, aux = (t.cpu().numpy()[0] for t in reader.replay([stream], first=100, every=100, n=50))
@@ -121,7 +112,7 @@ def test_collisions_keep_stream_order(reader, addr):
 
 def test_replay_across_many_folds_and_acks(reader, addr):
     rng = np.random.default_rng(4)
-    ops, ticks = _random_ops(rng, 100000)
+    ops, ticks = M.random_ops(rng, 100000)
     stream = _emit(1, ops, ticks, addr)
     assert len(M._acks_before(100000)) == 342 and 100000 > 24 * 4096   # ACKs after opcode 290 + 292 i; two dozen folds
     info = reader.scan([stream])

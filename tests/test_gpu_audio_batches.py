@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import audio_model as M
-from test_gpu_audio import _check_ticks, _signal
+from audio_model import check_ticks as _check_ticks, signal as _signal
 
 pytestmark = pytest.mark.gpu
 

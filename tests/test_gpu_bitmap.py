@@ -3,6 +3,8 @@
 import numpy as np
 import pytest
 
+from device_guards import ok
+
 pytestmark = pytest.mark.gpu
 
 
@@ -99,10 +101,6 @@ def _guards_kept(buf, view, lead=3):
     return bool((b[:lead] == fill).all() and (b[lead + view.numel():] == fill).all())
 
 
-def _ok(native, rc):
-    native.check(rc)
-
-
 @pytest.fixture(scope="module")
 def screens():
     """33 + 33 all-bit screens, every one different (bitmap_model.random_screens; its conditions are asserted on the CPU)"""
@@ -141,7 +139,7 @@ def test_pack_at_the_least_alignments_in_guarded_buffers(native, screens, packed
     abuf, aview = _bytes_at(aux, lead_aux)
     assert mview.data_ptr() % 4 == lead_main and aview.data_ptr() % 4 == lead_aux          # one byte off, and three
     obuf, oview = _guarded_words(n * 4096, torch.int64)
-    _ok(native, native.lib().iiv_pack(mode, n, native.dptr(mview), native.dptr(aview), native.dptr(oview), native.stream_ptr()))
+    ok(native, native.lib().iiv_pack(mode, n, native.dptr(mview), native.dptr(aview), native.dptr(oview), native.stream_ptr()))
     torch.cuda.current_stream().synchronize()
     assert np.array_equal(oview.cpu().numpy().view(np.uint64).reshape(n, 32, 128), packed[mode][5:5 + n])
     assert _guards_kept(obuf, oview)
@@ -168,7 +166,7 @@ def test_hgr_pack_does_not_read_aux(native, screens, packed):
     outs = []
     for aux in (None, junk):
         obuf, oview = _guarded_words(2 * 4096, torch.int64)
-        _ok(native, native.lib().iiv_pack(0, 2, native.dptr(main), native.dptr(aux), native.dptr(oview), native.stream_ptr()))
+        ok(native, native.lib().iiv_pack(0, 2, native.dptr(main), native.dptr(aux), native.dptr(oview), native.stream_ptr()))
         torch.cuda.current_stream().synchronize()
         assert _guards_kept(obuf, oview)
         outs.append(oview.cpu().numpy().view(np.uint64).reshape(2, 32, 128))
@@ -215,7 +213,7 @@ def test_diff_weights_equal_and_unequal_windows_at_the_page_edges(native, oracle
     d_src, d_tgt = _dev(src), _dev(tgt)
     for ia in _banks(mode):
         obuf, oview = _guarded_words(8192, torch.int32)
-        _ok(native, native.lib().iiv_diff_weights(mode, native.dptr(table), 1, native.dptr(d_src), native.dptr(d_tgt), ia,
+        ok(native, native.lib().iiv_diff_weights(mode, native.dptr(table), 1, native.dptr(d_src), native.dptr(d_tgt), ia,
                                                   native.dptr(oview), native.stream_ptr()))
         torch.cuda.current_stream().synchronize()
         got = oview.cpu().numpy().reshape(32, 256)
@@ -301,9 +299,9 @@ def test_refusals_write_nothing(native, device_tables, packed, mode):
     assert (main == 0x33).all() and (aux == 0x44).all() and not rows.any()
     assert np.array_equal(src.cpu().numpy().view(np.uint64), packed[mode][:2]) and np.array_equal(tgt.cpu().numpy().view(np.uint64), packed[mode][2:4])
     # and the same arguments, accepted, fill exactly the slices
-    _ok(native, L.iiv_pack(mode, 2, p(main), p(aux), p(pout), st))
-    _ok(native, L.iiv_diff_weights(mode, p(table), 2, p(src), p(tgt), ia, p(wout), st))
-    _ok(native, L.iiv_compute_delta_pages(mode, p(table), 2, p(tgt), p(pages), p(contents), p(rows), ia, p(dout), st))
+    ok(native, L.iiv_pack(mode, 2, p(main), p(aux), p(pout), st))
+    ok(native, L.iiv_diff_weights(mode, p(table), 2, p(src), p(tgt), ia, p(wout), st))
+    ok(native, L.iiv_compute_delta_pages(mode, p(table), 2, p(tgt), p(pages), p(contents), p(rows), ia, p(dout), st))
     torch.cuda.synchronize()
     assert _guards_kept(pbuf, pout) and _guards_kept(wbuf, wout) and _guards_kept(dbuf, dout)
     assert (pout != GUARD64).all() and (wout != GUARD32).all() and (dout != GUARD32).all()

@@ -16,6 +16,7 @@ import sys
 import numpy as np
 import pytest
 
+from device_guards import guarded, guards_kept
 import diffusion_model as D
 import ingest_model as M
 
@@ -82,17 +83,6 @@ def _assert_banks(got_main, got_aux, em, ea, mode, what):
         assert got_aux is None and ea is None
 
 
-def _guarded(torch, n_bytes, lead, trail):
-    """a buffer of GUARD bytes and the view of n_bytes that starts `lead` bytes into it"""
-    buf = torch.full((lead + n_bytes + trail,), GUARD, dtype=torch.uint8, device="cuda")
-    return buf, buf[lead:lead + n_bytes]
-
-
-def _guard_kept(buf, lead, n_bytes):
-    b = buf.cpu().numpy()
-    return bool((b[:lead] == GUARD).all() and (b[lead + n_bytes:] == GUARD).all())
-
-
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("name", list(D.KERNELS) + ["made-up 0", "made-up 1"])
 def test_kernels_equal_the_model(native, O, name, mode):
@@ -133,14 +123,14 @@ def test_frame_counts_and_guards(native, O, mode, n):
     frames, em, ea = _jarvis_batch(O, mode)
     w, d = D.KERNELS["jarvis"]
     dev = torch.from_numpy(frames[:n]).cuda()
-    mbuf, mview = _guarded(torch, n * 8192, 8192, 8192)
-    abuf, aview = _guarded(torch, n * 8192, 8192, 8192)
+    mbuf, mview = guarded(n * 8192, 8192, 8192, GUARD)
+    abuf, aview = guarded(n * 8192, 8192, 8192, GUARD)
     native.frames_to_memory_maps_diffused(mode, O.PALETTE_RGB[5], dev, w, d, out=(mview, aview))
     torch.cuda.synchronize()
     _assert_banks(mview, aview if mode == M.DHGR else None, em[:n], ea[:n] if ea is not None else None, mode, ("jarvis", mode, n))
-    assert _guard_kept(mbuf, 8192, n * 8192)
+    assert guards_kept(mbuf, 8192, n * 8192, GUARD)
     if mode == M.DHGR:
-        assert _guard_kept(abuf, 8192, n * 8192)
+        assert guards_kept(abuf, 8192, n * 8192, GUARD)
     else:
         assert (abuf.cpu().numpy() == GUARD).all()          # HGR has no aux bank: none of it is touched
 
@@ -155,14 +145,14 @@ def test_least_alignments(native, O, mode):
     sbuf = torch.full((n * FRAME_BYTES + 64,), GUARD, dtype=torch.uint8, device="cuda")
     sbuf[4:4 + n * FRAME_BYTES] = torch.from_numpy(frames[:n].reshape(-1)).cuda()
     src = sbuf[4:4 + n * FRAME_BYTES].view(n, 192, 280, 3)
-    mbuf, mview = _guarded(torch, n * 8192, 8, 40)
-    abuf, aview = _guarded(torch, n * 8192, 8, 40)
+    mbuf, mview = guarded(n * 8192, 8, 40, GUARD)
+    abuf, aview = guarded(n * 8192, 8, 40, GUARD)
     assert src.data_ptr() % 8 == 4 and mview.data_ptr() % 16 == 8 and aview.data_ptr() % 16 == 8
     native.frames_to_memory_maps_diffused(mode, O.PALETTE_RGB[5], src, w, d, out=(mview, aview))
     torch.cuda.synchronize()
     _assert_banks(mview, aview if mode == M.DHGR else None, em[:n], ea[:n] if ea is not None else None, mode, ("offsets", mode))
-    assert _guard_kept(mbuf, 8, n * 8192)
-    assert _guard_kept(abuf, 8, n * 8192) if mode == M.DHGR else bool((abuf.cpu().numpy() == GUARD).all())
+    assert guards_kept(mbuf, 8, n * 8192, GUARD)
+    assert guards_kept(abuf, 8, n * 8192, GUARD) if mode == M.DHGR else bool((abuf.cpu().numpy() == GUARD).all())
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -176,8 +166,8 @@ def test_invalid_arguments_are_refused_and_nothing_is_written(native, O, mode):
     src_buf = torch.zeros((n * FRAME_BYTES + 16,), dtype=torch.uint8, device="cuda")
     src_buf[:n * FRAME_BYTES] = torch.from_numpy(frames[:n].reshape(-1)).cuda()
     src = src_buf[:n * FRAME_BYTES].view(n, 192, 280, 3)
-    mbuf, mview = _guarded(torch, n * 8192, 8, 8)
-    abuf, aview = _guarded(torch, n * 8192, 8, 8)
+    mbuf, mview = guarded(n * 8192, 8, 8, GUARD)
+    abuf, aview = guarded(n * 8192, 8, 8, GUARD)
 
     def untouched():
         torch.cuda.synchronize()
@@ -204,11 +194,11 @@ def test_invalid_arguments_are_refused_and_nothing_is_written(native, O, mode):
     # alignments, as for iiv_frames_to_memory_maps
     for o in (1, 2):
         refused(("source offset", o), rgb=src_buf[o:o + n * FRAME_BYTES].view(n, 192, 280, 3))
-    main4_buf, main4 = _guarded(torch, n * 8192, 4, 4)
+    main4_buf, main4 = guarded(n * 8192, 4, 4, GUARD)
     refused("main offset 4", out=(main4, aview))
     assert (main4_buf.cpu().numpy() == GUARD).all()
     if mode == M.DHGR:
-        aux4_buf, aux4 = _guarded(torch, n * 8192, 4, 4)
+        aux4_buf, aux4 = guarded(n * 8192, 4, 4, GUARD)
         refused("aux offset 4", out=(mview, aux4))
         assert (aux4_buf.cpu().numpy() == GUARD).all()
     # a bad mode: through the C ABI itself

@@ -10,6 +10,8 @@ import random
 import numpy as np
 import pytest
 
+import encode_harness as H
+
 pytestmark = pytest.mark.gpu
 
 
@@ -56,8 +58,7 @@ def test_live_tags_start_over_on_clean_queues(O, oracle_tables):
     import screen
     import video
     import video_mode
-    from test_gpu_encode import _synth
-    frames = _synth(1, 3, 4711)
+    frames = H.synth(1, 3, 4711)
     random.seed(21)
     np.random.seed(22)
     v = video.Video(_FG(), ticks_per_second=14700., mode=video_mode.VideoMode.DHGR, palette=palette.Palette.NTSC)
@@ -326,8 +327,7 @@ def test_reseeding_between_generators_is_carried_to_the_device(O, oracle_tables)
     import screen
     import video
     import video_mode
-    from test_gpu_encode import _synth
-    frames = _synth(1, 3, 31337)
+    frames = H.synth(1, 3, 31337)
     sched = [(0, 0, 50), (1, 1, 40), (2, 0, 30)]
     random.seed(5)
     np.random.seed(6)
@@ -377,9 +377,8 @@ def test_video_random_interleavings(O, oracle_tables, mode, seed, fourth, monkey
     import screen
     import video
     import video_mode
-    from test_gpu_encode import _synth
     rng = np.random.default_rng(1000 + seed)
-    frames = _synth(mode, 4, 4242 + seed, coherent=True)
+    frames = H.synth(mode, 4, 4242 + seed, coherent=True)
     random.seed(seed)
     np.random.seed(seed + 50)
     if fourth == "strict":      # Video.STRICT_SYNC: the literal behaviour, every next() a full state round trip
@@ -466,8 +465,7 @@ def test_movie_paced_generators_are_single_launches(O, oracle_tables, mode, n_fr
     import stream_batch
     import video
     import video_mode
-    from test_gpu_encode import _synth
-    frames = _synth(mode, n_frames, 777, coherent=False)
+    frames = H.synth(mode, n_frames, 777, coherent=False)
     random.seed(11)
     np.random.seed(12)
     pal = palette.Palette.NTSC

@@ -4,51 +4,24 @@ Bit-exact against (a) opcode streams / final state / RNG positions recorded from
 the imported reference (tests/golden/g3_encode_runs.npz) and (b) the oracle on
 fresh seeded inputs, including batches of independent streams."""
 
-import ctypes as C
-
 import numpy as np
 import pytest
+
+import encode_harness as H
 
 pytestmark = pytest.mark.gpu
 
 N = None
 
 
-def _tags(g3):
-    return sorted(set(k.split("/")[0] for k in g3.files))
-
-
-def _seed_states(O, seed_py, seed_np):
-    return O.mt_seed_py(seed_py).state_words(), O.mt_seed_np(seed_np).state_words()
-
-
-def _run_device(native, device_tables, mode, pal, frames_list, sched, seeds, recurrence=True, wave=True,
-                prefix_sort=True):
-    """frames_list: list (per stream) of (n_frames, banks, 32, 256) arrays."""
-    import torch
-    t, s = device_tables.get(mode, pal)
-    n = len(frames_list)
-    enc = native.Encoder(mode, t, s, n, dm=device_tables.dm[(mode, pal)])
-    enc.set_diff_weights_mode(recurrence)
-    enc.set_greedy_kernel(wave)
-    enc.set_prefix_sort(prefix_sort)
-    fr = np.stack(frames_list)
-    fm = torch.from_numpy(np.ascontiguousarray(fr[:, :, 0])).cuda()
-    fa = torch.from_numpy(np.ascontiguousarray(fr[:, :, 1])).cuda() if mode == 1 else None
-    enc.set_state_all(native.STATE_RNG_PY, np.stack([py for py, _ in seeds]))
-    enc.set_state_all(native.STATE_RNG_NP, np.stack([npw for _, npw in seeds]))
-    segs = [(int(f), int(a), 1, int(k)) for (f, a, k) in sched]
-    ops = enc.encode(fm, fa, segs)
+def _run_device(native, O, device_tables, mode, pal, frames_list, sched, seeds, recurrence=True, wave=True, prefix_sort=True):
+    """frames_list: list (per stream) of (n_frames, banks, 32, 256) arrays; seeds: (seed_py, seed_np) per stream."""
+    enc = H.make_encoder(native, device_tables, mode, pal, len(frames_list), dw=recurrence, kernel=wave, prefix=prefix_sort,
+                         rng=seeds, O=O)
+    fm, fa = H.device_frames(mode, frames_list)
+    ops = enc.encode(fm, fa, H.segments(sched))
     enc.check()
     return enc, ops.cpu().numpy()
-
-
-def _next_draws(O, words, n, high):
-    m = O.MT()
-    m.set_state_words(words)
-    L = O.lib()
-    f = L.orc_py_getrandbits8 if high else L.orc_np_randint256
-    return [f(C.byref(m)) for _ in range(n)]
 
 
 @pytest.mark.parametrize("recurrence,wave", [(True, True), (False, True), (True, False), (False, False), (True, "team"),
@@ -61,54 +34,14 @@ def test_golden_runs(native, O, golden, device_tables, recurrence, wave):
     stream scoring the next list entries concurrently.  Every combination must reproduce the
     reference bit for bit."""
     g3 = golden.g3_encode_runs
-    for tag in _tags(g3):
-        mode, pal, sp, sn = (int(x) for x in g3[tag + "/meta"])
-        frames, sched, ops = g3[tag + "/frames"], g3[tag + "/schedule"], g3[tag + "/ops"]
-        enc, got = _run_device(native, device_tables, mode, pal, [frames], sched, [_seed_states(O, sp, sn)],
+    for tag in H.tags(g3):
+        rec = H.recorded(g3, tag)
+        mode, pal, sp, sn = (int(x) for x in rec["meta"])
+        enc, got = _run_device(native, O, device_tables, mode, pal, [rec["frames"]], rec["schedule"], [(sp, sn)],
                                recurrence=recurrence, wave=wave)
-        bad = np.nonzero((got[0] != ops).any(axis=1))[0]
-        assert len(bad) == 0, "%s: first mismatch at op %d: got %s want %s" % (
-            tag, bad[0], got[0][bad[0]], ops[bad[0]])
-        assert (enc.get_state(native.STATE_MEM_MAIN) == g3[tag + "/mem_main"]).all(), tag
-        assert (enc.get_state(native.STATE_UP_MAIN) == g3[tag + "/up_main"]).all(), tag
-        assert (enc.get_state(native.STATE_PACKED) == g3[tag + "/packed"]).all(), tag
-        if mode == 1:
-            assert (enc.get_state(native.STATE_MEM_AUX) == g3[tag + "/mem_aux"]).all(), tag
-            assert (enc.get_state(native.STATE_UP_AUX) == g3[tag + "/up_aux"]).all(), tag
-        assert enc.get_state(native.STATE_OUT_OF_WORK).tolist() == g3[tag + "/out_of_work"].tolist(), tag
-        assert _next_draws(O, enc.get_state(native.STATE_RNG_PY), 4, True) == g3[tag + "/py_next"].tolist(), tag
-        assert _next_draws(O, enc.get_state(native.STATE_RNG_NP), 4, False) == g3[tag + "/np_next"].tolist(), tag
+        H.check_ops(got[0], rec["ops"], tag)
+        H.check_recorded_state(native, O, enc, 0, rec, tag)
         enc.close()
-
-
-def _synth(mode, n_frames, seed, coherent=False):
-    holes = (np.arange(256) & 127) >= 120
-    rng = np.random.default_rng(seed)
-    hi = 128 if mode == 1 else 256
-    banks = 2 if mode == 1 else 1
-    fr = np.zeros((n_frames, 2, 32, 256), np.uint8)
-    prev = None
-    for f in range(n_frames):
-        cur = []
-        for b in range(banks):
-            new = rng.integers(0, hi, (32, 256), dtype=np.uint8)
-            if coherent and prev is not None:
-                new = np.where(rng.random((32, 256)) < 0.9, prev[b], new)
-            new[:, holes] = 0
-            cur.append(new)
-        prev = cur
-        for b in range(banks):
-            fr[f, b] = cur[b]
-    return fr
-
-
-def _oracle_run(O, oracle_tables, mode, pal, frames, sched, sp, sn):
-    v = O.Video(mode, oracle_tables.get(mode, pal), seed_py=sp, seed_np=sn)
-    out = []
-    for fi, ia, n in sched:
-        v.encode_frame(frames[fi, 0], frames[fi, 1] if mode == 1 else None, ia)
-        out.append(v.next(int(n)))
-    return v, np.concatenate(out)
 
 
 @pytest.mark.parametrize("mode,wave,prefix", [(1, True, True), (0, True, True), (1, False, True), (1, True, False), (1, "shared", True), (1, "shared", False), (0, "shared", True),
@@ -118,34 +51,23 @@ def test_batch_of_independent_streams(native, O, oracle_tables, device_tables, m
     ragged segment lengths incl. bank flips; every stream equals its own oracle run."""
     n = 12
     sched = [(0, 0, 37), (0, 1 if mode == 1 else 0, 291), (1, 0, 200), (1, 1 if mode == 1 else 0, 1), (2, 0, 490)]
-    frames = [_synth(mode, 3, 100 + i, coherent=(i % 2 == 1)) for i in range(n)]
+    frames = [H.synth(mode, 3, 100 + i, coherent=(i % 2 == 1)) for i in range(n)]
     seeds = [(i + 1, 1000 + i) for i in range(n)]
-    enc, got = _run_device(native, device_tables, mode, 5, frames, sched,
-                           [_seed_states(O, a, b) for a, b in seeds], wave=wave, prefix_sort=prefix)
+    enc, got = _run_device(native, O, device_tables, mode, 5, frames, sched, seeds, wave=wave, prefix_sort=prefix)
     for i in range(n):
-        v, exp = _oracle_run(O, oracle_tables, mode, 5, frames[i], sched, *seeds[i])
-        assert (got[i] == exp).all(), "stream %d" % i
-        assert (enc.get_state(native.STATE_MEM_MAIN, i) == v.memory(0)).all()
-        assert (enc.get_state(native.STATE_UP_MAIN, i) == v.update_priority(0)).all()
-        assert (enc.get_state(native.STATE_PACKED, i) == v.packed).all()
-        cnt = enc.get_state(native.STATE_COUNTERS, i)
-        assert (int(cnt[0]), int(cnt[1])) == v.draws()
+        v, exp = H.oracle_run(O, oracle_tables, mode, 5, frames[i], sched, seeds[i])
+        H.check_ops(got[i], exp, "stream %d" % i)
+        H.check_oracle_state(native, enc, i, v, mode, "stream %d" % i)
     enc.close()
 
 
 def test_continue_generator_and_lazy_segments(native, O, oracle_tables, device_tables):
     """restart=0 continues the same generator; an n_ops=0 restart segment is lazy
     (no side effects until the first next())."""
-    import torch
     mode = 1
-    frames = _synth(mode, 2, 77)
-    t, s = device_tables.get(mode)
-    enc = native.Encoder(mode, t, s, 1, dm=device_tables.dm[(mode, 5)])
-    py, npw = _seed_states(O, 3, 4)
-    enc.set_state(native.STATE_RNG_PY, py)
-    enc.set_state(native.STATE_RNG_NP, npw)
-    fm = torch.from_numpy(frames[None, :, 0].copy()).cuda()
-    fa = torch.from_numpy(frames[None, :, 1].copy()).cuda()
+    frames = H.synth(mode, 2, 77)
+    enc = H.make_encoder(native, device_tables, mode, rng=[(3, 4)], O=O)
+    fm, fa = H.device_frames(mode, [frames])
     segs = [(0, 0, 1, 10), (0, 0, 0, 5), (0, 0, 0, 1), (1, 1, 1, 0), (1, 1, 0, 7), (1, 1, 0, 3)]
     got = enc.encode(fm, fa, segs).cpu().numpy()[0]
     enc.check()
@@ -161,12 +83,10 @@ def test_continue_generator_and_lazy_segments(native, O, oracle_tables, device_t
 def test_idempotent_when_converged(native, O, device_tables):
     """Property: once a bank is exhausted, re-encoding the same target emits only
     padding opcodes (32, target[0,0], 0,0,0,0) and changes nothing."""
-    import torch
     mode = 0
-    frames = _synth(mode, 1, 5)
-    t, s = device_tables.get(mode)
-    enc = native.Encoder(mode, t, s, 1)
-    fm = torch.from_numpy(frames[None, :, 0].copy()).cuda()
+    frames = H.synth(mode, 1, 5)
+    enc = H.make_encoder(native, device_tables, mode, dm=False)
+    fm, _ = H.device_frames(mode, [frames])
     enc.encode(fm, None, [(0, 0, 1, 7000)])
     enc.check()
     assert enc.get_state(native.STATE_OUT_OF_WORK)[0] == 1
@@ -181,8 +101,7 @@ def test_idempotent_when_converged(native, O, device_tables):
 def test_reference_asserts_are_reported(native, device_tables):
     """video.py:137: a DHGR content byte with the palette bit set is an error, not silent."""
     import torch
-    t, s = device_tables.get(1)
-    enc = native.Encoder(1, t, s, 2)
+    enc = H.make_encoder(native, device_tables, 1, n_streams=2, dm=False)
     fm = torch.zeros((2, 1, 32, 256), dtype=torch.uint8, device="cuda")
     fa = torch.zeros((2, 1, 32, 256), dtype=torch.uint8, device="cuda")
     fm[1, 0, 3, 5] = 0x85
@@ -190,7 +109,7 @@ def test_reference_asserts_are_reported(native, device_tables):
     with pytest.raises(AssertionError):
         enc.check()
     enc.close()
-    enc = native.Encoder(1, t, s, 1)
+    enc = H.make_encoder(native, device_tables, 1, dm=False)
     with pytest.raises(native.IIVError):
         enc.encode(fm[:1], fa[:1], [(0, 0, 0, 5)])  # continues a generator that does not exist
     enc.close()
@@ -215,15 +134,11 @@ def test_image_like_streams(native, O, oracle_tables, device_tables, mode, wave)
     b = 1 if mode == 1 else 0
     sched = [(0, 0, 292), (0, b, 198), (1, b, 94), (1, 0, 292), (1, b, 104), (2, b, 490)]
     seeds = [(50 + i, 90 + i) for i in range(n)]
-    enc, got = _run_device(native, device_tables, mode, 5, frames, sched,
-                           [_seed_states(O, a, c) for a, c in seeds], wave=wave)
+    enc, got = _run_device(native, O, device_tables, mode, 5, frames, sched, seeds, wave=wave)
     for i in range(n):
-        v, exp = _oracle_run(O, oracle_tables, mode, 5, frames[i], sched, *seeds[i])
-        assert (got[i] == exp).all(), "stream %d" % i
-        assert (enc.get_state(native.STATE_UP_MAIN, i) == v.update_priority(0)).all()
-        assert (enc.get_state(native.STATE_PACKED, i) == v.packed).all()
-        cnt = enc.get_state(native.STATE_COUNTERS, i)
-        assert (int(cnt[0]), int(cnt[1])) == v.draws()
+        v, exp = H.oracle_run(O, oracle_tables, mode, 5, frames[i], sched, seeds[i])
+        H.check_ops(got[i], exp, "stream %d" % i)
+        H.check_oracle_state(native, enc, i, v, mode, "stream %d" % i)
     enc.close()
 
 
@@ -232,20 +147,12 @@ def test_per_stream_schedules(native, O, oracle_tables, device_tables, mode, wav
     """iiv_encode_streams: every stream has its own movie clock (movie.py:16-54) -- different
     clip lengths, every_n_video_frames and frame rates in ONE batch, over two calls so that
     generators are continued across calls.  Each stream equals its own oracle run."""
-    import torch
     import stream_batch
     n, nf = 7, 6
-    frames = [_synth(mode, nf, 300 + i, coherent=(i % 3 == 0)) for i in range(n)]
+    frames = [H.synth(mode, nf, 300 + i, coherent=(i % 3 == 0)) for i in range(n)]
     seeds = [(11 + i, 500 + i) for i in range(n)]
-    t, s = device_tables.get(mode)
-    enc = native.Encoder(mode, t, s, n, dm=device_tables.dm[(mode, 5)])
-    enc.set_greedy_kernel(wave)
-    st = [_seed_states(O, a, b) for a, b in seeds]
-    enc.set_state_all(native.STATE_RNG_PY, np.stack([x for x, _ in st]))
-    enc.set_state_all(native.STATE_RNG_NP, np.stack([y for _, y in st]))
-    fr = np.stack(frames)
-    fm = torch.from_numpy(np.ascontiguousarray(fr[:, :, 0])).cuda()
-    fa = torch.from_numpy(np.ascontiguousarray(fr[:, :, 1])).cuda() if mode == 1 else None
+    enc = H.make_encoder(native, device_tables, mode, n_streams=n, kernel=wave, rng=seeds, O=O)
+    fm, fa = H.device_frames(mode, frames)
     clocks = [stream_batch.MovieClock(mode == 1, every_n_video_frames=1 + i % 3, input_frame_rate=(30.0, 24.0, 60.0)[i % 3])
               for i in range(n)]
     lengths = [nf - (i % 3) for i in range(n)]              # clips of 6, 5, 4 frames
@@ -264,17 +171,9 @@ def test_per_stream_schedules(native, O, oracle_tables, device_tables, mode, wav
             got[i].append(ops[i, :totals[i]])
     assert len(set(len(x) for x in scheds)) > 1              # really different schedules
     for i in range(n):
-        v = O.Video(mode, oracle_tables.get(mode), seed_py=seeds[i][0], seed_np=seeds[i][1])
-        exp = []
-        for (f, ia, restart, k) in scheds[i]:
-            if restart:
-                v.encode_frame(frames[i][f, 0], frames[i][f, 1] if mode == 1 else None, ia)
-            exp.append(v.next(k))
-        exp = np.concatenate(exp)
-        g = np.concatenate(got[i])
-        assert g.shape == exp.shape and (g == exp).all(), "stream %d" % i
-        assert (enc.get_state(native.STATE_UP_MAIN, i) == v.update_priority(0)).all()
-        assert (enc.get_state(native.STATE_MEM_MAIN, i) == v.memory(0)).all()
+        v, exp = H.oracle_run(O, oracle_tables, mode, 5, frames[i], scheds[i], seeds[i])
+        H.check_ops(np.concatenate(got[i]), exp, "stream %d" % i)
+        H.check_oracle_state(native, enc, i, v, mode, "stream %d" % i)
     with pytest.raises(native.IIVError):
         enc.encode(fm, fa, [(0, 0, 1, 5)])                   # the streams no longer share a schedule
     enc.close()
@@ -285,21 +184,12 @@ def test_per_stream_schedules(native, O, oracle_tables, device_tables, mode, wav
 def test_generator_advanced_a_few_opcodes_per_launch(native, O, oracle_tables, device_tables, mode, kernel):
     """What video.Video does without a budget: hundreds of launches of one, two or three opcodes continuing the same
     generator (state, bitmaps, MT19937 block and window position saved and restored every time) equal one run of the oracle."""
-    import torch
-    t, s = device_tables.get(mode, 5)
-    frames = _synth(mode, 2, 4246, coherent=True)
-    fm = torch.from_numpy(frames[None, :, 0].copy()).cuda()
-    fa = torch.from_numpy(frames[None, :, 1].copy()).cuda() if mode == 1 else None
+    frames = H.synth(mode, 2, 4246, coherent=True)
+    fm, fa = H.device_frames(mode, [frames])
     n = 420
+    _, exp = H.oracle_run(O, oracle_tables, mode, 5, frames, [(0, 0, n)], (11, 12))
     for chunk in (1, 2, 3):
-        enc = native.Encoder(mode, t, s, 1, dm=device_tables.dm[(mode, 5)])
-        enc.set_greedy_kernel(kernel)
-        py, npw = _seed_states(O, 11, 12)
-        enc.set_state(native.STATE_RNG_PY, py)
-        enc.set_state(native.STATE_RNG_NP, npw)
-        v = O.Video(mode, oracle_tables.get(mode, 5), seed_py=11, seed_np=12)
-        v.encode_frame(frames[0, 0], frames[0, 1] if mode else None, 0)
-        exp = v.next(n)
+        enc = H.make_encoder(native, device_tables, mode, kernel=kernel, rng=[(11, 12)], O=O)
         got = np.concatenate([enc.encode(fm, fa, [(0, 0, 1 if i == 0 else 0, chunk)]).cpu().numpy()[0] for i in range(0, n, chunk)])
         enc.check()
         assert (got[:n] == exp).all(), (mode, kernel, chunk)
@@ -313,18 +203,11 @@ def test_live_queue_carries_every_opcode(native, O, oracle_tables, device_tables
     work; a launch that ends short marks the slot behind its last opcode; an encoder whose options keep it off the team
     kernel refuses before anything is launched."""
     import torch
-    frames = _synth(mode, 3, 91 + mode)
+    frames = H.synth(mode, 3, 91 + mode)
     sp, sn = 21, 22
     sched = [(0, 0, 1, 292), (0, 1 if mode else 0, 1, 198), (1, 0, 1, 2000), (2, 0, 1, 7), (2, 0, 0, 300)]
-    t, s = device_tables.get(mode, 5)
-    enc = native.Encoder(mode, t, s, 1, dm=device_tables.dm[(mode, 5)])
-    if fourth:
-        enc.set_fourth_offset(True)
-    fm = torch.from_numpy(np.ascontiguousarray(frames[None, :, 0])).cuda()
-    fa = torch.from_numpy(np.ascontiguousarray(frames[None, :, 1])).cuda() if mode == 1 else None
-    py, npw = _seed_states(O, sp, sn)
-    enc.set_state_all(native.STATE_RNG_PY, py[None])
-    enc.set_state_all(native.STATE_RNG_NP, npw[None])
+    enc = H.make_encoder(native, device_tables, mode, rng=[(sp, sn)], O=O, **({"fourth": True} if fourth else {}))
+    fm, fa = H.device_frames(mode, [frames])
     ov = O.Video(mode, oracle_tables.get(mode, 5), seed_py=sp, seed_np=sn)
     ov.set_fourth_offset(fourth)
     queues = [enc.live_queue(0), enc.live_queue(1)]
@@ -349,8 +232,7 @@ def test_live_queue_carries_every_opcode(native, O, oracle_tables, device_tables
     if mode == 1 and not fourth:
         bad = frames[:1].copy()
         bad[0, 0, np.arange(64) % 32, (np.arange(64) * 37) % 120] |= 0x80    # (64 bytes: one of them is popped within the launch)
-        fmb = torch.from_numpy(np.ascontiguousarray(bad[None, :, 0])).cuda()
-        fab = torch.from_numpy(np.ascontiguousarray(bad[None, :, 1])).cuda()
+        fmb, fab = H.device_frames(mode, [bad])
         enc.snapshot(0)
         enc.encode_live(fmb, fab, (0, 0, 1, 2048), ops_dev, 0, 77)
         with pytest.raises(AssertionError):
@@ -368,11 +250,8 @@ def test_live_queue_carries_every_opcode(native, O, oracle_tables, device_tables
         assert (ops[0].cpu().numpy() == rows[:-1, :6]).all()
     enc.close()
     # options that keep the launches off the team kernel: refused, nothing launched, the generator bookkeeping untouched
-    enc = native.Encoder(mode, t, s, 1, dm=device_tables.dm[(mode, 5)])
-    enc.set_greedy_kernel("plain")
+    enc = H.make_encoder(native, device_tables, mode, kernel="plain", rng=[(sp, sn)], O=O)
     enc.live_queue(0)
-    enc.set_state_all(native.STATE_RNG_PY, py[None])
-    enc.set_state_all(native.STATE_RNG_NP, npw[None])
     with pytest.raises(native.IIVError) as ei:
         enc.encode_live(fm, fa, (0, 0, 1, 50), ops_dev, 0, 5)
     assert ei.value.code == native.ERR_INVALID
@@ -388,21 +267,18 @@ def test_live_queue_carries_every_opcode(native, O, oracle_tables, device_tables
 def test_set_state_async_is_set_state_in_stream_order(native, O, oracle_tables, device_tables):
     """iiv_encoder_set_state_async (out_of_work flags, both RNG states): what iiv_encoder_set_state does, enqueued behind the
     launches already on the stream -- a generator launched after it sees the new values, one launched before does not."""
-    import torch
     mode = 1
-    frames = _synth(mode, 2, 17)
-    t, s = device_tables.get(mode, 5)
-    fm = torch.from_numpy(np.ascontiguousarray(frames[None, :, 0])).cuda()
-    fa = torch.from_numpy(np.ascontiguousarray(frames[None, :, 1])).cuda()
+    frames = H.synth(mode, 2, 17)
+    fm, fa = H.device_frames(mode, [frames])
     runs = []
     for use_async in (False, True):
-        enc = native.Encoder(mode, t, s, 1, dm=device_tables.dm[(mode, 5)])
-        put = enc.set_state_async if use_async else enc.set_state
-        py, npw = _seed_states(O, 5, 6)
+        enc = H.make_encoder(native, device_tables, mode)
+        put = enc.set_state_async if use_async else enc.set_state     # (the two calls under test: not the harness' upload)
+        py, npw = H.seed_states(O, 5, 6)
         put(native.STATE_RNG_PY, py)
         put(native.STATE_RNG_NP, npw)
         a = enc.encode(fm, fa, [(0, 0, 1, 300)]).cpu().numpy()
-        py2, npw2 = _seed_states(O, 7, 8)
+        py2, npw2 = H.seed_states(O, 7, 8)
         for _ in range(6):      # (more calls than the staging ring has slots)
             put(native.STATE_RNG_PY, py2)
             put(native.STATE_RNG_NP, npw2)

@@ -10,15 +10,11 @@ import collections
 import numpy as np
 import pytest
 
+import encode_harness as H
 import form_handover as FH
 import reference_corpus as RC
-from test_gpu_encode import _next_draws, _seed_states
-from test_gpu_reference_corpus import _device_frames
 
 pytestmark = pytest.mark.gpu
-
-N_DRAWS = 640       # draws compared behind the last launch: through the end of the block and into the next
-
 
 @pytest.fixture(scope="module")
 def corpus(golden):
@@ -27,14 +23,8 @@ def corpus(golden):
 
 def _encoder(native, O, device_tables, rec, seeds, recurrence=True):
     mode, pal, _, _, fourth, _ = (int(x) for x in rec["meta"])
-    t, s = device_tables.get(mode, pal)
-    enc = native.Encoder(mode, t, s, len(seeds), dm=device_tables.dm[(mode, pal)])
-    enc.set_diff_weights_mode(recurrence)
-    if fourth:
-        enc.set_fourth_offset(True)
-    st = [_seed_states(O, sp, sn) for sp, sn in seeds]
-    enc.set_state_all(native.STATE_RNG_PY, np.stack([py for py, _ in st]))
-    enc.set_state_all(native.STATE_RNG_NP, np.stack([npw for _, npw in st]))
+    enc = H.make_encoder(native, device_tables, mode, pal, len(seeds), dw=recurrence, rng=seeds, O=O,
+                         **({"fourth": True} if fourth else {}))
     enc.profile(True)
     return enc
 
@@ -60,12 +50,6 @@ def _run(enc, fm, fa, launches, between=None):
     return torch.cat(out, dim=1).cpu().numpy()
 
 
-def _first_bad(got, want):
-    assert got.shape == want.shape, (got.shape, want.shape)
-    bad = np.nonzero((got != want).any(axis=1))[0]
-    return None if len(bad) == 0 else int(bad[0])
-
-
 def _where(launches, pos):
     L = [x for x in launches if x.pos <= pos][-1]
     before = launches[launches.index(L) - 1].form if not L.restart else "(new generator)"
@@ -73,26 +57,22 @@ def _where(launches, pos):
 
 
 def _check_ops(tag, rec, got, streams, launches):
-    bad = _first_bad(got[0], rec["ops"])
+    bad = H.first_difference(got[0], rec["ops"], tag)
     assert bad is None, "%s stream 0 leaves the recording at %s: got %s want %s" % (tag, _where(launches, bad), got[0][bad], rec["ops"][bad])
     for i, e in enumerate(streams):
-        bad = _first_bad(got[i], e.ops)
+        bad = H.first_difference(got[i], e.ops, "%s stream %d" % (tag, i))
         assert bad is None, "%s stream %d leaves the oracle at %s: got %s want %s" % (tag, i, _where(launches, bad), got[i][bad], e.ops[bad])
 
 
-def _check_state(native, O, tag, rec, enc, streams):
-    """both memory maps, both priority arrays, out_of_work, the four counters and both RNG streams, behind the last launch"""
+def _check_state(native, tag, rec, enc, streams):
+    """the shared state check (both generators in full: every draw behind the last launch, through the end of the block and
+    into the next) and all four counters, behind the last launch"""
     mode, segs = int(rec["meta"][0]), FH.segments(rec)
     for i, e in enumerate(streams):
         v, what = e.video, "%s stream %d" % (tag, i)
-        for b in range(mode + 1):
-            assert (enc.get_state((native.STATE_MEM_MAIN, native.STATE_MEM_AUX)[b], i) == v.memory(b)).all(), (what, "memory", b)
-            assert (enc.get_state((native.STATE_UP_MAIN, native.STATE_UP_AUX)[b], i) == v.update_priority(b)).all(), (what, "priorities", b)
-        assert enc.get_state(native.STATE_OUT_OF_WORK, i).tolist() == [int(v.out_of_work(0)), int(v.out_of_work(1))], what
+        H.check_oracle_state(native, enc, i, v, mode, what)
         pad = sum(int(RC.is_padding(e.ops[s:s + n], rec["frames"], fi, ia).sum()) for (fi, ia, s, n, _) in segs)
         assert [int(x) for x in enc.get_state(native.STATE_COUNTERS, i)] == list(v.draws()) + [len(e.ops), pad], what
-        assert _next_draws(O, enc.get_state(native.STATE_RNG_PY, i), N_DRAWS, True) == _next_draws(O, v.rng_py().state_words(), N_DRAWS, True), what
-        assert _next_draws(O, enc.get_state(native.STATE_RNG_NP, i), 8, False) == _next_draws(O, v.rng_np().state_words(), 8, False), what
 
 
 @pytest.mark.parametrize("recurrence", [True, "split"])
@@ -108,13 +88,13 @@ def test_the_matrix(native, O, corpus, device_tables, tag, recurrence):
     launches = FH.plan(rec["schedule"], FH.forms_of(rec), start=FH.STARTS[0 if recurrence is True else 1])
     streams = FH.expected(tag, rec)
     enc = _encoder(native, O, device_tables, rec, FH.batch(rec), recurrence)
-    fm, fa = _device_frames(int(rec["meta"][0]), [rec["frames"]] * len(streams))
+    fm, fa = H.device_frames(int(rec["meta"][0]), [rec["frames"]] * len(streams))
     got = _run(enc, fm, fa, launches)
     ran = enc.launch_forms()
     print("%s, diff weights %r: %d launches, %d hand-overs, by kernel %s" % (tag, recurrence, len(launches), len(FH.handovers(launches)), ran))
     assert ran == _ran(launches, fourth) and all(ran[f] > 0 for f in FH.forms_of(rec)) and (ran["workgroup"] == 0) == fourth, ran
     _check_ops(tag, rec, got, streams, launches)
-    _check_state(native, O, tag, rec, enc, streams)
+    _check_state(native, tag, rec, enc, streams)
     enc.close()
 
 
@@ -134,7 +114,7 @@ def test_the_host_looks_in_between(native, O, corpus, device_tables, tag):
     assert len(tenth) >= 15 and len(differ) >= 8
     videos = {s: RC.oracle_video(FH._Seeded(rec, seeds[s])) for s in look_at}
     enc = _encoder(native, O, device_tables, rec, seeds)
-    fm, fa = _device_frames(mode, [rec["frames"]] * len(streams))
+    fm, fa = H.device_frames(mode, [rec["frames"]] * len(streams))
     looked = []
 
     def between(i):
@@ -167,12 +147,12 @@ def test_the_fallback_is_a_handover_too(native, O, corpus, device_tables, tag):
     assert sum(L.form == "workgroup" for L in launches) >= 40
     streams = FH.expected(tag, rec)
     enc = _encoder(native, O, device_tables, rec, FH.batch(rec))
-    fm, fa = _device_frames(int(rec["meta"][0]), [rec["frames"]] * len(streams))
+    fm, fa = H.device_frames(int(rec["meta"][0]), [rec["frames"]] * len(streams))
     got = _run(enc, fm, fa, launches)
     ran = enc.launch_forms()
     assert ran == _ran(launches, True) and ran["workgroup"] == 0 and min(ran["plain"], ran["shared"], ran["team"]) > 0, ran
     _check_ops(tag, rec, got, streams, launches)
-    _check_state(native, O, tag, rec, enc, streams)
+    _check_state(native, tag, rec, enc, streams)
     enc.close()
 
 
@@ -201,7 +181,7 @@ def test_one_call_two_forms(native, O, corpus, device_tables, swapped):
     scheds = [sched_x if s % 2 == 0 else sched_y for s in range(len(seeds))]
     enc = _encoder(native, O, device_tables, rec, seeds)
     enc.set_greedy_kernel("shared")
-    fm, fa = _device_frames(1, [frames] * len(seeds))
+    fm, fa = H.device_frames(1, [frames] * len(seeds))
     ops, totals = enc.encode_streams(fm, fa, scheds)
     enc.check()
     ran = enc.launch_forms()
@@ -216,13 +196,10 @@ def test_one_call_two_forms(native, O, corpus, device_tables, swapped):
             want.append(v.next(k))
         want = np.concatenate(want)
         assert totals[s] == len(want)
-        bad = _first_bad(got[s, :totals[s]], want)
+        bad = H.first_difference(got[s, :totals[s]], want, "stream %d" % s)
         assert bad is None, "stream %d (group %s) leaves the oracle at opcode %d of %s" % (s, "XY"[s % 2], bad, [g[3] for g in scheds[s]])
         assert not got[s, totals[s]:].any()
-        for b in (0, 1):
-            assert (enc.get_state((native.STATE_MEM_MAIN, native.STATE_MEM_AUX)[b], s) == v.memory(b)).all(), s
-            assert (enc.get_state((native.STATE_UP_MAIN, native.STATE_UP_AUX)[b], s) == v.update_priority(b)).all(), s
-        assert [int(x) for x in enc.get_state(native.STATE_COUNTERS, s)[:2]] == list(v.draws()), s
+        H.check_oracle_state(native, enc, s, v, 1, "stream %d" % s)
     if not swapped:
         assert (got[0, :totals[0]] == rec["ops"][:totals[0]]).all()
     enc.close()
@@ -240,9 +217,9 @@ def test_snapshot_under_one_form_roll_back_into_another(native, O, corpus, devic
     (f, a, start, n, real) = FH.segments(rec)[2]
     assert n > 4000 and n - real >= 20
     enc = _encoder(native, O, device_tables, rec, seeds)
-    fm, fa = _device_frames(1, [rec["frames"]] * len(seeds))
+    fm, fa = H.device_frames(1, [rec["frames"]] * len(seeds))
     enc.set_greedy_kernel("plain")
-    enc.encode(fm, fa, [(int(fi), int(ia), 1, int(k)) for (fi, ia, k) in rec["schedule"][:2]])
+    enc.encode(fm, fa, H.segments(rec["schedule"][:2]))
     pos, want_forms = 0, collections.Counter(plain=2)
     for slot, at in ((1, real // 2), (0, real - 280)):
         enc.set_greedy_kernel("plain")
@@ -259,7 +236,7 @@ def test_snapshot_under_one_form_roll_back_into_another(native, O, corpus, devic
         enc.check()
         for form, ops in runs.items():
             for s, e in enumerate(streams):
-                bad = _first_bad(ops[s], e.ops[start + at:start + at + 300])
+                bad = H.first_difference(ops[s], e.ops[start + at:start + at + 300], "slot %d, %r, stream %d" % (slot, form, s))
                 assert bad is None, "slot %d, %r from opcode %d: stream %d differs at +%d" % (slot, form, at, s, bad)
         pos = at + 300
     assert pos == real + 20
@@ -282,7 +259,7 @@ def test_live_and_back(native, O, corpus, device_tables, tag):
     others = ("plain", "workgroup", "shared")
     launches = [L._replace(form="team" if i % 2 == 0 else others[(i // 2) % 3]) for i, L in enumerate(cuts)]
     enc = _encoder(native, O, device_tables, rec, FH.batch(rec)[:1])
-    fm, fa = _device_frames(mode, [rec["frames"]])
+    fm, fa = H.device_frames(mode, [rec["frames"]])
     enc.live_queue(0), enc.live_queue(1)
     buf = torch.empty((1, 128, 6), dtype=torch.uint8, device="cuda")
     out = []
@@ -296,7 +273,7 @@ def test_live_and_back(native, O, corpus, device_tables, tag):
     enc.check()
     assert enc.launch_forms() == _ran(launches, False) and min(enc.launch_forms().values()) >= 30
     got = torch.cat(out, dim=1).cpu().numpy()
-    bad = _first_bad(got[0], rec["ops"])
+    bad = H.first_difference(got[0], rec["ops"], tag)
     assert bad is None, "%s leaves the recording at %s" % (tag, _where(launches, bad))
-    _check_state(native, O, tag, rec, enc, FH.expected(tag, rec)[:1])
+    _check_state(native, tag, rec, enc, FH.expected(tag, rec)[:1])
     enc.close()

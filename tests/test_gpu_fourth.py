@@ -9,53 +9,27 @@ tests hold the kernel to both."""
 import numpy as np
 import pytest
 
-from test_gpu_encode import _next_draws, _seed_states, _synth
+import encode_harness as H
 
 pytestmark = pytest.mark.gpu
-
-
-def _tags(g):
-    return sorted(set(k.split("/")[0] for k in g.files))
-
-
-def _encoder(native, device_tables, mode, pal, n, recurrence=True, prefix=True, kernel=None):
-    t, s = device_tables.get(mode, pal)
-    enc = native.Encoder(mode, t, s, n, dm=device_tables.dm[(mode, pal)])
-    enc.set_diff_weights_mode(recurrence)
-    enc.set_prefix_sort(prefix)
-    enc.set_greedy_kernel(kernel)      # (the option runs in the one-wave and the eight-wave kernel; others fall back to the one-wave)
-    enc.set_fourth_offset(True)
-    return enc
 
 
 @pytest.mark.parametrize("recurrence,prefix,kernel", [(True, True, None), (False, False, "team"), ("split", True, False), (True, False, "shared")])
 def test_reference_with_exit_test_at_four(native, O, golden, device_tables, recurrence, prefix, kernel):
     """The reference's own runs with `len(offsets) == 4`: opcodes, memory maps, priorities, packed screen,
     out_of_work and both RNG positions, incl. runs to exhaustion (bag phase with three pushes per step, padding)."""
-    import torch
     g8 = golden.g8_fourth_offset
-    for tag in _tags(g8):
-        mode, pal, sp, sn = (int(x) for x in g8[tag + "/meta"])
-        frames, sched, ops = g8[tag + "/frames"], g8[tag + "/schedule"], g8[tag + "/ops"]
-        enc = _encoder(native, device_tables, mode, pal, 1, recurrence, prefix, kernel)
-        py, npw = _seed_states(O, sp, sn)
-        enc.set_state(native.STATE_RNG_PY, py)
-        enc.set_state(native.STATE_RNG_NP, npw)
-        fm = torch.from_numpy(np.ascontiguousarray(frames[None, :, 0])).cuda()
-        fa = torch.from_numpy(np.ascontiguousarray(frames[None, :, 1])).cuda() if mode == 1 else None
-        got = enc.encode(fm, fa, [(int(f), int(a), 1, int(k)) for (f, a, k) in sched]).cpu().numpy()
+    for tag in H.tags(g8):
+        rec = H.recorded(g8, tag)
+        mode, pal, sp, sn = (int(x) for x in rec["meta"])
+        # (the option runs in the one-wave and the eight-wave kernel; others fall back to the one-wave)
+        enc = H.make_encoder(native, device_tables, mode, pal, dw=recurrence, kernel=kernel, prefix=prefix, fourth=True,
+                             rng=[(sp, sn)], O=O)
+        fm, fa = H.device_frames(mode, [rec["frames"]])
+        got = enc.encode(fm, fa, H.segments(rec["schedule"])).cpu().numpy()
         enc.check()
-        bad = np.nonzero((got[0] != ops).any(axis=1))[0]
-        assert len(bad) == 0, "%s: first mismatch at op %d: got %s want %s" % (tag, bad[0], got[0][bad[0]], ops[bad[0]])
-        assert (enc.get_state(native.STATE_MEM_MAIN) == g8[tag + "/mem_main"]).all(), tag
-        assert (enc.get_state(native.STATE_UP_MAIN) == g8[tag + "/up_main"]).all(), tag
-        assert (enc.get_state(native.STATE_PACKED) == g8[tag + "/packed"]).all(), tag
-        if mode == 1:
-            assert (enc.get_state(native.STATE_MEM_AUX) == g8[tag + "/mem_aux"]).all(), tag
-            assert (enc.get_state(native.STATE_UP_AUX) == g8[tag + "/up_aux"]).all(), tag
-        assert enc.get_state(native.STATE_OUT_OF_WORK).tolist() == g8[tag + "/out_of_work"].tolist(), tag
-        assert _next_draws(O, enc.get_state(native.STATE_RNG_PY), 4, True) == g8[tag + "/py_next"].tolist(), tag
-        assert _next_draws(O, enc.get_state(native.STATE_RNG_NP), 4, False) == g8[tag + "/np_next"].tolist(), tag
+        H.check_ops(got[0], rec["ops"], tag)
+        H.check_recorded_state(native, O, enc, 0, rec, tag)
         enc.close()
 
 
@@ -79,23 +53,10 @@ def test_movie_paced_batches_equal_the_oracle(native, O, oracle_tables, device_t
     got = ops.cpu().numpy()
     four = 0
     for i in range(n):
-        v = O.Video(mode, oracle_tables.get(mode, 5), seed_py=seeds[i][0], seed_np=seeds[i][1])
-        v.set_fourth_offset(True)
-        exp = []
-        for (fr, a, restart, k) in segs:
-            if restart:
-                v.encode_frame(fm[i, fr].numpy(), fa[i, fr].numpy() if fa is not None else None, a)
-            exp.append(v.next(k))
-        exp = np.concatenate(exp)
-        bad = np.nonzero((got[i] != exp).any(axis=1))[0]
-        assert len(bad) == 0, "stream %d: first mismatch at op %d: got %s want %s" % (i, bad[0], got[i][bad[0]], exp[bad[0]])
-        assert (b.enc.get_state(native.STATE_UP_MAIN, i) == v.update_priority(0)).all()
-        assert (b.enc.get_state(native.STATE_MEM_MAIN, i) == v.memory(0)).all()
-        if mode == 1:
-            assert (b.enc.get_state(native.STATE_UP_AUX, i) == v.update_priority(1)).all()
-            assert (b.enc.get_state(native.STATE_MEM_AUX, i) == v.memory(1)).all()
-        cnt = b.enc.get_state(native.STATE_COUNTERS, i)
-        assert (int(cnt[0]), int(cnt[1])) == v.draws()
+        frames = np.stack([fm[i].numpy(), (fa if fa is not None else fm)[i].numpy()], axis=1)      # (HGR: bank 1 is not read)
+        v, exp = H.oracle_run(O, oracle_tables, mode, 5, frames, segs, seeds[i], fourth=True)
+        H.check_ops(got[i], exp, "stream %d" % i)
+        H.check_oracle_state(native, b.enc, i, v, mode, "stream %d" % i)
         four += int((exp[:, 5] != exp[:, 2]).sum())
     b.close()
     assert four > 0     # fourth offsets that are not a copy of the first
@@ -105,26 +66,17 @@ def test_movie_paced_batches_equal_the_oracle(native, O, oracle_tables, device_t
 def test_fourth_offset_leaves_less_error_per_opcode(native, O, device_tables, mode):
     """What the option is for: the same clips, the same opcode budget (three Movie-paced frames), a third more useful
     stores -- every one of 8 clips ends with less perceptual error between screen and target."""
-    from test_gpu_joint import _screen_error
-    import torch
     n = 8
     sched = ([(0, 0, 292), (0, 1, 198), (1, 1, 94), (1, 0, 292), (1, 1, 104), (2, 1, 188), (2, 0, 292), (2, 1, 10)]
              if mode == 1 else [(0, 0, 490), (1, 0, 490), (2, 0, 490)])
-    frames = [_synth(mode, 3, 900 + i, coherent=(i % 2 == 1)) for i in range(n)]
+    frames = [H.synth(mode, 3, 900 + i, coherent=(i % 2 == 1)) for i in range(n)]
+    fm, fa = H.device_frames(mode, frames)
     res = {}
     for fourth in (False, True):
-        t, s = device_tables.get(mode, 5)
-        enc = native.Encoder(mode, t, s, n, dm=device_tables.dm[(mode, 5)])
-        enc.set_fourth_offset(fourth)
-        fr = np.stack(frames)
-        fm = torch.from_numpy(np.ascontiguousarray(fr[:, :, 0])).cuda()
-        fa = torch.from_numpy(np.ascontiguousarray(fr[:, :, 1])).cuda() if mode == 1 else None
-        st = [_seed_states(O, i + 1, i + 1) for i in range(n)]
-        enc.set_state_all(native.STATE_RNG_PY, np.stack([py for py, _ in st]))
-        enc.set_state_all(native.STATE_RNG_NP, np.stack([npw for _, npw in st]))
-        enc.encode(fm, fa, [(int(f), int(a), 1, int(k)) for (f, a, k) in sched])
+        enc = H.make_encoder(native, device_tables, mode, n_streams=n, fourth=fourth, rng=[(i + 1, i + 1) for i in range(n)], O=O)
+        enc.encode(fm, fa, H.segments(sched))
         enc.check()
-        res[fourth] = _screen_error(native, device_tables, mode, enc, frames, 2, n)
+        res[fourth] = H.screen_error(native, device_tables, mode, enc, frames, 2, n)
         enc.close()
     assert (res[True] < res[False]).all(), (res[True], res[False])
     gain = 1.0 - res[True].sum() / res[False].sum()
@@ -141,42 +93,30 @@ def test_team_kernel_to_exhaustion_on_picture_like_input(native, O, oracle_table
     n, nf = 4, 2
     fm, fa = stream_batch.synth_frames_img(n, nf, mode == 1, seed=31, device="cpu")
     sched = [(0, 0, 1, 2500), (0, 0, 0, 2500), (1, 0, 1, 3000), (1, 0, 0, 3000)]
-    enc = _encoder(native, device_tables, mode, 5, n, kernel="team")
-    enc.set_fourth_offset(fourth)
     seeds = [(i + 3, i + 9) for i in range(n)]
-    for i, (sp, sn) in enumerate(seeds):
-        enc.set_state(native.STATE_RNG_PY, O.mt_seed_py(sp).state_words(), i)
-        enc.set_state(native.STATE_RNG_NP, O.mt_seed_np(sn).state_words(), i)
+    enc = H.make_encoder(native, device_tables, mode, n_streams=n, dw=True, kernel="team", prefix=True, fourth=fourth, rng=seeds, O=O)
     got = enc.encode(fm.cuda(), fa.cuda() if fa is not None else None, sched).cpu().numpy()
     enc.check()
     for i in range(n):
-        v = O.Video(mode, oracle_tables.get(mode, 5), seed_py=seeds[i][0], seed_np=seeds[i][1])
-        v.set_fourth_offset(fourth)
-        exp = []
-        for (fr, a, restart, k) in sched:
-            if restart:
-                v.encode_frame(fm[i, fr].numpy(), fa[i, fr].numpy() if fa is not None else None, a)
-            exp.append(v.next(k))
-        exp = np.concatenate(exp)
-        bad = np.nonzero((got[i] != exp).any(axis=1))[0]
-        assert len(bad) == 0, "stream %d: first mismatch at op %d: got %s want %s" % (i, bad[0], got[i][bad[0]], exp[bad[0]])
-        assert v.out_of_work(0) and enc.get_state(native.STATE_OUT_OF_WORK, i)[0] == 1
-        assert (enc.get_state(native.STATE_UP_MAIN, i) == v.update_priority(0)).all()
+        frames = np.stack([fm[i].numpy(), (fa if fa is not None else fm)[i].numpy()], axis=1)      # (HGR: bank 1 is not read)
+        v, exp = H.oracle_run(O, oracle_tables, mode, 5, frames, sched, seeds[i], fourth=fourth)
+        H.check_ops(got[i], exp, "stream %d" % i)
+        assert v.out_of_work(0)
+        H.check_oracle_state(native, enc, i, v, mode, "stream %d" % i)
     enc.close()
 
 
 def test_option_rules(native, device_tables):
     """Off unless asked for; needs the split store table (dm); together with the joint content choice since round 6, in
     either order (tests/test_gpu_joint.py holds the pair to the oracle's definition)."""
-    t, s = device_tables.get(1, 5)
-    enc = native.Encoder(1, t, s, 1, dm=device_tables.dm[(1, 5)])
-    enc.set_fourth_offset(True)
+    enc = H.make_encoder(native, device_tables, 1)
+    enc.set_fourth_offset(True)                # (the order of these calls is what is tested: made here, not by the harness)
     enc.set_content_choice(True)
     enc.set_fourth_offset(False)
     enc.set_content_choice(True)
     enc.set_fourth_offset(True)
     enc.close()
-    enc = native.Encoder(1, t, s, 1)          # no dm: workgroup kernel only
+    enc = H.make_encoder(native, device_tables, 1, dm=False)          # no dm: workgroup kernel only
     with pytest.raises(native.IIVError):
         enc.set_fourth_offset(True)
     enc.close()
@@ -196,7 +136,7 @@ def test_dropin_video_fourth_offset(O, oracle_tables):
         input_frame_rate = 30.0
 
     mode = 1
-    frames = _synth(mode, 2, 51)
+    frames = H.synth(mode, 2, 51)
     random.seed(4)
     np.random.seed(4)
     v = video.Video(FG(), 14700.0, mode=video_mode.VideoMode.DHGR, palette=palette.Palette.NTSC, fourth_offset=True)

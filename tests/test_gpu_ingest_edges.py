@@ -12,6 +12,7 @@ tests/test_ingest_model.py holds to an independent model of the contract on the 
 import numpy as np
 import pytest
 
+from device_guards import guarded, guards_kept
 import ingest_model as M
 from ingest_model import NAMES, frames_of, palette
 
@@ -57,17 +58,6 @@ def _batch(O, mode, dither):
     return (_cache["frames"],) + _cache[key]
 
 
-def _guarded(torch, n_bytes, lead, trail):
-    """a buffer of GUARD bytes and the view of n_bytes that starts `lead` bytes into it"""
-    buf = torch.full((lead + n_bytes + trail,), GUARD, dtype=torch.uint8, device="cuda")
-    return buf, buf[lead:lead + n_bytes]
-
-
-def _assert_guard_kept(buf, lead, n_bytes):
-    b = buf.cpu().numpy()
-    assert (b[:lead] == GUARD).all() and (b[lead + n_bytes:] == GUARD).all()
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("name", NAMES)
@@ -97,8 +87,8 @@ def test_frame_counts(native, O, mode, dither, n):
     import torch
     frames, em, ea = _batch(O, mode, dither)
     dev = torch.from_numpy(frames[:n]).cuda()
-    mbuf, mview = _guarded(torch, n * 8192, 0, 8192)
-    abuf, aview = _guarded(torch, n * 8192, 0, 8192)
+    mbuf, mview = guarded(n * 8192, 0, 8192, GUARD)
+    abuf, aview = guarded(n * 8192, 0, 8192, GUARD)
     native.frames_to_memory_maps(mode, O.PALETTE_RGB[5], dev, dither, out=(mview, aview))
     torch.cuda.synchronize()
     got = mbuf.cpu().numpy().reshape(n + 1, 32, 256)
@@ -154,20 +144,20 @@ def test_output_offsets(native, O, mode, dither):
     frames, em, ea = _batch(O, mode, dither)
     dev = torch.from_numpy(frames[:n]).cuda()
     for om, oa in ((8, 24), (24, 8)):
-        mbuf, mview = _guarded(torch, n * 8192, om, 40)
-        abuf, aview = _guarded(torch, n * 8192, oa, 40)
+        mbuf, mview = guarded(n * 8192, om, 40, GUARD)
+        abuf, aview = guarded(n * 8192, oa, 40, GUARD)
         assert mview.data_ptr() % 16 == 8 and aview.data_ptr() % 16 == 8
         native.frames_to_memory_maps(mode, O.PALETTE_RGB[5], dev, dither, out=(mview.view(n, 32, 256), aview.view(n, 32, 256)))
         torch.cuda.synchronize()
         got = mview.cpu().numpy().reshape(n, 32, 256)
         for i in range(n):
             assert (got[i] == em[i]).all(), (mode, dither, om, i, int((got[i] != em[i]).sum()))
-        _assert_guard_kept(mbuf, om, n * 8192)
+        assert guards_kept(mbuf, om, n * 8192, GUARD)
         if mode == M.DHGR:
             got = aview.cpu().numpy().reshape(n, 32, 256)
             for i in range(n):
                 assert (got[i] == ea[i]).all(), (mode, dither, oa, i, "aux", int((got[i] != ea[i]).sum()))
-            _assert_guard_kept(abuf, oa, n * 8192)
+            assert guards_kept(abuf, oa, n * 8192, GUARD)
         else:
             assert (abuf.cpu().numpy() == GUARD).all()
 
@@ -184,8 +174,8 @@ def test_misaligned_arguments_are_refused_and_nothing_is_written(native, O, mode
     pal = O.PALETTE_RGB[5]
     src_buf = torch.zeros((n * FRAME_BYTES + 16,), dtype=torch.uint8, device="cuda")
     src_buf[:n * FRAME_BYTES] = torch.from_numpy(frames[:n].reshape(-1)).cuda()
-    mbuf, mview = _guarded(torch, n * 8192, 8, 8)
-    abuf, aview = _guarded(torch, n * 8192, 8, 8)
+    mbuf, mview = guarded(n * 8192, 8, 8, GUARD)
+    abuf, aview = guarded(n * 8192, 8, 8, GUARD)
 
     def untouched():
         torch.cuda.synchronize()
@@ -197,13 +187,13 @@ def test_misaligned_arguments_are_refused_and_nothing_is_written(native, O, mode
             native.frames_to_memory_maps(mode, pal, src, dither, out=(mview, aview))
         assert untouched(), ("source offset", o)
     src = src_buf[:n * FRAME_BYTES].view(n, 192, 280, 3)
-    main4_buf, main4 = _guarded(torch, n * 8192, 4, 4)
+    main4_buf, main4 = guarded(n * 8192, 4, 4, GUARD)
     with pytest.raises(native.IIVError):
         native.frames_to_memory_maps(mode, pal, src, dither, out=(main4, aview))
     torch.cuda.synchronize()
     assert (main4_buf.cpu().numpy() == GUARD).all() and untouched(), "main offset 4"
     if mode == M.DHGR:
-        aux4_buf, aux4 = _guarded(torch, n * 8192, 4, 4)
+        aux4_buf, aux4 = guarded(n * 8192, 4, 4, GUARD)
         with pytest.raises(native.IIVError):
             native.frames_to_memory_maps(mode, pal, src, dither, out=(mview, aux4))
         torch.cuda.synchronize()

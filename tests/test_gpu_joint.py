@@ -7,38 +7,21 @@ the screen for the same number of opcodes -- and that the default stays the refe
 import numpy as np
 import pytest
 
-from test_gpu_encode import _seed_states, _synth
+import encode_harness as H
 
 pytestmark = pytest.mark.gpu
 
 
 def _device(native, device_tables, mode, frames_list, sched, seeds, O, joint, fourth=False):
-    import torch
-    t, s = device_tables.get(mode, 5)
-    n = len(frames_list)
-    enc = native.Encoder(mode, t, s, n, dm=device_tables.dm[(mode, 5)])
-    enc.set_content_choice(joint)
-    enc.set_fourth_offset(fourth)
-    fr = np.stack(frames_list)
-    fm = torch.from_numpy(np.ascontiguousarray(fr[:, :, 0])).cuda()
-    fa = torch.from_numpy(np.ascontiguousarray(fr[:, :, 1])).cuda() if mode == 1 else None
-    st = [_seed_states(O, a, b) for a, b in seeds]
-    enc.set_state_all(native.STATE_RNG_PY, np.stack([py for py, _ in st]))
-    enc.set_state_all(native.STATE_RNG_NP, np.stack([npw for _, npw in st]))
-    ops = enc.encode(fm, fa, [(int(f), int(a), 1, int(k)) for (f, a, k) in sched])
+    enc = H.make_encoder(native, device_tables, mode, n_streams=len(frames_list), fourth=fourth, joint=joint, rng=seeds, O=O)
+    fm, fa = H.device_frames(mode, frames_list)
+    ops = enc.encode(fm, fa, H.segments(sched))
     enc.check()
     return enc, ops.cpu().numpy()
 
 
 def _oracle(O, oracle_tables, mode, frames, sched, sp, sn, joint, fourth=False):
-    v = O.Video(mode, oracle_tables.get(mode, 5), seed_py=sp, seed_np=sn)
-    v.set_joint(joint)
-    v.set_fourth_offset(fourth)
-    out = []
-    for fi, ia, n in sched:
-        v.encode_frame(frames[fi, 0], frames[fi, 1] if mode == 1 else None, ia)
-        out.append(v.next(int(n)))
-    return v, np.concatenate(out)
+    return H.oracle_run(O, oracle_tables, mode, 5, frames, sched, (sp, sn), fourth=fourth, joint=joint)
 
 
 @pytest.mark.parametrize("fourth", [False, True])
@@ -52,7 +35,7 @@ def test_joint_steps_equal_the_definition(native, O, oracle_tables, device_table
     the fourth offset per opcode (IIV_OPT_FOURTH_OFFSET: the joint score then takes three deltas)."""
     n = 4
     sched = [(0, 0, 60), (0, 1 if mode == 1 else 0, 45), (1, 0, 70), (1, 1 if mode == 1 else 0, 1), (2, 0, 40)]
-    frames = [_synth(mode, 3, 300 + i, coherent=(i % 2 == 1)) for i in range(n)]
+    frames = [H.synth(mode, 3, 300 + i, coherent=(i % 2 == 1)) for i in range(n)]
     seeds = [(i + 5, 70 + i) for i in range(n)]
     enc, got = _device(native, device_tables, mode, frames, sched, seeds, O, impl, fourth)
     differs_from_greedy = 0
@@ -61,35 +44,12 @@ def test_joint_steps_equal_the_definition(native, O, oracle_tables, device_table
         assert ((o[:, 1:] != o[:, :-1]).sum(axis=1) + 1).max() == 4
     for i in range(n):
         v, exp = _oracle(O, oracle_tables, mode, frames[i], sched, *seeds[i], True, fourth)
-        bad = np.nonzero((got[i] != exp).any(axis=1))[0]
-        assert len(bad) == 0, "stream %d: first mismatch at op %d: got %s want %s" % (i, bad[0], got[i][bad[0]], exp[bad[0]])
-        assert (enc.get_state(native.STATE_MEM_MAIN, i) == v.memory(0)).all()
-        assert (enc.get_state(native.STATE_UP_MAIN, i) == v.update_priority(0)).all()
-        if mode == 1:
-            assert (enc.get_state(native.STATE_MEM_AUX, i) == v.memory(1)).all()
-            assert (enc.get_state(native.STATE_UP_AUX, i) == v.update_priority(1)).all()
-        assert (enc.get_state(native.STATE_PACKED, i) == v.packed).all()
-        cnt = enc.get_state(native.STATE_COUNTERS, i)
-        assert (int(cnt[0]), int(cnt[1])) == v.draws()
+        H.check_ops(got[i], exp, "stream %d" % i)
+        H.check_oracle_state(native, enc, i, v, mode, "stream %d" % i)
         _, greedy = _oracle(O, oracle_tables, mode, frames[i], sched, *seeds[i], False, fourth)
         differs_from_greedy += int((greedy != exp).any())
     enc.close()
     assert differs_from_greedy == n          # the mode really does something else
-
-
-def _screen_error(native, device_tables, mode, enc, frames, last, n):
-    """sum of Bitmap.diff_weights(current screen -> target frame `last`) over both banks, per stream"""
-    import torch
-    t, _ = device_tables.get(mode, 5)
-    tot = np.zeros(n, np.int64)
-    for i in range(n):
-        cur_m = enc.get_state(native.STATE_MEM_MAIN, i)
-        cur_a = enc.get_state(native.STATE_MEM_AUX, i) if mode == 1 else None
-        src = native.pack(mode, cur_m[None], cur_a[None] if cur_a is not None else None)
-        tgt = native.pack(mode, frames[i][last, 0][None], frames[i][last, 1][None] if mode == 1 else None)
-        for ia in ((0, 1) if mode == 1 else (0,)):
-            tot[i] += int(native.diff_weights(mode, t, src, tgt, ia).sum())
-    return tot
 
 
 @pytest.mark.parametrize("mode", [1, 0])
@@ -102,12 +62,12 @@ def test_joint_leaves_less_error_per_opcode(native, O, device_tables, mode):
     n = 8
     sched = ([(0, 0, 292), (0, 1, 198), (1, 1, 94), (1, 0, 292), (1, 1, 104), (2, 1, 188), (2, 0, 292), (2, 1, 10)]
              if mode == 1 else [(0, 0, 490), (1, 0, 490), (2, 0, 490)])
-    frames = [_synth(mode, 3, 900 + i, coherent=(i % 2 == 1)) for i in range(n)]
+    frames = [H.synth(mode, 3, 900 + i, coherent=(i % 2 == 1)) for i in range(n)]
     seeds = [(i + 1, i + 1) for i in range(n)]
     res = {}
     for joint in (False, True):
         enc, ops = _device(native, device_tables, mode, frames, sched, seeds, O, joint)
-        res[joint] = _screen_error(native, device_tables, mode, enc, frames, 2, n)
+        res[joint] = H.screen_error(native, device_tables, mode, enc, frames, 2, n)
         enc.close()
     assert (res[True] < res[False]).all(), (res[True], res[False])
     gain = 1.0 - res[True].sum() / res[False].sum()
@@ -129,32 +89,23 @@ def test_joint_runs_past_the_list_into_the_bag(native, O, oracle_tables, device_
     enc, got = _device(native, device_tables, mode, frames, sched, seeds, O, impl, fourth)
     for i in range(n):
         v, exp = _oracle(O, oracle_tables, mode, frames[i], sched, *seeds[i], True, fourth)
-        bad = np.nonzero((got[i] != exp).any(axis=1))[0]
-        assert len(bad) == 0, "stream %d: first mismatch at op %d: got %s want %s" % (i, bad[0], got[i][bad[0]], exp[bad[0]])
-        assert (enc.get_state(native.STATE_UP_MAIN, i) == v.update_priority(0)).all()
-        assert (enc.get_state(native.STATE_MEM_MAIN, i) == v.memory(0)).all()
+        H.check_ops(got[i], exp, "stream %d" % i)
+        H.check_oracle_state(native, enc, i, v, mode, "stream %d" % i)
     enc.close()
 
 
 def test_default_is_the_reference_step(native, O, oracle_tables, device_tables):
     """The flag is off unless asked for, and switching it off again restores the reference's stream."""
     mode = 1
-    frames = [_synth(mode, 1, 41)]
+    frames = [H.synth(mode, 1, 41)]
     sched = [(0, 0, 80)]
     enc, a = _device(native, device_tables, mode, frames, sched, [(2, 3)], O, False)
     enc.close()
     _, exp = _oracle(O, oracle_tables, mode, frames[0], sched, 2, 3, False)
     assert (a[0] == exp).all()
-    import torch
-    t, s = device_tables.get(mode, 5)
-    enc = native.Encoder(mode, t, s, 1, dm=device_tables.dm[(mode, 5)])
-    enc.set_content_choice(True)
-    enc.set_content_choice(False)
-    py, npw = _seed_states(O, 2, 3)
-    enc.set_state(native.STATE_RNG_PY, py)
-    enc.set_state(native.STATE_RNG_NP, npw)
-    fm = torch.from_numpy(frames[0][None, :, 0].copy()).cuda()
-    fa = torch.from_numpy(frames[0][None, :, 1].copy()).cuda()
+    enc = H.make_encoder(native, device_tables, mode, joint=True, rng=[(2, 3)], O=O)
+    enc.set_content_choice(False)      # (switched off again: the call under test)
+    fm, fa = H.device_frames(mode, frames)
     assert (enc.encode(fm, fa, [(0, 0, 1, 80)]).cpu().numpy()[0] == exp).all()
     enc.close()
 
@@ -175,7 +126,7 @@ def test_dropin_video_joint_content(O, oracle_tables):
         input_frame_rate = 30
 
     mode = 1
-    frames = _synth(mode, 2, 4242)
+    frames = H.synth(mode, 2, 4242)
     sched = [(0, 0, 70), (0, 1, 30), (1, 1, 25)]
     random.seed(9)
     np.random.seed(11)
@@ -208,8 +159,7 @@ def test_dropin_video_joint_content(O, oracle_tables):
 def test_options_that_need_the_diff_matrix_say_so(native, device_tables):
     """An encoder made without dm (caller's own tables) has no split tables: the joint content choice,
     the split diff-weight mode and the one-wave / team kernels refuse instead of reading nothing."""
-    t, s = device_tables.get(1, 5)
-    enc = native.Encoder(1, t, s, 1)
+    enc = H.make_encoder(native, device_tables, 1, dm=False)
     for call in (lambda: enc.set_content_choice(True), lambda: enc.set_diff_weights_mode("split"),
                  lambda: enc.set_greedy_kernel(True), lambda: enc.set_greedy_kernel("team")):
         with pytest.raises(native.IIVError):

@@ -11,6 +11,7 @@ these inputs do reach the limit.  Every comparison is exact."""
 import numpy as np
 import pytest
 
+import encode_harness as H
 import limit_matrices as LM
 
 pytestmark = pytest.mark.gpu
@@ -169,25 +170,16 @@ def _ran(kernel, forms):
 
 
 def _device_run(native, O, mode, name, frames, parts, kernel=None, dw=None, fourth=False, joint=False, seeds=(5, 6), write_back=()):
-    """One encoder stream over the parts of a schedule -> (opcodes, [priorities of every bank after each part], the final
-    memory of every bank, draw counters, launch forms).  Reading the priorities runs materialise_up_kernel (16-bit copy ->
+    """One encoder stream over the parts of a schedule -> (opcodes, [priorities of every bank after each part], the encoder
+    behind the last part -- _compare reads its state and closes it --, None, launch forms).  Reading the priorities runs materialise_up_kernel (16-bit copy ->
     int32 array); after the parts listed in write_back exactly what was read is written back with set_state, which runs
     materialise_up_kernel, the copy, and compact_up_kernel (int32 array -> 16-bit copy): nothing is planted, the kernels
     after it read what compact_up_kernel left."""
-    import torch
-    table, dense = device_tables(native, mode, name)
-    enc = native.Encoder(mode, table, dense, 1, dm=LM.matrix(mode, name))
-    if kernel is not None:
-        enc.set_greedy_kernel(kernel)
-    if dw is not None:
-        enc.set_diff_weights_mode(dw)
-    enc.set_fourth_offset(fourth)
-    enc.set_content_choice(joint)
-    enc.set_state(native.STATE_RNG_PY, O.mt_seed_py(seeds[0]).state_words())
-    enc.set_state(native.STATE_RNG_NP, O.mt_seed_np(seeds[1]).state_words())
+    named = {k: v for k, v in (("kernel", kernel), ("dw", dw)) if v is not None}
+    enc = H.make_encoder(native, device_tables(native, mode, name) + (LM.matrix(mode, name),), mode, fourth=fourth, joint=joint,
+                         rng=[seeds], O=O, **named)
     enc.profile(True)
-    fm = torch.from_numpy(np.ascontiguousarray(frames[None, :, 0])).cuda()
-    fa = torch.from_numpy(np.ascontiguousarray(frames[None, :, 1])).cuda() if mode == LM.DHGR else None
+    fm, fa = H.device_frames(mode, [frames])
     ops, ups = [], []
     for part in parts:
         got = enc.encode(fm, fa, part)
@@ -197,24 +189,17 @@ def _device_run(native, O, mode, name, frames, parts, kernel=None, dw=None, four
         if len(ups) - 1 in write_back:
             for b in banks(mode):
                 enc.set_state(native.STATE_UP_MAIN + b, ups[-1][b])
-    mem = [enc.get_state(native.STATE_MEM_MAIN + b) for b in banks(mode)]
-    cnt = enc.get_state(native.STATE_COUNTERS)
-    forms = enc.launch_forms()
-    enc.close()
-    return np.concatenate(ops), ups, mem, (int(cnt[0]), int(cnt[1])), forms
+    return np.concatenate(ops), ups, enc, None, enc.launch_forms()
 
 
-def _compare(mode, tag, dev, v, want_ops, want_ups=None):
-    ops, ups, mem, draws, _ = dev
-    bad = np.nonzero((ops != want_ops).any(axis=1))[0]
-    assert len(bad) == 0, "%s: first mismatch at op %d of %d: got %s want %s" % (tag, bad[0], len(ops), ops[bad[0]], want_ops[bad[0]])
+def _compare(native, mode, tag, dev, v, want_ops, want_ups=None):
+    ops, ups, enc, _, _ = dev
+    H.check_ops(ops, want_ops, str(tag))
     for b in banks(mode):
-        if want_ups is not None:
-            for i, w in enumerate(want_ups):
-                assert np.array_equal(ups[i][b], w[b]), (tag, "priorities after part", i, "bank", b)
-        assert np.array_equal(ups[-1][b], v.update_priority(b)), (tag, "priorities", b)
-        assert np.array_equal(mem[b], v.memory(b)), (tag, "memory", b)
-    assert draws == v.draws(), tag
+        for i, w in enumerate(want_ups or ()):
+            assert np.array_equal(ups[i][b], w[b]), (tag, "priorities after part", i, "bank", b)
+    H.check_oracle_state(native, enc, 0, v, mode, str(tag))
+    enc.close()
 
 
 @pytest.mark.parametrize("name", LM.MATRICES)
@@ -233,14 +218,14 @@ def test_encode_at_the_limit_in_every_kernel_form(native, O, mode, name):
         dev = _device_run(native, O, mode, name, frames, [sched], kernel, dw)
         assert _ran(kernel, dev[4]), (kernel, dw, dev[4])
         ran |= {k for k, n in dev[4].items() if n}
-        _compare(mode, (mode, name, kernel, dw), dev, v, want)
+        _compare(native, mode, (mode, name, kernel, dw), dev, v, want)
     assert ran == {"plain", "shared", "team", "workgroup"}
     v4, want4 = LM.oracle_run(O, mode, otab, frames, sched, fourth=True)
     assert (want4[:, 5] != want4[:, 2]).any()                       # fourth offsets that are no copy of the first
     for kernel in FOURTH_KERNELS:
         dev = _device_run(native, O, mode, name, frames, [sched], kernel, fourth=True)
         assert _ran(kernel, dev[4]), (kernel, "fourth", dev[4])
-        _compare(mode, (mode, name, kernel, "fourth"), dev, v4, want4)
+        _compare(native, mode, (mode, name, kernel, "fourth"), dev, v4, want4)
     short = LM.encode_schedule(mode, cap=90)                        # (the oracle's joint step is slow)
     for fourth in (False, True):
         vj, wantj = LM.oracle_run(O, mode, otab, frames, short, fourth=fourth, joint=True)
@@ -248,7 +233,7 @@ def test_encode_at_the_limit_in_every_kernel_form(native, O, mode, name):
             if f == fourth:
                 dev = _device_run(native, O, mode, name, frames, [short], fourth=fourth, joint=joint)
                 assert _ran(False, dev[4]), (joint, fourth, dev[4])           # the joint choice's home is the workgroup kernel
-                _compare(mode, (mode, name, "joint", joint, fourth), dev, vj, wantj)
+                _compare(native, mode, (mode, name, "joint", joint, fourth), dev, vj, wantj)
 
 
 @pytest.mark.parametrize("name", LM.MATRICES)
@@ -264,12 +249,12 @@ def test_stored_values_at_the_limit_in_every_kernel_form(native, O, mode, name):
     for kernel, dw in KERNEL_FORMS:
         dev = _device_run(native, O, mode, name, frames, [sched], kernel, dw)
         assert _ran(kernel, dev[4]), (kernel, dw, dev[4])
-        _compare(mode, (mode, name, kernel, dw), dev, v, want)
+        _compare(native, mode, (mode, name, kernel, dw), dev, v, want)
     v4, want4 = LM.oracle_run(O, mode, otab, frames, sched, fourth=True)
     for kernel in FOURTH_KERNELS:
         dev = _device_run(native, O, mode, name, frames, [sched], kernel, fourth=True)
         assert _ran(kernel, dev[4]), (kernel, "fourth", dev[4])
-        _compare(mode, (mode, name, kernel, "fourth"), dev, v4, want4)
+        _compare(native, mode, (mode, name, kernel, "fourth"), dev, v4, want4)
 
 
 # ---- 5. priorities that cross 16 bits on the device
@@ -300,4 +285,4 @@ def test_priorities_cross_16_bits_by_the_prologues_own_additions(native, O, mode
     for kernel in (True, "shared", "team", False):
         dev = _device_run(native, O, mode, name, frames, parts, kernel, write_back=(1,))
         assert _ran(kernel, dev[4]), (kernel, dev[4])
-        _compare(mode, (mode, name, kernel), dev, v, want, want_ups)
+        _compare(native, mode, (mode, name, kernel), dev, v, want, want_ups)

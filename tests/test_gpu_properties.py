@@ -5,47 +5,30 @@ batch size."""
 import numpy as np
 import pytest
 
+import encode_harness as H
+
 pytestmark = pytest.mark.gpu
 
 HOLES = (np.arange(256) & 127) >= 120
 
 
-def _seed_states(O, a, b):
-    return O.mt_seed_py(a).state_words(), O.mt_seed_np(b).state_words()
-
-
 def _encode(native, device_tables, mode, frames, sched, seeds, O, wave=None, prefix=True, init=None):
     """frames: (n_streams, n_frames, 2, 32, 256)."""
-    import torch
-    t, s = device_tables.get(mode)
-    n = frames.shape[0]
-    enc = native.Encoder(mode, t, s, n, dm=device_tables.dm[(mode, 5)])
-    enc.set_greedy_kernel(wave)
-    enc.set_prefix_sort(prefix)
-    for i, (a, b) in enumerate(seeds):
-        py, npw = _seed_states(O, a, b)
+    enc = H.make_encoder(native, device_tables, mode, n_streams=frames.shape[0], kernel=wave, prefix=prefix)
+    for i, (a, b) in enumerate(seeds):      # (one set_state per stream, on purpose: the other tests upload with set_state_all)
+        py, npw = H.seed_states(O, a, b)
         enc.set_state(native.STATE_RNG_PY, py, i)
         enc.set_state(native.STATE_RNG_NP, npw, i)
     if init:
         init(enc)
-    fm = torch.from_numpy(np.ascontiguousarray(frames[:, :, 0])).cuda()
-    fa = torch.from_numpy(np.ascontiguousarray(frames[:, :, 1])).cuda() if mode == 1 else None
+    fm, fa = H.device_frames(mode, list(frames))
     ops = enc.encode(fm, fa, sched)
     enc.check()
     return enc, ops.cpu().numpy()
 
 
 def _oracle(O, oracle_tables, mode, frames1, sched, seed, init=None):
-    v = O.Video(mode, oracle_tables.get(mode), seed_py=seed[0], seed_np=seed[1])
-    if init:
-        init(v)
-    out = []
-    for (f, ia, restart, n) in sched:
-        if restart:
-            v.encode_frame(frames1[f, 0], frames1[f, 1] if mode == 1 else None, ia)
-        if n:
-            out.append(v.next(n))
-    return v, (np.concatenate(out) if out else np.zeros((0, 6), np.uint8))
+    return H.oracle_run(O, oracle_tables, mode, 5, frames1, sched, seed, init=init)
 
 
 @pytest.mark.parametrize("wave", [True, False, "shared"])
@@ -271,14 +254,8 @@ def test_bench_batch_size_sampled_against_the_oracle(native, O, oracle_tables, d
             b.close()
         assert np.array_equal(res["plain"], res["shared"]), fourth
         for j, i in enumerate(sample):
-            v = O.Video(1, oracle_tables.get(1), seed_py=seeds[i][0], seed_np=seeds[i][1])
-            v.set_fourth_offset(fourth)
-            exp = []
-            for (f, ia, restart, n) in segs:
-                if restart:
-                    v.encode_frame(tm[j, f], ta[j, f], ia)
-                exp.append(v.next(n))
-            assert np.array_equal(res["shared"][i], np.concatenate(exp)), (fourth, i)
+            _, exp = H.oracle_run(O, oracle_tables, 1, 5, np.stack([tm[j], ta[j]], axis=1), segs, seeds[i], fourth=fourth)
+            assert np.array_equal(res["shared"][i], exp), (fourth, i)
 
 
 @pytest.mark.parametrize("kern", ["plain", "shared"])

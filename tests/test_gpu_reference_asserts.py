@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 
 import assert_inputs as A
-import mt_model
+import encode_harness as H
 
 pytestmark = pytest.mark.gpu
 
@@ -37,25 +37,11 @@ class Batch:
     """an encoder over one clip per stream, every stream seeded as its oracle run is"""
 
     def __init__(self, native, O, device_tables, mode, clips, seeds, kernel=None, fourth=False, joint=False, dw=None):
-        import torch
         self.native, self.mode, self.n, self.kernel = native, mode, len(clips), kernel
-        t, s = device_tables.get(mode)
-        self.enc = enc = native.Encoder(mode, t, s, self.n, dm=device_tables.dm[(mode, 5)])
-        if kernel is not None:
-            enc.set_greedy_kernel(kernel)
-        if dw is not None:
-            enc.set_diff_weights_mode(dw)
-        enc.set_fourth_offset(fourth)
-        enc.set_content_choice(joint)
-        enc.set_state_all(native.STATE_RNG_PY, np.stack([O.mt_seed_py(a).state_words() for a, _ in seeds]))
-        enc.set_state_all(native.STATE_RNG_NP, np.stack([O.mt_seed_np(b).state_words() for _, b in seeds]))
-        enc.profile(True)
-        nf = max(len(c) for c in clips)
-        fr = np.zeros((self.n, nf, 2, 32, 256), np.uint8)
-        for i, c in enumerate(clips):
-            fr[i, :len(c)] = c
-        self.fm = torch.from_numpy(np.ascontiguousarray(fr[:, :, 0])).cuda()
-        self.fa = torch.from_numpy(np.ascontiguousarray(fr[:, :, 1])).cuda() if mode == A.DHGR else None
+        named = {k: v for k, v in (("kernel", kernel), ("dw", dw)) if v is not None}
+        self.enc = H.make_encoder(native, device_tables, mode, 5, self.n, fourth=fourth, joint=joint, rng=list(seeds), O=O, **named)
+        self.enc.profile(True)
+        self.fm, self.fa = H.device_frames(mode, clips)
 
     def encode(self, scheds):
         ops, _ = self.enc.encode_streams(self.fm, self.fa, scheds)
@@ -67,14 +53,13 @@ class Batch:
         rc = self.native.lib().iiv_encoder_check(self.enc._h, C.byref(bad), self.native.stream_ptr())
         return rc, bad.value, self.native.lib().iiv_last_error().decode("utf-8", "replace") if rc else ""
 
-    def state(self, i, full=True):
-        n, e = self.native, self.enc
-        st = {"mem": [e.get_state(n.STATE_MEM_MAIN + b, i) for b in A.banks(self.mode)], "packed": e.get_state(n.STATE_PACKED, i)}
-        if full:
-            st.update(up=[e.get_state(n.STATE_UP_MAIN + b, i) for b in A.banks(self.mode)],
-                      draws=tuple(int(x) for x in e.get_state(n.STATE_COUNTERS, i)[:2]),
-                      py=mt_model.canonical(e.get_state(n.STATE_RNG_PY, i)), np=mt_model.canonical(e.get_state(n.STATE_RNG_NP, i)))
-        return st
+    def state(self, i):
+        """stream i's state as the device holds it now (encode_harness.State)"""
+        return H.device_state(self.native, self.enc, i, self.mode)
+
+    def same_state(self, i, want, tag, fields=H.FIELDS):
+        """stream i against an oracle's (or the stream's own earlier) State"""
+        H.check_oracle_state(self.native, self.enc, i, want, self.mode, str(tag), fields)
 
     def close(self):
         """the kernel asked for is the one that ran, and no other (a silent fall-back must not pass), in every test"""
@@ -84,30 +69,8 @@ class Batch:
         self.enc.close()
 
 
-def oracle_state(v, mode, full=True):
-    st = {"mem": [v.memory(b).copy() for b in A.banks(mode)], "packed": v.packed.copy()}
-    if full:
-        st.update(up=[v.update_priority(b).copy() for b in A.banks(mode)], draws=v.draws(),
-                  py=mt_model.canonical(v.rng_py().state_words()), np=mt_model.canonical(v.rng_np().state_words()))
-    return st
-
-
-def same_state(got, want, tag):
-    for k, w in want.items():
-        g = got[k]
-        if isinstance(w, list):
-            for b in range(len(w)):
-                assert np.array_equal(g[b], w[b]), (tag, k, "bank", b)
-        elif isinstance(w, tuple):
-            assert g == w, (tag, k, g, w)
-        else:
-            assert np.array_equal(g, w), (tag, k)
-
-
-def same_ops(got, want, tag):
-    assert got.shape == want.shape, (tag, got.shape, want.shape)
-    bad = np.nonzero((got != want).any(axis=1))[0]
-    assert len(bad) == 0, "%s: first mismatch at op %d of %d: got %s want %s" % (tag, bad[0], len(want), got[bad[0]], want[bad[0]])
+# a stream that an assert stopped: the reference raises out of the step, so only what the steps before it stored is defined
+STOPPED = ("mem", "packed")
 
 
 def _otab(oracle_tables, mode):
@@ -136,7 +99,7 @@ def test_accepted_inputs_equal_the_oracle_in_every_form(native, O, oracle_tables
         frames, sched, seeds = _accepted(O, table, mode, name, fourth=fourth)
         v, want, code = A.oracle_run(O, mode, table, frames, sched, seeds, fourth=fourth)
         assert code == 0
-        wstate = oracle_state(v, mode)
+        wstate = H.oracle_state(v, mode)
         for kernel, f in FORMS:
             if f != fourth:
                 continue
@@ -146,8 +109,8 @@ def test_accepted_inputs_equal_the_oracle_in_every_form(native, O, oracle_tables
             forms = b.enc.launch_forms()
             assert A.ran(kernel, forms), (kernel, fourth, forms)
             ran |= {k for k, n in forms.items() if n}
-            same_ops(ops[0], want, (name, mode, kernel, fourth))
-            same_state(b.state(0), wstate, (name, mode, kernel, fourth))
+            H.check_ops(ops[0], want, (name, mode, kernel, fourth))
+            b.same_state(0, wstate, (name, mode, kernel, fourth))
             b.close()
         framesj, schedj, seeds = _accepted(O, table, mode, name, cap=JOINT_CAP, fourth=fourth, joint=True)
         vj, wantj, code = A.oracle_run(O, mode, table, framesj, schedj, seeds, fourth=fourth, joint=True)
@@ -157,8 +120,8 @@ def test_accepted_inputs_equal_the_oracle_in_every_form(native, O, oracle_tables
             ops = b.encode([schedj])
             assert b.check() == (0, -1, ""), (joint, fourth)
             assert A.ran(False, b.enc.launch_forms()), (joint, fourth, b.enc.launch_forms())
-            same_ops(ops[0], wantj, (name, mode, "joint", joint, fourth))
-            same_state(b.state(0), oracle_state(vj, mode), (name, mode, "joint", joint, fourth))
+            H.check_ops(ops[0], wantj, (name, mode, "joint", joint, fourth))
+            b.same_state(0, H.oracle_state(vj, mode), (name, mode, "joint", joint, fourth))
             b.close()
     assert ran == {"plain", "shared", "team", "workgroup"}
 
@@ -180,11 +143,11 @@ def _four_streams(O, oracle_tables, fourth):
     runs = []
     for i in range(4):
         v, ops1, code1 = A.oracle_run(O, A.DHGR, table, clips[i], calls[0][i], seeds[i], fourth=fourth)
-        st1 = oracle_state(v, A.DHGR)
+        st1 = H.oracle_state(v, A.DHGR)
         ops2, code2, st2 = None, code1, st1
         if not code1:
             _, ops2, code2 = A.oracle_run(O, A.DHGR, table, clips[i], calls[1][i], seeds[i], fourth=fourth, v=v)
-            st2 = oracle_state(v, A.DHGR)
+            st2 = H.oracle_state(v, A.DHGR)
         runs.append(dict(ops=[ops1, ops2], code=[code1, code2], state=[st1, st2]))
     assert [r["code"] for r in runs] == [[0, 0], [A.ERR_PALETTE_BIT] * 2, [0, A.ERR_PALETTE_BIT], [0, 0]]
     assert 30 < len(runs[1]["ops"][0]) < 230 and 0 < len(runs[2]["ops"][1]) < A.LATE_MORE[0][3]
@@ -208,32 +171,32 @@ def test_the_assert_fires_where_the_references_fires(native, O, oracle_tables, d
     _names_stream(native, b.check(), 1, A.MSG_137)
     assert A.ran(kernel, b.enc.launch_forms()), (tag, b.enc.launch_forms())
     n_ok = len(runs[1]["ops"][0])
-    same_ops(ops[1][:n_ok], runs[1]["ops"][0], (tag, "stream 1, the opcodes in front of the assert"))
-    same_state(b.state(1, full=False), {k: runs[1]["state"][0][k] for k in ("mem", "packed")}, (tag, "stream 1 stopped there"))
+    H.check_ops(ops[1][:n_ok], runs[1]["ops"][0], (tag, "stream 1, the opcodes in front of the assert"))
+    b.same_state(1, runs[1]["state"][0], (tag, "stream 1 stopped there"), STOPPED)
     for i in (0, 2, 3):
         want = runs[i]["ops"][0]
-        same_ops(ops[i][:len(want)], want, (tag, "call 1, stream", i))
-        same_state(b.state(i), runs[i]["state"][0], (tag, "call 1, stream", i))
+        H.check_ops(ops[i][:len(want)], want, (tag, "call 1, stream", i))
+        b.same_state(i, runs[i]["state"][0], (tag, "call 1, stream", i))
     # -- c: stream 1 stays out of the next call (which asks it to go on), whatever the others do
     before = b.state(1)
     ops = b.encode(calls[1])
     _names_stream(native, b.check(), 1, A.MSG_137)
-    same_state(b.state(1), before, (tag, "stream 1 after a further call"))
+    b.same_state(1, before, (tag, "stream 1 after a further call"))
     # -- the continuation: stream 2 stops at the oracle's index; 0 and 3 are exact across both calls
     n_ok2 = len(runs[2]["ops"][1])
     assert n_ok2 == A.LATE_MORE_INDEX
-    same_ops(ops[2][:n_ok2], runs[2]["ops"][1], (tag, "stream 2, the opcodes in front of the assert"))
-    same_state(b.state(2, full=False), {k: runs[2]["state"][1][k] for k in ("mem", "packed")}, (tag, "stream 2 stopped there"))
+    H.check_ops(ops[2][:n_ok2], runs[2]["ops"][1], (tag, "stream 2, the opcodes in front of the assert"))
+    b.same_state(2, runs[2]["state"][1], (tag, "stream 2 stopped there"), STOPPED)
     for i in (0, 3):
         want = runs[i]["ops"][1]
-        same_ops(ops[i][:len(want)], want, (tag, "call 2, stream", i))
-        same_state(b.state(i), runs[i]["state"][1], (tag, "call 2, stream", i))
+        H.check_ops(ops[i][:len(want)], want, (tag, "call 2, stream", i))
+        b.same_state(i, runs[i]["state"][1], (tag, "call 2, stream", i))
     # -- and a call that STARTS generators: streams 1 and 2 stay as they are (no prologue runs on them), check() still says 1
     before = [b.state(i) for i in (1, 2)]
     b.encode([[(2, 1, 1, 30)]] * 4)
     _names_stream(native, b.check(), 1, A.MSG_137)
     for k, i in enumerate((1, 2)):
-        same_state(b.state(i), before[k], (tag, "stream %d after a further restart" % i))
+        b.same_state(i, before[k], (tag, "stream %d after a further restart" % i))
     b.close()
 
 
@@ -250,9 +213,9 @@ def test_rollback_clears_the_error_and_the_opcodes_in_front_of_it_are_the_oracle
     assert b.check() == (0, -1, "")
     ops = b.encode([calls[0][0], [calls[0][1][0], (0, 0, 1, n_ok - 30)]])
     assert b.check() == (0, -1, "")
-    same_ops(ops[1][:n_ok], runs[1]["ops"][0], (kernel, "the n_ok opcodes"))
-    same_state(b.state(1), runs[1]["state"][0], (kernel, "the state in front of the assert"))
-    same_ops(ops[0], runs[0]["ops"][0], (kernel, "stream 0"))
+    H.check_ops(ops[1][:n_ok], runs[1]["ops"][0], (kernel, "the n_ok opcodes"))
+    b.same_state(1, runs[1]["state"][0], (kernel, "the state in front of the assert"))
+    H.check_ops(ops[0], runs[0]["ops"][0], (kernel, "stream 0"))
     # one more opcode is the one that asserts
     b.encode([[], [(0, 0, 0, 1)]])
     _names_stream(native, b.check(), 1, A.MSG_137)
@@ -305,8 +268,8 @@ def test_a_byte_in_the_memory_maps_hole_stops_the_generator_before_it_draws(nati
         drawn.append((kernel, before, b.state(1)))
         v, want, code = A.oracle_run(O, mode, table, clip, sched, seeds)
         for i in (0, 2):
-            same_ops(ops[i], want, (kernel, "neighbour", i))
-            same_state(b.state(i), oracle_state(v, mode), (kernel, "neighbour", i))
+            H.check_ops(ops[i], want, (kernel, "neighbour", i))
+            b.same_state(i, H.oracle_state(v, mode), (kernel, "neighbour", i))
         b.close()
     # the oracle agrees: code -1, nothing drawn
     v = A.oracle_video(O, mode, table, seeds)
@@ -325,13 +288,13 @@ def test_a_byte_in_the_memory_maps_hole_stops_the_generator_before_it_draws(nati
             b.enc.set_state(native.STATE_MEM_MAIN + 1 - bank, _hole_map())
             ops = b.encode([sched])
             assert b.check() == (0, -1, ""), kernel
-            same_ops(ops[0], want, (kernel, "other bank's hole"))
-            same_state(b.state(0), oracle_state(v, mode), (kernel, "other bank's hole"))
+            H.check_ops(ops[0], want, (kernel, "other bank's hole"))
+            b.same_state(0, H.oracle_state(v, mode), (kernel, "other bank's hole"))
             b.close()
     # the reference raises in front of its draw (oracle: gen_prologue returns before draw_np): nothing is drawn
     for kernel, before, after in drawn:
-        assert after["draws"] == before["draws"] == (0, 0), (kernel, after["draws"])
-        assert np.array_equal(after["py"], before["py"]) and np.array_equal(after["np"], before["np"]), kernel
+        assert after.draws == before.draws == (0, 0), (kernel, after.draws)
+        assert np.array_equal(after.py, before.py) and np.array_equal(after.np, before.np), kernel
 
 
 # ---- f. video.py:117
@@ -378,12 +341,12 @@ def test_negative_priorities(native, O, oracle_tables, device_tables, mode):
             ops = b.encode([sched] * 2)
             if wcode:
                 _names_stream(native, b.check(), 1, A.MSG_117)
-                assert b.state(1)["draws"] == (0, 0), (kernel, value)          # (raised in front of the draw)
+                assert b.state(1).draws == (0, 0), (kernel, value)          # (raised in front of the draw)
             else:
                 assert b.check() == (0, -1, ""), (kernel, value)
-                same_ops(ops[1], want, (kernel, value, "planted stream"))
-                same_state(b.state(1), oracle_state(vo, mode), (kernel, value, "planted stream"))
-            same_ops(ops[0], clean_ops, (kernel, value, "neighbour"))
+                H.check_ops(ops[1], want, (kernel, value, "planted stream"))
+                b.same_state(1, H.oracle_state(vo, mode), (kernel, value, "planted stream"))
+            H.check_ops(ops[0], clean_ops, (kernel, value, "neighbour"))
             b.close()
             # the byte that equals the target: zeroed by :115, never fires, the opcodes are a clean stream's
             up = np.zeros((32, 256), np.int32)
@@ -392,8 +355,8 @@ def test_negative_priorities(native, O, oracle_tables, device_tables, mode):
             b.enc.set_state(native.STATE_UP_MAIN, up)
             ops = b.encode([sched])
             assert b.check() == (0, -1, ""), (kernel, value)
-            same_ops(ops[0], clean_ops, (kernel, value, "zeroed plant"))
-            same_state(b.state(0), oracle_state(v, mode), (kernel, value, "zeroed plant"))
+            H.check_ops(ops[0], clean_ops, (kernel, value, "zeroed plant"))
+            b.same_state(0, H.oracle_state(v, mode), (kernel, value, "zeroed plant"))
             b.close()
 
 
@@ -439,13 +402,9 @@ def test_errored_streams_in_the_persistent_workgroups_queue(native, O, oracle_ta
     fr[bad] = bad_clip[0]
     fm = torch.from_numpy(np.ascontiguousarray(fr[:, None, 0])).cuda()
     fa = torch.from_numpy(np.ascontiguousarray(fr[:, None, 1])).cuda()
-    t, s = device_tables.get(A.DHGR)
     res = {}
     for kernel in ("plain", "shared"):
-        enc = native.Encoder(A.DHGR, t, s, S, dm=device_tables.dm[(A.DHGR, 5)])
-        enc.set_greedy_kernel(kernel)
-        enc.set_state_all(native.STATE_RNG_PY, np.stack([O.mt_seed_py(a).state_words() for a, _ in seeds]))
-        enc.set_state_all(native.STATE_RNG_NP, np.stack([O.mt_seed_np(c).state_words() for _, c in seeds]))
+        enc = H.make_encoder(native, device_tables, A.DHGR, 5, S, kernel=kernel, rng=seeds, O=O)
         enc.profile(True)
         ops = enc.encode(fm, fa, [(0, 0, 1, K)])
         bad_stream = C.c_int(-1)
@@ -462,11 +421,11 @@ def test_errored_streams_in_the_persistent_workgroups_queue(native, O, oracle_ta
         got = res[kernel][bad[:24]].cpu().numpy()
         for k in range(24):
             want = bad_ops[k % len(bad_seeds)]
-            same_ops(got[k][:len(want)], want, (kernel, "bad stream", bad[k]))
+            H.check_ops(got[k][:len(want)], want, (kernel, "bad stream", bad[k]))
     sample = sorted({0, S - 1} | {i + 1 for i in bad[:14]})
     assert len(sample) == 16
     shared = res["shared"][sample].cpu().numpy()
     for j, i in enumerate(sample):
         _, want, code = A.oracle_run(O, A.DHGR, table, fr[i][None], [(0, 0, 1, K)], seeds[i])
         assert code == 0
-        same_ops(shared[j], want, ("stream", i))
+        H.check_ops(shared[j], want, ("stream", i))

@@ -9,8 +9,8 @@ import random
 import numpy as np
 import pytest
 
+import encode_harness as H
 import reference_corpus as RC
-from test_gpu_encode import _next_draws, _seed_states
 
 pytestmark = pytest.mark.gpu
 
@@ -28,52 +28,17 @@ def _meta(rec):
     return mode, pal, sp, sn, bool(fourth)
 
 
-def _encoder(native, O, device_tables, mode, pal, seeds, recurrence, kernel, prefix, fourth=False):
-    t, s = device_tables.get(mode, pal)
-    enc = native.Encoder(mode, t, s, len(seeds), dm=device_tables.dm[(mode, pal)])
-    enc.set_diff_weights_mode(recurrence)
-    enc.set_greedy_kernel(kernel)
-    enc.set_prefix_sort(prefix)
-    if fourth:
-        enc.set_fourth_offset(True)
-    st = [_seed_states(O, sp, sn) for sp, sn in seeds]
-    enc.set_state_all(native.STATE_RNG_PY, np.stack([py for py, _ in st]))
-    enc.set_state_all(native.STATE_RNG_NP, np.stack([npw for _, npw in st]))
-    return enc
-
-
-def _device_frames(mode, frames_list):
-    """streams' (n_frames, banks, 32, 256) arrays -> (main, aux | None) device tensors (n, max n_frames, 32, 256); a stream
-    with fewer frames is filled up with copies of its last one (its schedule never names them)"""
-    import torch
-    nf = max(len(f) for f in frames_list)
-    fr = np.stack([np.concatenate([f] + [f[-1:]] * (nf - len(f))) for f in frames_list])
-    fm = torch.from_numpy(np.ascontiguousarray(fr[:, :, 0])).cuda()
-    fa = torch.from_numpy(np.ascontiguousarray(fr[:, :, 1])).cuda() if mode == 1 else None
-    return fm, fa
-
-
 def _check_stream(native, O, enc, i, got, rec, what):
-    want = rec["ops"]
-    assert got.shape == want.shape, what
-    bad = np.nonzero((got != want).any(axis=1))[0]
-    assert len(bad) == 0, "%s: first mismatch at op %d of %d: got %s want %s" % (what, bad[0], len(want), got[bad[0]], want[bad[0]])
-    assert (enc.get_state(native.STATE_MEM_MAIN, i) == rec["mem_main"]).all(), what
-    assert (enc.get_state(native.STATE_UP_MAIN, i) == rec["up_main"]).all(), what
-    assert (enc.get_state(native.STATE_PACKED, i) == rec["packed"]).all(), what
-    if int(rec["meta"][0]) == 1:
-        assert (enc.get_state(native.STATE_MEM_AUX, i) == rec["mem_aux"]).all(), what
-        assert (enc.get_state(native.STATE_UP_AUX, i) == rec["up_aux"]).all(), what
-    assert enc.get_state(native.STATE_OUT_OF_WORK, i).tolist() == rec["out_of_work"].tolist(), what
-    assert _next_draws(O, enc.get_state(native.STATE_RNG_PY, i), 4, True) == rec["py_next"].tolist(), what
-    assert _next_draws(O, enc.get_state(native.STATE_RNG_NP, i), 4, False) == rec["np_next"].tolist(), what
+    H.check_ops(got, rec["ops"], what)
+    H.check_recorded_state(native, O, enc, i, rec, what)
 
 
 def _one_stream(native, O, device_tables, rec, tag, recurrence, kernel, prefix):
     mode, pal, sp, sn, fourth = _meta(rec)
-    enc = _encoder(native, O, device_tables, mode, pal, [(sp, sn)], recurrence, kernel, prefix, fourth)
-    fm, fa = _device_frames(mode, [rec["frames"]])
-    got = enc.encode(fm, fa, [(int(f), int(a), 1, int(k)) for (f, a, k) in rec["schedule"]])
+    enc = H.make_encoder(native, device_tables, mode, pal, dw=recurrence, kernel=kernel, prefix=prefix, rng=[(sp, sn)], O=O,
+                         **({"fourth": True} if fourth else {}))
+    fm, fa = H.device_frames(mode, [rec["frames"]])
+    got = enc.encode(fm, fa, H.segments(rec["schedule"]))
     enc.check()
     _check_stream(native, O, enc, 0, got.cpu().numpy()[0], rec, "%s (prefix sort %s)" % (tag, "on" if prefix else "off"))
     enc.close()
@@ -118,10 +83,11 @@ def test_corpus_as_one_batch(native, O, corpus, device_tables, mode, pal, kernel
     assert len(tags) >= 3, tags
     for order in (tags, tags[::-1]):
         recs = [corpus[t] for t in order]
-        enc = _encoder(native, O, device_tables, mode, pal, [_meta(r)[2:4] for r in recs], True, kernel, True)
-        fm, fa = _device_frames(mode, [r["frames"] for r in recs])
+        enc = H.make_encoder(native, device_tables, mode, pal, len(recs), dw=True, kernel=kernel, prefix=True,
+                             rng=[_meta(r)[2:4] for r in recs], O=O)
+        fm, fa = H.device_frames(mode, [r["frames"] for r in recs])
         enc.profile(True)
-        ops, totals = enc.encode_streams(fm, fa, [[(int(f), int(a), 1, int(k)) for (f, a, k) in r["schedule"]] for r in recs])
+        ops, totals = enc.encode_streams(fm, fa, [H.segments(r["schedule"]) for r in recs])
         enc.check()
         print("%s pal %d, kernel=%r: greedy launches by form %s" % ("DHGR" if mode else "HGR", pal, kernel, enc.launch_forms()))
         got = ops.cpu().numpy()

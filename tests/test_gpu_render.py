@@ -19,6 +19,8 @@ import sys
 import numpy as np
 import pytest
 
+from device_guards import guarded
+import encode_harness as H
 import render_model as R
 
 pytestmark = pytest.mark.gpu
@@ -81,11 +83,6 @@ def test_constant_and_alternating_screens_in_every_palette(native, mode, pal_nam
     assert (got[1, :, 3:] == pal[15]).all()               # every dot lit: white from the fourth dot on
 
 
-def _guarded(torch, n_bytes, lead, trail):
-    buf = torch.full((lead + n_bytes + trail,), GUARD, dtype=torch.uint8, device="cuda")
-    return buf, buf[lead:lead + n_bytes]
-
-
 @pytest.mark.parametrize("mode", MODES)
 def test_guards_and_least_alignments(native, mode):
     """The output sliced from a larger allocation at 16 bytes and no more, the inputs at 8: the 64 bytes in front of and behind
@@ -93,11 +90,11 @@ def test_guards_and_least_alignments(native, mode):
     import torch
     n = 2
     main, aux = _random_screens(n, 40 + mode)
-    mbuf, mview = _guarded(torch, n * 8192, 8, 8)
-    abuf, aview = _guarded(torch, n * 8192, 8, 8)
+    mbuf, mview = guarded(n * 8192, 8, 8, GUARD)
+    abuf, aview = guarded(n * 8192, 8, 8, GUARD)
     mview.copy_(torch.from_numpy(main).reshape(-1))
     aview.copy_(torch.from_numpy(aux).reshape(-1))
-    obuf, oview = _guarded(torch, n * FRAME, 64 + 16, 64)
+    obuf, oview = guarded(n * FRAME, 64 + 16, 64, GUARD)
     assert oview.data_ptr() % 32 == 16 and mview.data_ptr() % 16 == 8 and aview.data_ptr() % 16 == 8
     got = native.render_rgb(mode, DISTINCT, mview, aview if mode == R.DHGR else None, out=oview).cpu().numpy()
     want = R.render_rgb(mode, main, aux, DISTINCT)
@@ -114,7 +111,7 @@ def test_refusals_write_nothing(native):
     main, aux = _random_screens(n, 77)
     dm, da = torch.from_numpy(main).cuda(), torch.from_numpy(aux).cuda()
     pal = np.ascontiguousarray(DISTINCT).reshape(48)
-    obuf, oview = _guarded(torch, n * FRAME, 64, 64)
+    obuf, oview = guarded(n * FRAME, 64, 64, GUARD)
     st = native.stream_ptr()
 
     def call(mode, count, pm, pa, po):
@@ -159,17 +156,6 @@ def test_round_trip_of_a_colour_card(native, pal_name):
     assert (got[:, 512 + 4:] == pal[0]).all()
 
 
-def _seeded_batch(native, device_tables, mode, n_streams):
-    import stream_batch
-    table, store = device_tables.get(mode)
-    return stream_batch.StreamBatch(mode, table, store, n_streams, seeds=[(s + 1, s + 11) for s in range(n_streams)],
-                                    dm=device_tables.dm[(mode, 5)])
-
-
-_STATE = ["STATE_MEM_MAIN", "STATE_MEM_AUX", "STATE_UP_MAIN", "STATE_UP_AUX", "STATE_RNG_PY", "STATE_RNG_NP", "STATE_OUT_OF_WORK",
-          "STATE_COUNTERS"]
-
-
 @pytest.mark.parametrize("mode", MODES)
 def test_encoder_render(native, device_tables, mode):
     """Two streams, three frames of forty opcodes: behind every frame the encoder's rendering is iiv_render_rgb of the maps
@@ -180,7 +166,7 @@ def test_encoder_render(native, device_tables, mode):
     S = 2
     fm, fa = stream_batch.synth_frames_torch(S, 4, mode == R.DHGR, seed=17)
     pal = _palettes()["NTSC"]
-    drawn, plain = _seeded_batch(native, device_tables, mode, S), _seeded_batch(native, device_tables, mode, S)
+    drawn, plain = H.seeded_batch(device_tables, mode, S), H.seeded_batch(device_tables, mode, S)
     ops = {id(drawn): [], id(plain): []}
     for f in range(3):
         seg = [(f, f & 1 if mode == R.DHGR else 0, 1, 40)]
@@ -199,7 +185,7 @@ def test_encoder_render(native, device_tables, mode):
         one = native.encoder_render(drawn.enc, pal, first_stream=1, n_streams=1)
         assert torch.equal(one[0], got[1])
     # a range that is not inside the encoder's: refused, nothing written
-    obuf, oview = _guarded(torch, S * FRAME, 64, 64)
+    obuf, oview = guarded(S * FRAME, 64, 64, GUARD)
     hp = np.ascontiguousarray(pal).reshape(48)
     for first, count in ((1, 2), (2, 1), (-1, 1), (0, 3), (0, -1)):
         rc = native.lib().iiv_encoder_render(drawn.enc._h, first, count, native.hptr(hp), native.dptr(oview), native.stream_ptr())
@@ -214,7 +200,7 @@ def test_encoder_render(native, device_tables, mode):
         b.enc.check()
     for x, y in zip(ops[id(drawn)], ops[id(plain)]):
         assert (x == y).all()
-    for name in [n for n in _STATE if mode == R.DHGR or "AUX" not in n]:
+    for name in [n for n in H.STATE_NAMES if mode == R.DHGR or "AUX" not in n]:
         for s in range(S):
             assert (drawn.enc.get_state(getattr(native, name), s) == plain.enc.get_state(getattr(native, name), s)).all(), name
     drawn.close()
@@ -234,9 +220,8 @@ def test_video_screen_rgb_and_screen_render_rgb(native, O, oracle_tables, mode):
     import torch
     import video
     import video_mode
-    from test_gpu_encode import _synth
     vm = video_mode.VideoMode.DHGR if mode == R.DHGR else video_mode.VideoMode.HGR
-    frames = _synth(mode, 2, 909)
+    frames = H.synth(mode, 2, 909)
     random.seed(31)
     np.random.seed(32)
     v = video.Video(_FG(), ticks_per_second=14700., mode=vm, palette=palette.Palette.NTSC)

@@ -21,6 +21,7 @@ import sys
 import numpy as np
 import pytest
 
+import encode_harness as H
 import ingest_model
 import render_error_model as E
 import render_model as R
@@ -217,17 +218,6 @@ def test_refusals_write_nothing(native):
     assert (out.cpu().numpy().reshape(-1)[:9 * n].reshape(n, 3, 3) == want).all()
 
 
-def _seeded_batch(native, device_tables, mode, n_streams):
-    import stream_batch
-    table, store = device_tables.get(mode)
-    return stream_batch.StreamBatch(mode, table, store, n_streams, seeds=[(s + 1, s + 11) for s in range(n_streams)],
-                                    dm=device_tables.dm[(mode, 5)])
-
-
-_STATE = ["STATE_MEM_MAIN", "STATE_MEM_AUX", "STATE_UP_MAIN", "STATE_UP_AUX", "STATE_RNG_PY", "STATE_RNG_NP", "STATE_OUT_OF_WORK",
-          "STATE_COUNTERS"]
-
-
 @pytest.mark.parametrize("mode", MODES)
 def test_encoder_render_error(native, device_tables, mode):
     """Three streams, two frames of forty opcodes: behind each the encoder's sums -- the full range at width 560, the middle
@@ -243,7 +233,7 @@ def test_encoder_render_error(native, device_tables, mode):
     _, _, ref = _random_case(S, 560, 60 + mode)
     narrow = np.ascontiguousarray(ref[:, :, 1::2])
     dref, dnarrow = torch.from_numpy(ref).cuda(), torch.from_numpy(narrow).cuda()
-    measured, plain = _seeded_batch(native, device_tables, mode, S), _seeded_batch(native, device_tables, mode, S)
+    measured, plain = H.seeded_batch(device_tables, mode, S), H.seeded_batch(device_tables, mode, S)
     ops = {id(measured): [], id(plain): []}
     for f in range(2):
         seg = [(f, f & 1 if mode == R.DHGR else 0, 1, 40)]
@@ -284,7 +274,7 @@ def test_encoder_render_error(native, device_tables, mode):
         b.enc.check()
     for x, y in zip(ops[id(measured)], ops[id(plain)]):
         assert (x == y).all()
-    for name in [n for n in _STATE if mode == R.DHGR or "AUX" not in n]:
+    for name in [n for n in H.STATE_NAMES if mode == R.DHGR or "AUX" not in n]:
         for s in range(S):
             assert (measured.enc.get_state(getattr(native, name), s) == plain.enc.get_state(getattr(native, name), s)).all(), name
     measured.close()
@@ -304,9 +294,8 @@ def test_video_screen_error_and_screen_render_error(native, O, oracle_tables, mo
     import torch
     import video
     import video_mode
-    from test_gpu_encode import _synth
     vm = video_mode.VideoMode.DHGR if mode == R.DHGR else video_mode.VideoMode.HGR
-    frames = _synth(mode, 1, 909)
+    frames = H.synth(mode, 1, 909)
     random.seed(31)
     np.random.seed(32)
     v = video.Video(_FG(), ticks_per_second=14700., mode=vm, palette=palette.Palette.NTSC)

@@ -16,6 +16,7 @@ import re
 import numpy as np
 import pytest
 
+import encode_harness as H
 import mt_model
 
 pytestmark = pytest.mark.gpu
@@ -41,43 +42,19 @@ def _narrow(a):
 def _oracle_run(O, oracle_tables, mode, frames, sched, py_words, np_words, fourth=False):
     """One stream through the oracle from the given generator states, one opcode per call: everything a device stream is
     compared with, the draws of `random` per opcode and of `np.random` per restart."""
-    v = O.Video(mode, oracle_tables.get(mode, 5))
-    v.rng_py().set_state_words(py_words)     # (the generators live inside the oracle's Video: orc_video_rng_py / _np)
-    v.rng_np().set_state_words(np_words)
-    v.set_fourth_offset(fourth)
-    ops, steps, seg_np = [], [], []
-    for (f, ia, restart, n) in sched:
-        if restart:
-            before = v.draws()[1]
-            v.encode_frame(frames[f, 0], frames[f, 1] if mode == 1 else None, ia)
-        for k in range(n):
-            d0 = v.draws()[0]
-            ops.append(v.next(1))
-            if restart and k == 0:
-                seg_np.append(v.draws()[1] - before)     # (the reference's generator is lazy: its prologue runs in the first next())
-            steps.append(v.draws()[0] - d0)
-    return {"ops": np.concatenate(ops), "mem": [v.memory(b).copy() for b in range(mode + 1)],
-            "up": [_narrow(v.update_priority(b)) for b in range(mode + 1)], "draws": v.draws(),
-            "py": v.rng_py().state_words(), "np": v.rng_np().state_words(), "steps": steps, "seg_np": seg_np}
+    v, ops, steps, seg_np = H.oracle_run(O, oracle_tables, mode, 5, frames, sched, (py_words, np_words), fourth=fourth, per_opcode=True)
+    st = H.oracle_state(v, mode)
+    st.up = [_narrow(u) for u in st.up]
+    return {"ops": ops, "state": st, "draws": st.draws, "steps": steps, "seg_np": seg_np}
 
 
 def _encoder(native, device_tables, mode, frames, py_states, np_states, kernel, fourth=False, prefix=True, dw=True):
     """An encoder of len(py_states) streams in the given generator states, and the target frames on the device.
     frames: (n_frames, 2, 32, 256), shared by all streams."""
-    import torch
     n = len(py_states)
-    t, s = device_tables.get(mode, 5)
-    enc = native.Encoder(mode, t, s, n, dm=device_tables.dm[(mode, 5)])
-    enc.set_diff_weights_mode(dw)
-    enc.set_greedy_kernel(kernel)
-    enc.set_prefix_sort(prefix)
-    if fourth:
-        enc.set_fourth_offset(True)
-    fr = torch.from_numpy(np.ascontiguousarray(frames)).unsqueeze(0).expand(n, -1, -1, -1, -1)
-    fm = fr[:, :, 0].contiguous().cuda()
-    fa = fr[:, :, 1].contiguous().cuda() if mode == 1 else None
-    enc.set_state_all(native.STATE_RNG_PY, np.stack(py_states))
-    enc.set_state_all(native.STATE_RNG_NP, np.stack(np_states))
+    enc = H.make_encoder(native, device_tables, mode, 5, n, dw=dw, kernel=kernel, prefix=prefix, rng=list(zip(py_states, np_states)),
+                         **({"fourth": True} if fourth else {}))
+    fm, fa = H.device_frames(mode, [frames] * n)
     return enc, fm, fa
 
 
@@ -88,38 +65,16 @@ def _device_run(native, device_tables, mode, frames, sched, py_states, np_states
     return enc, ops.cpu().numpy()
 
 
-def _state_of(native, enc, mode, i):
-    return {"mem": [enc.get_state(native.STATE_MEM_MAIN + b, i) for b in range(mode + 1)],
-            "up": [enc.get_state(native.STATE_UP_MAIN + b, i) for b in range(mode + 1)],
-            "draws": tuple(int(x) for x in enc.get_state(native.STATE_COUNTERS, i)[:2]),
-            "py": enc.get_state(native.STATE_RNG_PY, i), "np": enc.get_state(native.STATE_RNG_NP, i)}
-
-
-def _same_stream(got, want, what):
-    g, w = mt_model.canonical(got), mt_model.canonical(want)
-    bad = np.nonzero(g != w)[0]
-    assert len(bad) == 0, "%s: canonical state differs in %d words, first at %d (624 = the index): got %d (raw index %d), want %d" % (
-        what, len(bad), bad[0], g[bad[0]], got[624], w[bad[0]])
-
-
 def _compare(native, enc, mode, ops, i, ref, tag):
+    """opcodes and the whole state of stream i against its oracle run -> what was read from the device"""
     tag = "%s, stream %d" % (tag, i)
-    bad = np.nonzero((ops[i] != ref["ops"]).any(axis=1))[0]
-    assert len(bad) == 0, "%s: first opcode mismatch at %d: got %s want %s" % (tag, bad[0], ops[i][bad[0]], ref["ops"][bad[0]])
-    st = _state_of(native, enc, mode, i)
-    for b in range(mode + 1):
-        assert np.array_equal(st["mem"][b], ref["mem"][b]), "%s: memory map of bank %d" % (tag, b)
-        assert np.array_equal(st["up"][b], ref["up"][b]), "%s: priorities of bank %d" % (tag, b)
-    assert st["draws"] == ref["draws"], "%s: draw counters %s, oracle %s" % (tag, st["draws"], ref["draws"])
-    _same_stream(st["py"], ref["py"], tag + ", random")
-    _same_stream(st["np"], ref["np"], tag + ", np.random")
-    return st
+    H.check_ops(ops[i], ref["ops"], tag)
+    return H.check_oracle_state(native, enc, i, ref["state"], mode, tag)
 
 
 def _iid_frame(mode, seed):
-    """one frame the way test_gpu_encode._synth makes them"""
-    from test_gpu_encode import _synth
-    return _synth(mode, 1, seed)[0]
+    """one frame the way encode_harness.synth makes them"""
+    return H.synth(mode, 1, seed)[0]
 
 
 def _img_frame(mode, seed):
@@ -213,8 +168,8 @@ def test_random_index_sweep(native, O, oracle_tables, device_tables, mode, kerne
     for b in range(mode + 1):
         assert np.array_equal(got[624]["mem"][b], got[625]["mem"][b]) and np.array_equal(got[624]["up"][b], got[625]["up"][b]), tag
     assert got[624]["draws"] == got[625]["draws"], tag
-    _same_stream(got[624]["py"], got[625]["py"], tag + ", streams 624 and 625, random")
-    _same_stream(got[624]["np"], got[625]["np"], tag + ", streams 624 and 625, np.random")
+    H.same_stream(got[624]["py"], got[625]["py"], tag + ", streams 624 and 625, random")
+    H.same_stream(got[624]["np"], got[625]["np"], tag + ", streams 624 and 625, np.random")
     enc.close()
 
 
@@ -356,12 +311,12 @@ def test_snapshot_and_rollback_across_a_boundary(native, O, oracle_tables, devic
     for again in (False, True):
         if again:
             enc.rollback(1)
-            back = _state_of(native, enc, mode, 0)
-            assert np.array_equal(back["py"], py[0]) and np.array_equal(back["np"], npw[0]) and back["draws"] == (0, 0)
+            assert np.array_equal(enc.get_state(native.STATE_RNG_PY), py[0]) and np.array_equal(enc.get_state(native.STATE_RNG_NP), npw[0])
+            assert enc.get_state(native.STATE_COUNTERS)[:2].tolist() == [0, 0]
         ops = enc.encode(fm, fa, sched).cpu().numpy()
         enc.check()
         runs.append((ops, _compare(native, enc, mode, ops, 0, ref, "kernel %r, %s" % (kernel, "after the rollback" if again else "first run"))))
     assert np.array_equal(runs[0][0], runs[1][0])
-    _same_stream(runs[1][1]["py"], runs[0][1]["py"], "random, second run against the first")
-    _same_stream(runs[1][1]["np"], runs[0][1]["np"], "np.random, second run against the first")
+    H.same_stream(runs[1][1]["py"], runs[0][1]["py"], "random, second run against the first")
+    H.same_stream(runs[1][1]["np"], runs[0][1]["np"], "np.random, second run against the first")
     enc.close()

@@ -16,17 +16,16 @@ import mono_model
 import render_error_model
 import render_model
 import resize_model
-from stream_cases import Enc as _Enc, dp as _dp, frames as _frames, g6_addresses, maps as _maps, next_draws as _next_draws, seed_words as _seed_words
+from stream_cases import Enc as _Enc, dp as _dp, frames as _frames, g6_addresses, maps as _maps, next_draws as _next_draws
+from a2m_model import random_ops
+from device_guards import ok
+from encode_harness import seed_states as _seed_states
 from stream_probe import Probe
 
 pytestmark = pytest.mark.gpu
 
 HGR, DHGR = 0, 1
 MODES = [DHGR, HGR]
-
-
-def _ok(native, rc):
-    native.check(rc)
 
 
 def _np(t):
@@ -57,7 +56,7 @@ def test_colour_ingest(native, O, colour_frames, mode, dither):
     pal = p.host(np.asarray(O.PALETTE_RGB[5], np.uint8).reshape(48), np.asarray(O.PALETTE_RGB[0], np.uint8).reshape(48))
 
     def call(st):
-        _ok(native, L.iiv_frames_to_memory_maps(mode, _hp(pal), 5, _dp(rgb), dither, _dp(main), _dp(aux), st))
+        ok(native, L.iiv_frames_to_memory_maps(mode, _hp(pal), 5, _dp(rgb), dither, _dp(main), _dp(aux), st))
     call(native.stream_ptr())
     p.run(call)
     assert np.array_equal(_np(main), np.stack([e[0] for e in exp]))
@@ -83,7 +82,7 @@ def test_diffused_ingest(native, O, colour_frames, atkinson, mode):
     wt = p.host(w.astype(np.uint8).reshape(15), lite.astype(np.uint8).reshape(15))
 
     def call(st):
-        _ok(native, L.iiv_frames_to_memory_maps_diffused(mode, _hp(pal), 5, _dp(rgb), _hp(wt), div, _dp(main), _dp(aux), st))
+        ok(native, L.iiv_frames_to_memory_maps_diffused(mode, _hp(pal), 5, _dp(rgb), _hp(wt), div, _dp(main), _dp(aux), st))
     call(native.stream_ptr())
     p.run(call)
     em, ea = atkinson[mode]
@@ -103,7 +102,7 @@ def test_mono_ingest(native, mode, dither):
     main, aux = p.output((5, 32, 256)), p.output((5, 32, 256))
 
     def call(st):
-        _ok(native, L.iiv_frames_to_memory_maps_mono(mode, 5, _dp(rgb), dither, _dp(main), _dp(aux), st))
+        ok(native, L.iiv_frames_to_memory_maps_mono(mode, 5, _dp(rgb), dither, _dp(main), _dp(aux), st))
     call(native.stream_ptr())
     p.run(call)
     assert np.array_equal(_np(main), em)
@@ -119,7 +118,7 @@ def test_resize(native):
     dst = p.output((3, 192, 280, 3))
 
     def call(st):
-        _ok(native, L.iiv_resize_frames(3, 37, 53, _dp(src), 37 * 53 * 3, 53 * 3, 192, 280, _dp(dst), st))
+        ok(native, L.iiv_resize_frames(3, 37, 53, _dp(src), 37 * 53 * 3, 53 * 3, 192, 280, _dp(dst), st))
     call(native.stream_ptr())                                         # the first use of a size pair uploads its tables
     p.run(call)
     assert np.array_equal(_np(dst), resize_model.resize(real, (192, 280)))
@@ -138,7 +137,7 @@ def test_render_rgb(native, O, mode):
     pal = p.host(np.asarray(O.PALETTE_RGB[5], np.uint8).reshape(48), np.asarray(O.PALETTE_RGB[0], np.uint8).reshape(48))
 
     def call(st):
-        _ok(native, L.iiv_render_rgb(mode, _hp(pal), 3, _dp(main), _dp(aux), _dp(out), st))
+        ok(native, L.iiv_render_rgb(mode, _hp(pal), 3, _dp(main), _dp(aux), _dp(out), st))
     call(native.stream_ptr())
     p.run(call)
     assert np.array_equal(_np(out), render_model.render_rgb(mode, rm, ra if mode == DHGR else None, O.PALETTE_RGB[5]))
@@ -159,7 +158,7 @@ def test_render_error(native, O, mode, width):
     pal = p.host(np.asarray(O.PALETTE_RGB[5], np.uint8).reshape(48), np.asarray(O.PALETTE_RGB[0], np.uint8).reshape(48))
 
     def call(st):
-        _ok(native, L.iiv_render_error(mode, _hp(pal), 3, _dp(main), _dp(aux), _dp(ref), width, _dp(out), st))
+        ok(native, L.iiv_render_error(mode, _hp(pal), 3, _dp(main), _dp(aux), _dp(ref), width, _dp(out), st))
     call(native.stream_ptr())
     p.run(call)
     exp = render_error_model.render_error(mode, rm, ra if mode == DHGR else None, O.PALETTE_RGB[5], rref)
@@ -212,7 +211,7 @@ def test_encode(native, O, device_tables, oracle_tables, mode, form):
     p.scribble(scribble)
 
     def call(st):
-        _ok(native, L.iiv_encode(e.enc._h, _dp(d_main), _dp(d_aux if mode == DHGR else None), 2, segs, len(segments), _dp(ops), st))
+        ok(native, L.iiv_encode(e.enc._h, _dp(d_main), _dp(d_aux if mode == DHGR else None), 2, segs, len(segments), _dp(ops), st))
     e.warm(call)
     e.enc.profile(True)
     p.run(call)
@@ -244,7 +243,7 @@ def _encode_streams(native, O, device_tables, oracle_tables, mode, scheds, seed0
     p.scribble(scribble)
 
     def call(st):
-        _ok(native, L.iiv_encode_streams(e.enc._h, _dp(d_main), _dp(d_aux if mode == DHGR else None), 2, segs,
+        ok(native, L.iiv_encode_streams(e.enc._h, _dp(d_main), _dp(d_aux if mode == DHGR else None), 2, segs,
                                         begin.ctypes.data_as(C.POINTER(C.c_int32)), _dp(ops), width * 6, st))
     e.warm(call)
     e.enc.profile(kernel is not None)
@@ -295,11 +294,11 @@ def test_snapshot_and_rollback_between_encodes(native, O, device_tables, oracle_
     aux = (lambda: _dp(d_aux)) if mode == DHGR else (lambda: C.c_void_p(0))
 
     def call(st):
-        _ok(native, L.iiv_encode(e.enc._h, _dp(d_main), aux(), 2, sa, 1, _dp(oa), st))
-        _ok(native, L.iiv_encoder_snapshot(e.enc._h, st))
-        _ok(native, L.iiv_encode(e.enc._h, _dp(d_main), aux(), 2, sb, 2, _dp(ob1), st))
-        _ok(native, L.iiv_encoder_rollback(e.enc._h, st))
-        _ok(native, L.iiv_encode(e.enc._h, _dp(d_main), aux(), 2, sb, 2, _dp(ob2), st))
+        ok(native, L.iiv_encode(e.enc._h, _dp(d_main), aux(), 2, sa, 1, _dp(oa), st))
+        ok(native, L.iiv_encoder_snapshot(e.enc._h, st))
+        ok(native, L.iiv_encode(e.enc._h, _dp(d_main), aux(), 2, sb, 2, _dp(ob1), st))
+        ok(native, L.iiv_encoder_rollback(e.enc._h, st))
+        ok(native, L.iiv_encode(e.enc._h, _dp(d_main), aux(), 2, sb, 2, _dp(ob2), st))
     e.warm(call)
     p.run(call)
     e.enc.check()
@@ -325,18 +324,18 @@ def test_async_state_calls_around_an_encode(native, O, device_tables, oracle_tab
     ops = p.output((n, 260, 6))
     segs, scribble = _segment_arrays(native, segments, [(1, 0, 1, 100), (0, 0, 1, 60)])
     p.scribble(scribble)
-    py, npw = _seed_words(O, [(77, 78)])
-    py_other, np_other = _seed_words(O, [(5, 6)])
-    h_py, h_np = p.host(py[0], py_other[0]), p.host(npw[0], np_other[0])
+    py, npw = _seed_states(O, 77, 78)
+    py_other, np_other = _seed_states(O, 5, 6)
+    h_py, h_np = p.host(py, py_other), p.host(npw, np_other)
     h_oow = p.host(np.array([0, 0], np.int32), np.array([1, 1], np.int32))
     pinned = torch.zeros(C.sizeof(native.VideoBrief), dtype=torch.uint8).pin_memory()
     brief = native.VideoBrief.from_address(pinned.data_ptr())
 
     def call(st):
         for what, a in ((native.STATE_RNG_PY, h_py), (native.STATE_RNG_NP, h_np), (native.STATE_OUT_OF_WORK, h_oow)):
-            _ok(native, L.iiv_encoder_set_state_async(e.enc._h, 1, what, _hp(a), a.nbytes, st))
-        _ok(native, L.iiv_encode(e.enc._h, _dp(d_main), _dp(d_aux), 2, segs, 2, _dp(ops), st))
-        _ok(native, L.iiv_encoder_get_video_brief_async(e.enc._h, 1, C.byref(brief), st))
+            ok(native, L.iiv_encoder_set_state_async(e.enc._h, 1, what, _hp(a), a.nbytes, st))
+        ok(native, L.iiv_encode(e.enc._h, _dp(d_main), _dp(d_aux), 2, segs, 2, _dp(ops), st))
+        ok(native, L.iiv_encoder_get_video_brief_async(e.enc._h, 1, C.byref(brief), st))
     e.warm(call)
     C.memset(pinned.data_ptr(), 0, C.sizeof(native.VideoBrief))
     p.run(call)
@@ -380,9 +379,9 @@ def test_encoder_render_and_error_behind_an_encode(native, O, device_tables, ora
     segs = native.segment_array(segments)
 
     def call(st):
-        _ok(native, L.iiv_encode(e.enc._h, _dp(d_main), _dp(d_aux if mode == DHGR else None), 2, segs, len(segments), _dp(ops), st))
-        _ok(native, L.iiv_encoder_render(e.enc._h, 0, n, _hp(pal), _dp(rgb), st))
-        _ok(native, L.iiv_encoder_render_error(e.enc._h, 0, n, _hp(pal), _dp(ref), 280, _dp(err), st))
+        ok(native, L.iiv_encode(e.enc._h, _dp(d_main), _dp(d_aux if mode == DHGR else None), 2, segs, len(segments), _dp(ops), st))
+        ok(native, L.iiv_encoder_render(e.enc._h, 0, n, _hp(pal), _dp(rgb), st))
+        ok(native, L.iiv_encoder_render_error(e.enc._h, 0, n, _hp(pal), _dp(ref), 280, _dp(err), st))
     e.warm(call)
     p.run(call)
     e.enc.check()
@@ -409,23 +408,17 @@ def test_encoder_check_waits_for_the_stream(native, O, device_tables, oracle_tab
     ops = p.output((1, 2048, 6))
     segs = native.segment_array([(0, 0, 1, 2048)])
     clean = native.segment_array([(0, 0, 1, 8)])
-    _ok(native, L.iiv_encode(e.enc._h, _dp(d_main), _dp(d_aux), 1, clean, 1, _dp(ops), native.stream_ptr()))   # warm-up, on the decoy
+    ok(native, L.iiv_encode(e.enc._h, _dp(d_main), _dp(d_aux), 1, clean, 1, _dp(ops), native.stream_ptr()))   # warm-up, on the decoy
     e.enc.check()
 
     def call(st):
-        _ok(native, L.iiv_encode(e.enc._h, _dp(d_main), _dp(d_aux), 1, segs, 1, _dp(ops), st))
+        ok(native, L.iiv_encode(e.enc._h, _dp(d_main), _dp(d_aux), 1, segs, 1, _dp(ops), st))
         return L.iiv_encoder_check(e.enc._h, None, st)
     assert p.run(call, asynchronous=False) == native.ERR_ASSERT
     e.close()
 
 
 # ---- .a2m reading and writing ----------------------------------------------------------------------------------------
-
-def _random_ops(rng, n):
-    ops = rng.integers(0, 256, (n, 6), dtype=np.uint8)
-    ops[:, 0] = rng.integers(32, 64, n)
-    return ops, (rng.integers(0, 32, n) * 2 + 4).astype(np.uint8)
-
 
 @pytest.fixture(scope="module")
 def addresses(golden):
@@ -442,7 +435,7 @@ def test_a2m_scan_decode_replay(native, O, addresses):
     assert a2m_model.P(n_ops) > 2 * 2048
 
     def streams():
-        return np.stack([O.emit_stream(modes[s], *_random_ops(rng, n_ops), tick, ack, term) for s in range(S)])
+        return np.stack([O.emit_stream(modes[s], *random_ops(rng, n_ops), tick, ack, term) for s in range(S)])
     real, decoy = streams(), streams()
     stride = real.shape[1]
     max_ops = a2m_model.max_ops(stride)
@@ -457,10 +450,10 @@ def test_a2m_scan_decode_replay(native, O, addresses):
     main, aux = p.output((S, 3, 32, 256)), p.output((S, 3, 32, 256))
 
     def call(st):
-        _ok(native, L.iiv_a2m_scan(reader._h, S, _dp(data), stride, _dp(lengths), _dp(info), st))
-        _ok(native, L.iiv_a2m_decode(reader._h, S, _dp(data), stride, _dp(info), _dp(ops), max_ops * 6, _dp(ticks), _dp(banks),
+        ok(native, L.iiv_a2m_scan(reader._h, S, _dp(data), stride, _dp(lengths), _dp(info), st))
+        ok(native, L.iiv_a2m_decode(reader._h, S, _dp(data), stride, _dp(info), _dp(ops), max_ops * 6, _dp(ticks), _dp(banks),
                                     max_ops, st))
-        _ok(native, L.iiv_a2m_replay(reader._h, S, _dp(data), stride, _dp(info), 100, 300, 3, _dp(im), _dp(ia), _dp(main), _dp(aux), st))
+        ok(native, L.iiv_a2m_replay(reader._h, S, _dp(data), stride, _dp(info), 100, 300, 3, _dp(im), _dp(ia), _dp(main), _dp(aux), st))
     call(native.stream_ptr())
     p.run(call)
     g_info, g_ops, g_ticks, g_banks, g_main, g_aux = (_np(t) for t in (info, ops, ticks, banks, main, aux))
@@ -482,19 +475,19 @@ def test_emit_chunk(native, O, addresses, mode):
     tick, ack, term = addresses
     rng = np.random.default_rng(31 + mode)
     S, first, n = 3, 250, 400
-    full = [_random_ops(rng, first + n) for _ in range(S)]
-    other = [_random_ops(rng, n) for _ in range(S)]
+    full = [random_ops(rng, first + n) for _ in range(S)]
+    other = [random_ops(rng, n) for _ in range(S)]
     p = Probe()
     ops = p.input(np.stack([o[first:] for o, _ in full]), np.stack([o for o, _ in other]))
     ticks = p.input(np.stack([t[first:] for _, t in full]), np.stack([t for _, t in other]))
     d_tick = p.input(tick.view(np.int16), np.ascontiguousarray(tick[::-1]).view(np.int16))
     b0, nb = C.c_size_t(0), C.c_size_t(0)
-    _ok(native, L.iiv_emit_chunk(mode, 1, first, n, None, 0, None, 0, 34, None, 0, None, 0, C.byref(b0), C.byref(nb), None, None))
+    ok(native, L.iiv_emit_chunk(mode, 1, first, n, None, 0, None, 0, 34, None, 0, None, 0, C.byref(b0), C.byref(nb), None, None))
     width = int(nb.value) + 16
     out = p.output((S, width))
 
     def call(st):
-        _ok(native, L.iiv_emit_chunk(mode, S, first, n, _dp(ops), n * 6, _dp(ticks), n, 34, _dp(d_tick), ack, _dp(out), width,
+        ok(native, L.iiv_emit_chunk(mode, S, first, n, _dp(ops), n * 6, _dp(ticks), n, 34, _dp(d_tick), ack, _dp(out), width,
                                     C.byref(b0), C.byref(nb), None, st))
     call(native.stream_ptr())
     p.run(call)
@@ -513,7 +506,7 @@ def test_emit_stream_waits_for_the_stream(native, O, addresses):
     tick, ack, term = addresses
     rng = np.random.default_rng(41)
     S, n = 2, 650
-    real, other = [_random_ops(rng, n) for _ in range(S)], [_random_ops(rng, n) for _ in range(S)]
+    real, other = [random_ops(rng, n) for _ in range(S)], [random_ops(rng, n) for _ in range(S)]
     length = native.emit_stream_size(DHGR, n, tick, ack, term)
     p = Probe()
     ops = p.input(np.stack([o for o, _ in real]), np.stack([o for o, _ in other]))
@@ -523,7 +516,7 @@ def test_emit_stream_waits_for_the_stream(native, O, addresses):
     got_len = C.c_size_t(0)
 
     def call(st):
-        _ok(native, L.iiv_emit_stream(DHGR, S, n, _dp(ops), _dp(ticks), _hp(ta), ack, term, 0, _dp(out), length + 8, C.byref(got_len), st))
+        ok(native, L.iiv_emit_stream(DHGR, S, n, _dp(ops), _dp(ticks), _hp(ta), ack, term, 0, _dp(out), length + 8, C.byref(got_len), st))
     p.run(call, asynchronous=False)
     assert got_len.value == length
     for s in range(S):
@@ -560,7 +553,7 @@ def _audio_host(p):
 
 
 def test_audio_ticks(native, audio):
-    from test_gpu_audio import _check_ticks
+    from audio_model import check_ticks as _check_ticks
     L = native.lib()
     streams, real, decoy = audio
     norms = [audio_model.normalization(q.reshape(-1), q.shape[1], 44100) for q in streams]
@@ -574,7 +567,7 @@ def test_audio_ticks(native, audio):
     got = np.zeros(2, np.dtype(C.c_long))
 
     def call(st):
-        _ok(native, L.iiv_audio_ticks(2, _dp(pcm), 10000, _hp(nf), _hp(ch), _hp(rt), 14700, 2048, _hp(nm), _dp(out), stride, _hp(got), st))
+        ok(native, L.iiv_audio_ticks(2, _dp(pcm), 10000, _hp(nf), _hp(ch), _hp(rt), 14700, 2048, _hp(nm), _dp(out), stride, _hp(got), st))
         return got.copy()
     call(native.stream_ptr())
     assert list(p.run(call)) == counts
@@ -598,7 +591,7 @@ def test_audio_resample(native, audio):
     got = np.zeros(2, np.dtype(C.c_long))
 
     def call(st):
-        _ok(native, L.iiv_audio_resample(2, _dp(pcm), 10000, _hp(nf), _hp(ch), _hp(rt), 14700, _dp(out), stride, _hp(got), st))
+        ok(native, L.iiv_audio_resample(2, _dp(pcm), 10000, _hp(nf), _hp(ch), _hp(rt), 14700, _dp(out), stride, _hp(got), st))
         return got.copy()
     call(native.stream_ptr())
     assert list(p.run(call)) == lens
@@ -619,7 +612,7 @@ def test_audio_normalization_waits_for_the_stream(native, audio):
     got = np.zeros(2, np.float64)
 
     def call(st):
-        _ok(native, L.iiv_audio_normalization(2, _dp(pcm), 10000, _hp(nf), _hp(ch), _hp(rt), 14700, _hp(got), st))
+        ok(native, L.iiv_audio_normalization(2, _dp(pcm), 10000, _hp(nf), _hp(ch), _hp(rt), 14700, _hp(got), st))
         return got.copy()
     got_now = p.run(call, asynchronous=False)
     for s, q in enumerate(streams):
@@ -642,8 +635,8 @@ def test_cie2000_calls_on_a_sleeping_stream(native, O):
     f, i, de = np.zeros((16, 16)), np.zeros((16, 16), np.int32), np.zeros(40)
 
     def call(st):
-        _ok(native, L.iiv_cie2000_matrix(_hp(rgb), _hp(f), _hp(i), st))
-        _ok(native, L.iiv_delta_e_cie2000(40, _hp(a), _hp(b), _hp(de), st))
+        ok(native, L.iiv_cie2000_matrix(_hp(rgb), _hp(f), _hp(i), st))
+        ok(native, L.iiv_delta_e_cie2000(40, _hp(a), _hp(b), _hp(de), st))
         return f.copy(), i.copy(), de.copy()
     f, i, de = p.run(call, asynchronous=False)
     fo, io = O.cie2000_matrix(O.PALETTE_RGB[5])
@@ -673,9 +666,9 @@ def test_bitmap_operations(native, golden, device_tables, mode, name):
     packed, weights, delta = p.output((2, 32, 128), torch.int64), p.output((1, 32, 256), torch.int32), p.output((k, 256), torch.int32)
 
     def call(st):
-        _ok(native, L.iiv_pack(mode, 2, _dp(d_main), _dp(d_aux if mode == DHGR else None), _dp(packed), st))
-        _ok(native, L.iiv_diff_weights(mode, _dp(table), 1, _dp(d_src), _dp(d_tgt), 0, _dp(weights), st))
-        _ok(native, L.iiv_compute_delta_pages(mode, _dp(table), k, _dp(d_tgt), _dp(d_pages), _dp(d_contents), _dp(d_rows), 0,
+        ok(native, L.iiv_pack(mode, 2, _dp(d_main), _dp(d_aux if mode == DHGR else None), _dp(packed), st))
+        ok(native, L.iiv_diff_weights(mode, _dp(table), 1, _dp(d_src), _dp(d_tgt), 0, _dp(weights), st))
+        ok(native, L.iiv_compute_delta_pages(mode, _dp(table), k, _dp(d_tgt), _dp(d_pages), _dp(d_contents), _dp(d_rows), 0,
                                              _dp(delta), st))
     call(native.stream_ptr())
     p.run(call)
@@ -705,8 +698,8 @@ def test_tables_from_a_file_table(native, oracle_tables, device_tables):
 
     def call(st, t=None):
         t = table if t is None else t
-        _ok(native, L.iiv_symmetrise_table(HGR, _dp(t), st))
-        _ok(native, L.iiv_store_table_from_table(HGR, _dp(t), _dp(store), st))
+        ok(native, L.iiv_symmetrise_table(HGR, _dp(t), st))
+        ok(native, L.iiv_store_table_from_table(HGR, _dp(t), _dp(store), st))
     call(native.stream_ptr(), decoy.clone())                                                # warm-up, not on the probe's table
     p.run(call)
     assert np.array_equal(_np(keep).view(np.uint16), otab)

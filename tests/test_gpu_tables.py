@@ -7,6 +7,8 @@ import hashlib
 import numpy as np
 import pytest
 
+import encode_harness as H
+
 pytestmark = pytest.mark.gpu
 
 
@@ -128,7 +130,7 @@ def test_encoder_falls_back_when_its_tables_disagree(native, device_tables, dms,
     table, dense = device_tables.get(mode, 5)
     bad = dense.clone()
     bad.view(-1)[12345] += 1
-    enc = native.Encoder(mode, table, bad, 1, dm=dms[5])
+    enc = native.Encoder(mode, table, bad, 1, dm=dms[5])       # (construction under test: a store table that is not dm's)
     for kern in (True, "team", "shared", "plain"):
         with pytest.raises(native.IIVError):
             enc.set_greedy_kernel(kern)
@@ -143,7 +145,7 @@ def test_encoder_falls_back_when_its_tables_disagree(native, device_tables, dms,
     enc.check()
     assert ops.shape == (1, 12, 6) and int(ops[0, 0, 0]) == 32 + 3
     enc.close()
-    enc = native.Encoder(mode, table, dense, 1, dm=dms[5])
+    enc = native.Encoder(mode, table, dense, 1, dm=dms[5])     # (... and with the one that is)
     enc.set_greedy_kernel(True)
     enc.close()
 
@@ -241,11 +243,9 @@ def test_user_supplied_table_file(native, O, oracle_tables, device_tables, tmp_p
         rng = np.random.default_rng(3)
         fr[:] = rng.integers(0, 128, fr.shape)
         fr[..., (np.arange(256) & 127) >= 120] = 0
-        enc = native.Encoder(mode, tab.table, tab.store, 1)          # dm = None: table gathers + workgroup kernel
-        enc.set_state(native.STATE_RNG_PY, O.mt_seed_py(5).state_words())
-        enc.set_state(native.STATE_RNG_NP, O.mt_seed_np(6).state_words())
-        fm = torch.from_numpy(np.ascontiguousarray(fr[:, :, 0])).cuda()
-        fa = torch.from_numpy(np.ascontiguousarray(fr[:, :, 1])).cuda()
+        # dm = None: table gathers + workgroup kernel
+        enc = H.make_encoder(native, (tab.table, tab.store, None), mode, dm=False, rng=[(5, 6)], O=O)
+        fm, fa = H.device_frames(mode, list(fr))
         sched = [(0, 0, 1, 291), (0, 1, 1, 198), (1, 1, 1, 94), (1, 0, 1, 292)]
         got = enc.encode(fm, fa, sched).cpu().numpy()[0]
         enc.check()
@@ -256,7 +256,7 @@ def test_user_supplied_table_file(native, O, oracle_tables, device_tables, tmp_p
         for (f, ia, _, k) in sched:
             v.encode_frame(fr[0, f, 0], fr[0, f, 1], ia)
             exp.append(v.next(k))
-        assert (got == np.concatenate(exp)).all()
+        H.check_ops(got, np.concatenate(exp), "table-only encoder")
         enc.close()
     finally:
         screen.DHGRBitmap._edit_distances.cache_clear()
@@ -309,7 +309,6 @@ def test_arbitrary_diff_matrices(native, O, mode, seed):
     build, the split and narrow store tables (exact for every entry, re-read with the kernels' own arithmetic), the
     split diff-weight table, and a short encode in every kernel form against the oracle built from the same matrix."""
     import torch
-    from test_gpu_encode import _seed_states, _synth
     rng = np.random.default_rng(500 + seed)
     hi = (110, 12, 60)[seed - 1]
     dm = rng.integers(0, hi, (16, 16), dtype=np.int32)
@@ -330,9 +329,8 @@ def test_arbitrary_diff_matrices(native, O, mode, seed):
     assert n_bad == 0 and bool((exp == dense).all())
     assert native.check_split_diff_table(mode, dm, table) == 0
     assert native.check_diff_weight_pieces(mode, dm, table) == 0
-    frames = _synth(mode, 2, 77 + seed, coherent=True)
-    fm = torch.from_numpy(frames[None, :, 0].copy()).cuda()
-    fa = torch.from_numpy(frames[None, :, 1].copy()).cuda() if mode == 1 else None
+    frames = H.synth(mode, 2, 77 + seed, coherent=True)
+    fm, fa = H.device_frames(mode, [frames])
     sched = [(0, 0, 300), (1, 1 if mode else 0, 250), (1, 0, 2200)]
     v = O.Video(mode, otab, seed_py=5, seed_np=6)
     exp_ops = []
@@ -341,13 +339,8 @@ def test_arbitrary_diff_matrices(native, O, mode, seed):
         exp_ops.append(v.next(k))
     exp_ops = np.concatenate(exp_ops)
     for kern, rec in (("team", True), (True, "split"), ("shared", False), (False, True)):
-        enc = native.Encoder(mode, table, dense, 1, dm=dm)
-        enc.set_greedy_kernel(kern)
-        enc.set_diff_weights_mode(rec)
-        py, npw = _seed_states(O, 5, 6)
-        enc.set_state(native.STATE_RNG_PY, py)
-        enc.set_state(native.STATE_RNG_NP, npw)
-        got = enc.encode(fm, fa, [(f, ia, 1, k) for (f, ia, k) in sched]).cpu().numpy()[0]
+        enc = H.make_encoder(native, (table, dense, dm), mode, dw=rec, kernel=kern, rng=[(5, 6)], O=O)
+        got = enc.encode(fm, fa, H.segments(sched)).cpu().numpy()[0]
         enc.check()
-        assert (got == exp_ops).all(), (mode, seed, kern, rec)
+        H.check_ops(got, exp_ops, str((mode, seed, kern, rec)))
         enc.close()

@@ -5,29 +5,25 @@ path; the golden runs are the reference's own recorded opcode streams."""
 import numpy as np
 import pytest
 
+import encode_harness as H
+
 pytestmark = pytest.mark.gpu
 
 
 def test_operators_are_registered_and_run_the_golden_encode(native, O, device_tables, golden):
     import torch
     import torch_ops
-    from test_gpu_encode import _seed_states, _tags
     for name in torch_ops.NAMES:
         assert hasattr(torch.ops.iivision, name), name
     g3 = golden.g3_encode_runs
-    for tag in _tags(g3)[:6]:
+    for tag in H.tags(g3)[:6]:
         mode, pal, sp, sn = (int(x) for x in g3[tag + "/meta"])
         frames, sched, want = g3[tag + "/frames"], g3[tag + "/schedule"], g3[tag + "/ops"]
-        table, store = device_tables.get(mode, pal)
-        fm = torch.from_numpy(np.ascontiguousarray(frames[None, :, 0])).cuda()
-        fa = torch.from_numpy(np.ascontiguousarray(frames[None, :, 1])).cuda() if mode == 1 else None
-        segs = [(int(f), int(a), 1, int(k)) for (f, a, k) in sched]
-        py, npw = _seed_states(O, sp, sn)
+        fm, fa = H.device_frames(mode, [frames])
+        segs = H.segments(sched)
         outs = []
         for via_op in (True, False):
-            enc = native.Encoder(mode, table, store, 1, dm=device_tables.dm[(mode, pal)])
-            enc.set_state(native.STATE_RNG_PY, py)
-            enc.set_state(native.STATE_RNG_NP, npw)
+            enc = H.make_encoder(native, device_tables, mode, pal, rng=[(sp, sn)], O=O)
             ops = torch_ops.encode_via_op(enc, fm, fa, segs) if via_op else enc.encode(fm, fa, segs)
             enc.check()
             outs.append(ops.cpu().numpy()[0])
@@ -53,11 +49,11 @@ def test_stream_batch_goes_through_the_operators(native, device_tables):
     assert np.array_equal(outs[0], outs[1])
     # per-stream schedules through encode_streams
     import torch_ops
-    enc = native.Encoder(1, table, store, 2, dm=device_tables.dm[(1, 5)])
+    enc = H.make_encoder(native, device_tables, 1, n_streams=2)
     sched = [[(0, 0, 1, 100), (0, 1, 1, 50)], [(1, 1, 1, 70)]]
     ref, totals = enc.encode_streams(fm[:2], fa[:2], sched)
     enc.check()
-    enc2 = native.Encoder(1, table, store, 2, dm=device_tables.dm[(1, 5)])
+    enc2 = H.make_encoder(native, device_tables, 1, n_streams=2)
     flat = torch.tensor([list(g) for s in sched for g in s], dtype=torch.int32)
     begin = torch.tensor([0, 2, 3], dtype=torch.int32)
     out = torch.zeros_like(ref)
@@ -94,7 +90,7 @@ def test_mismatched_batches_raise_instead_of_launching(native, device_tables):
     import stream_batch
     table, store = device_tables.get(1, 5)
     fm, fa = stream_batch.synth_frames_torch(4, 2, True, seed=3)
-    enc = native.Encoder(1, table, store, 4, dm=device_tables.dm[(1, 5)])
+    enc = H.make_encoder(native, device_tables, 1, n_streams=4)
     assert native.encoder_info(enc.handle) == (1, 4)
     segs = [(0, 0, 1, 20)]
     seg_t = torch.tensor(segs, dtype=torch.int32)
@@ -123,7 +119,7 @@ def test_mismatched_batches_raise_instead_of_launching(native, device_tables):
     # ... and the well-formed calls still run, and agree
     torch.ops.iivision.encode(enc.handle, fm, fa, seg_t, good_out)
     enc.check()
-    enc2 = native.Encoder(1, table, store, 4, dm=device_tables.dm[(1, 5)])
+    enc2 = H.make_encoder(native, device_tables, 1, n_streams=4)
     ref = enc2.encode(fm, fa, segs)
     enc2.check()
     assert torch.equal(good_out, ref)
