@@ -149,6 +149,8 @@ _SIGNATURES = {
     "iiv_a2m_scan": (_i32, [_vp, _i32, _vp, _sz, _vp, _vp, _vp]),
     "iiv_a2m_decode": (_i32, [_vp, _i32, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
     "iiv_a2m_replay": (_i32, [_vp, _i32, _vp, _sz, _vp, _lg, _lg, _i32, _vp, _vp, _vp, _vp, _vp]),
+    # ---- f10: direct ingest
+    "iiv_frames_to_memory_maps_direct": (_i32, [_i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 SYMBOLS = list(_SIGNATURES)
 
@@ -800,6 +802,29 @@ def frames_to_memory_maps_diffused(mode, palette_rgb, rgb, weights, divisor, out
     check(lib().iiv_frames_to_memory_maps_diffused(mode, hptr(pal), n, dptr(rgb), hptr(w), int(divisor), dptr(main), dptr(aux),
                                                    stream_ptr()))
     return main, aux
+
+
+# ---- f10: direct ingest ---------------------------------------------------------------
+
+def frames_to_memory_maps_direct(mode, palette_rgb, rgb, dither=0, cost=False, out=None):
+    """rgb: CUDA uint8 (n, 192, 280 or 560, 3) -> (main, aux) CUDA uint8 (n, 32, 256), aux None for HGR: per screen row the bytes
+    whose RENDERED dots are nearest the source (include/iivision.h: iiv_frames_to_memory_maps_direct).  dither: 0..255, the
+    amplitude of the ordered dither added to the target (no error diffusion here).  cost=True: (main, aux, cost), cost a CUDA
+    uint64 (n,) tensor of the frames' summed squared differences.  out and the asynchrony: exactly as frames_to_memory_maps."""
+    torch = _torch()
+    if mode not in (HGR, DHGR):
+        raise ValueError("mode must be HGR or DHGR")
+    _cuda_u8(rgb, "rgb")
+    if rgb.dim() != 4 or int(rgb.shape[1]) != 192 or int(rgb.shape[2]) not in REF_WIDTHS or int(rgb.shape[3]) != 3:
+        raise ValueError("rgb has shape %s, not (n, 192, 280 or 560, 3)" % (tuple(rgb.shape),))
+    n = int(rgb.shape[0])
+    pal = np.ascontiguousarray(palette_rgb, dtype=np.uint8).reshape(48)
+    main, aux = _memory_maps_out(mode, n, out)
+    d_cost = torch.empty((n,), dtype=torch.uint64, device="cuda") if cost else None
+    if n:   # (empty tensors have no address to hand over)
+        check(lib().iiv_frames_to_memory_maps_direct(mode, hptr(pal), n, dptr(rgb), int(rgb.shape[2]), int(dither), dptr(main), dptr(aux),
+                                                     dptr(d_cost), stream_ptr()))
+    return (main, aux, d_cost) if cost else (main, aux)
 
 
 # ---- f6: mono playback mode -----------------------------------------------------------

@@ -64,10 +64,12 @@ class ArrayFrameGrabber(FrameGrabber):
     (192, 280) for HGR --, resize=True resizes to that size, and the conversion is iiv_frames_to_memory_maps_mono.
     dither: 0..255 = amplitude of the ordered dither; "diffusion" = Floyd-Steinberg (iiv_frames_to_memory_maps); a name of
     DIFFUSION_KERNELS or (3 x 5 weights, divisor) = error diffusion with that kernel (iiv_frames_to_memory_maps_diffused;
-    colour palettes only)."""
+    colour palettes only); "direct" = per screen row the bytes whose rendered dots are nearest the frame
+    (iiv_frames_to_memory_maps_direct; colour palettes only), `amplitude` 0..255 the ordered dither added to its
+    target -- `amplitude` is legal with "direct" alone."""
 
     def __init__(self, frames_rgb, mode: VideoMode, palette: Palette = Palette.NTSC, dither=32,
-                 input_frame_rate: float = 30, batch: int = 256, resize: bool = False):
+                 input_frame_rate: float = 30, batch: int = 256, resize: bool = False, amplitude: int = 0):
         super().__init__(mode)
         rgb = np.asarray(frames_rgb)
         mode_id = native.DHGR if mode == VideoMode.DHGR else native.HGR
@@ -85,6 +87,15 @@ class ArrayFrameGrabber(FrameGrabber):
         # diffusion, the kind of dither the reference asks bmp2dhr for (D9, frame_grabber.py:80-82,106-108)
         # a name of DIFFUSION_KERNELS, or (3 x 5 weights, divisor): error diffusion with that kernel (csrc/iiv_diffuse.hip)
         self.diffusion_kernel = None
+        self.direct = dither == "direct"
+        if not self.direct and amplitude != 0:
+            raise ValueError("amplitude goes with dither=\"direct\" alone (an ordered dither's amplitude is `dither` itself)")
+        if self.direct:
+            if palette == Palette.MONO:
+                raise ValueError("Palette.MONO shows dots, not windows: dither=\"direct\" is the colour conversion's")
+            if not 0 <= int(amplitude) <= 255:
+                raise ValueError("amplitude must be 0..255")
+            dither = int(amplitude)
         if isinstance(dither, str) and dither != "diffusion":
             if dither not in DIFFUSION_KERNELS:
                 raise ValueError("dither: unknown diffusion kernel %r (one of %s, or \"diffusion\")" % (dither, ", ".join(sorted(DIFFUSION_KERNELS))))
@@ -117,6 +128,8 @@ class ArrayFrameGrabber(FrameGrabber):
         if self.palette == Palette.MONO:
             return native.frames_to_memory_maps_mono(mode, rgb, self.dither)
         pal = palette_mod.PALETTES[self.palette].rgb_array()
+        if self.direct:
+            return native.frames_to_memory_maps_direct(mode, pal, rgb, self.dither)
         if self.diffusion_kernel is not None:
             return native.frames_to_memory_maps_diffused(mode, pal, rgb, *self.diffusion_kernel)
         return native.frames_to_memory_maps(mode, pal, rgb, self.dither)

@@ -771,6 +771,34 @@ int iiv_a2m_replay(const iiv_a2m_reader *reader, int n_streams, const uint8_t *d
                    long first_snap, long snap_every, int n_snaps, const uint8_t *d_init_main, const uint8_t *d_init_aux,
                    uint8_t *d_main, uint8_t *d_aux, void *stream);
 
+/* ==== f10: direct ingest ====================================================
+ * RGB frames -> memory maps chosen THROUGH the colour model: the reference README's "direct image encoding".  f3 picks, per
+ * 140-wide colour pixel, the nearest colour and writes its aligned dot quad; the screen shows a sliding four-dot window (f7),
+ * so every boundary between two different quads shows dots of colours nobody chose.  Here every screen row gets the byte row
+ * whose RENDERED dots are nearest the source.  Rows are independent, the arithmetic is integer, and the rule is global, so
+ * every implementation agrees byte for byte (tests/direct_model.py restates it in numpy and is held to it by exhaustive
+ * search through tests/render_model.py; csrc/iiv_direct.hip computes it).
+ *   Source.  d_rgb is [n][192][ref_width][3] u8, ref_width 280 or 560; as in f8, R[y][x][c] = rgb[y][x * ref_width / 560][c] for
+ *   dot x in 0..559.
+ *   Target.  T[y][x][c] = clamp(R[y][x][c] + floor((2 * B[y & 3][(x >> 2) & 3] - 15) * dither / 16), 0, 255), B the 4x4 Bayer
+ *   matrix of f3, dither 0..255 (indexed by the quad x >> 2: f3's colour pixel k).  IIV_DITHER_DIFFUSION is refused.
+ *   What a byte row shows is exactly f7: the row's bytes (DHGR: 80, aux[0], main[0], aux[1], ...; HGR: 40) give the dots by
+ *   f7's rules -- HGR's palette-bit shift, bit 6 of the byte to the left and the dropped 561st dot included -- and dot x shows
+ *   value(x) = rol4(w, (x + 1) & 3), w as in f7, dots left of the row 0.
+ *   Cost of a byte row: the sum over x < 560, c < 3 of (palette_rgb[3 * value(x) + c] - T[y][x][c])^2 (at most 560 * 3 * 255^2).
+ *   The row written: among all byte rows with bit 7 clear (DHGR), or all byte rows (HGR: bit 7 is the palette bit), one of
+ *   least cost; among several of least cost the one whose value sum b[i] * 256^i is smallest, i the byte's position in the
+ *   sequence above (the last byte is the most significant).
+ *   Bytes land at y_to_base_addr (screen.py:16-22); the screen holes are written as 0; d_aux is ignored in HGR.
+ *   d_cost, if not NULL, is [n] uint64 and is overwritten with the sum of the frame's 192 row costs.  With dither 0 that is
+ *   iiv_render_error's level 0 of the maps written, summed over the channels -- and no memory map has a smaller one.
+ * d_rgb 4-byte aligned, d_main / d_aux / d_cost 8-byte aligned.  Asynchronous on `stream`; the palette is read before the call
+ * returns; nothing is allocated.  n_frames == 0 succeeds and writes nothing.  IIV_ERR_INVALID before anything is launched,
+ * with nothing written: a bad mode, n_frames < 0, a NULL palette_rgb, d_rgb or d_main, a NULL d_aux in DHGR, ref_width not
+ * 280 or 560, dither outside 0..255, a bad alignment. */
+int iiv_frames_to_memory_maps_direct(int mode, const uint8_t palette_rgb[48], int n_frames, const uint8_t *d_rgb, int ref_width,
+                                     int dither, uint8_t *d_main, uint8_t *d_aux, uint64_t *d_cost, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

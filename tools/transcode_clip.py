@@ -57,7 +57,9 @@ def main():
                     help="MONO: a monochrome monitor -- one source pixel per dot (560x192 DHGR, 280x192 HGR), dot-level distances (DESIGN.md 12)")
     ap.add_argument("--dither", default="diffusion",
                     help='"diffusion" (Floyd-Steinberg), the amplitude 0..255 of the ordered dither, or an error-diffusion kernel by name: '
-                         'floyd-steinberg, jarvis, stucki, atkinson, burkes, sierra, sierra-2, sierra-lite, buckels (frame_grabber.DIFFUSION_KERNELS)')
+                         'floyd-steinberg, jarvis, stucki, atkinson, burkes, sierra, sierra-2, sierra-lite, buckels (frame_grabber.DIFFUSION_KERNELS), or "direct": per screen row the bytes whose rendered dots '
+                         'are nearest the frame (DESIGN.md 22)')
+    ap.add_argument("--amplitude", type=int, default=0, help='with --dither direct: the ordered dither 0..255 added to its target')
     ap.add_argument("--dbg", help="player/iivision.dbg (opcode entry points)")
     ap.add_argument("--tick", type=int, default=34, help="without audio: speaker duty cycle of every opcode (4..66, even)")
     ap.add_argument("--audio", help="16-bit PCM .wav: the clip's audio track")
@@ -95,7 +97,8 @@ def main():
     rgb = np.load(a.frames) if a.frames else test_card(a.synthetic, native.MONO_SIZE[mode][1] if pal_id == palette.Palette.MONO else 280)
     t0 = time.perf_counter()
     grab = frame_grabber.ArrayFrameGrabber(rgb, video_mode.VideoMode[a.mode], pal_id,
-                                           dither=int(a.dither) if a.dither.isdigit() else a.dither, resize=True)
+                                           dither=int(a.dither) if a.dither.isdigit() else a.dither, resize=True,
+                                           amplitude=a.amplitude)
     main_maps, aux_maps = grab.memory_maps()                       # (n, 32, 256) on the device
     dm = palette.diff_matrix(pal_id)                               # CIE2000 of the palette's colours; MONO: the dot distance
     table = native.build_table(mode, dm, True)
