@@ -284,6 +284,172 @@ int launch_v(const uint8_t *src, size_t src_fs, size_t src_rs, int frames, int r
     return IIV_OK;
 }
 
+// ---- f11: YUV 4:2:0 sources (include/iivision.h: iiv_resize_frames_yuv420) ------------------------------------
+// The conversion is fused into the horizontal pass: resize_h_yuv_kernel is resize_h_kernel with another loader.  Where the
+// horizontal pass does not come first (same size, vertical only, h > 100 w) yuv_to_rgb_kernel writes the RGB frames of a chunk
+// into a stream-ordered scratch and iiv_resize_frames takes them from there.
+
+struct YuvMatrix {   // (y_off, ky, rv, gu, gv, bu) of the header, by value in the kernel's arguments
+    int32_t y_off, ky, rv, gu, gv, bu;
+};
+
+struct YuvSrc {   // the planes of a batch of frames: byte strides, ps = the chroma pixel stride (1 planar, 2 interleaved)
+    const uint8_t *y;
+    size_t y_fs, y_rs;
+    const uint8_t *u, *v;
+    size_t c_fs, c_rs;
+    int ps;
+};
+
+// what two neighbouring chroma samples add to R, G and B of the pixels under them, the rounding 128 included
+struct ChromaTerms {
+    int32_t r[2], g[2], b[2];
+};
+
+// uu / vv: sample 0 in byte 0, sample 1 in byte ps
+__device__ inline ChromaTerms chroma_terms(uint32_t uu, uint32_t vv, int ps, const YuvMatrix &m)
+{
+    ChromaTerms t;
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+        const int d = (int)((uu >> (8 * ps * s)) & 0xffu) - 128, e = (int)((vv >> (8 * ps * s)) & 0xffu) - 128;
+        t.r[s] = __mul24(m.rv, e) + 128;
+        t.g[s] = __mul24(m.gu, d) + __mul24(m.gv, e) + 128;
+        t.b[s] = __mul24(m.bu, d) + 128;
+    }
+    return t;
+}
+
+// (the empty asm keeps the byte a 32-bit value of its own: where two of them meet as clamp(a >> 8) | clamp(b >> 8) << 8, hipcc
+//  selects gfx950's v_ashr_pk_u8_i32 for the pair, and yuv_to_rgb_kernel then stored bytes 2 and 3 of its dwords with bits of
+//  the unclamped sums in them on an MI355X -- DESIGN.md 23)
+__device__ inline uint32_t clamp_shift8(int32_t v)
+{
+    v >>= 8;
+    uint32_t b = (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+    asm volatile("" : "+v"(b));
+    return b;
+}
+
+// four pixels of one row (yy: pixel j in byte j; samples 0, 0, 1, 1 above them) -> r | g << 8 | b << 16 each
+__device__ inline uint4 yuv_to_rgb4(uint32_t yy, const ChromaTerms &t, const YuvMatrix &m)
+{
+    uint32_t q[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int32_t c = __mul24((int)((yy >> (8 * j)) & 0xffu) - m.y_off, m.ky);
+        const int s = j >> 1;
+        q[j] = clamp_shift8(c + t.r[s]) | (clamp_shift8(c + t.g[s]) << 8) | (clamp_shift8(c + t.b[s]) << 16);
+    }
+    return make_uint4(q[0], q[1], q[2], q[3]);
+}
+
+// the chroma terms of pixels 4 g .. 4 g + 3 of source row `row` of frame f (aligned dword loads inside the chroma row only)
+__device__ inline ChromaTerms load_chroma(const YuvSrc &s, size_t f, int row, int g, int w, const YuvMatrix &m)
+{
+    const size_t off = f * s.c_fs + (size_t)(row >> 1) * s.c_rs;
+    const size_t len = (size_t)(((w + 1) >> 1) - 1) * s.ps + 1, at = (size_t)(2 * g) * s.ps;
+    const uint8_t *ur = s.u + off, *vr = s.v + off;
+    return chroma_terms(load_unaligned(ur + at, ur + len), load_unaligned(vr + at, vr + len), s.ps, m);
+}
+
+// Horizontal pass over a 4:2:0 source: resize_h_kernel, the R rows' pixels converted as they are unpacked into LDS.  R = 2:
+// rows (2 k, 2 k + 1), which share their chroma row (an odd h leaves the last row alone).
+template <int R>
+__global__ __launch_bounds__(1024) void resize_h_yuv_kernel(YuvSrc s, YuvMatrix m, int rows, int w, int W,
+                                                            const int2 *__restrict__ bounds, const int32_t *__restrict__ k_taps,
+                                                            uint8_t *__restrict__ dst, size_t dst_fs, size_t dst_rs)
+{
+    extern __shared__ uint32_t px[];   // [R][w_pad] pixels, r | g << 8 | b << 16
+    const int groups = (rows + R - 1) / R;
+    const int f = blockIdx.x / groups, r0 = (blockIdx.x % groups) * R;
+    const int w_pad = (w + 3) & ~3;
+    const int n4 = w_pad >> 2;
+    for (int g = threadIdx.x; g < n4; g += blockDim.x) {
+        const ChromaTerms t = load_chroma(s, (size_t)f, r0, g, w, m);
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            if (r0 + r >= rows) break;
+            const uint8_t *row = s.y + (size_t)f * s.y_fs + (size_t)(r0 + r) * s.y_rs;
+            *(uint4 *)&px[r * w_pad + 4 * g] = yuv_to_rgb4(load_unaligned(row + 4 * (size_t)g, row + w), t, m);
+        }
+    }
+    __syncthreads();
+    const int x = threadIdx.x;
+    if (x >= W) return;
+    const int2 bd = bounds[x];
+    int32_t acc[R][3];
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r][0] = acc[r][1] = acc[r][2] = 1 << (kPrecisionBits - 1);
+    const uint32_t *pr = px + bd.x;
+    const int32_t *kp = k_taps + x;
+#pragma unroll 4
+    for (int j = 0; j < bd.y; j++) {
+        const int32_t c = kp[(size_t)j * W];
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const uint32_t v = pr[r * w_pad + j];
+            acc[r][0] += __mul24((int)(v & 0xffu), c);
+            acc[r][1] += __mul24((int)((v >> 8) & 0xffu), c);
+            acc[r][2] += __mul24((int)(v >> 16), c);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        if (r0 + r >= rows) break;
+        uint8_t *o = dst + (size_t)f * dst_fs + (size_t)(r0 + r) * dst_rs + 3 * (size_t)x;
+        o[0] = (uint8_t)clamp_shift(acc[r][0]);
+        o[1] = (uint8_t)clamp_shift(acc[r][1]);
+        o[2] = (uint8_t)clamp_shift(acc[r][2]);
+    }
+}
+
+// The conversion alone: thread = four pixels of one row -> twelve bytes of dst [frames][rows][dst_rs], dst 4-byte aligned
+// and dst_rs = 3 w_pad (the last group's pad pixels land inside the row's stride).  `total` = frames * rows * w_pad / 4.
+__global__ __launch_bounds__(256) void yuv_to_rgb_kernel(YuvSrc s, YuvMatrix m, int rows, int w, size_t total,
+                                                         uint8_t *__restrict__ dst, size_t dst_fs, size_t dst_rs)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int n4 = (w + 3) >> 2;
+    const int g = (int)(i % n4);
+    const size_t fr = i / n4, f = fr / rows;
+    const int y = (int)(fr % rows);
+    const ChromaTerms t = load_chroma(s, f, y, g, w, m);
+    const uint8_t *row = s.y + f * s.y_fs + (size_t)y * s.y_rs;
+    const uint4 q = yuv_to_rgb4(load_unaligned(row + 4 * (size_t)g, row + w), t, m);
+    uint32_t *o = (uint32_t *)(dst + f * dst_fs + (size_t)y * dst_rs + 12 * (size_t)g);
+    o[0] = q.x | (q.y << 24);
+    o[1] = (q.y >> 8) | (q.z << 16);
+    o[2] = (q.z >> 16) | (q.w << 8);
+}
+
+YuvSrc from_frame(YuvSrc s, int f0)
+{
+    s.y += (size_t)f0 * s.y_fs;
+    s.u += (size_t)f0 * s.c_fs;
+    s.v += (size_t)f0 * s.c_fs;
+    return s;
+}
+
+int launch_h_yuv(const YuvSrc &src, const YuvMatrix &m, int frames, int rows, int w, int W, const Table &t, uint8_t *dst,
+                 size_t dst_fs, size_t dst_rs, hipStream_t st)
+{
+    const int threads = (W + 63) & ~63;
+    const int w_pad = (w + 3) & ~3;
+    const int R = w_pad <= 4096 ? 2 : 1;
+    const unsigned bpf = (unsigned)((rows + R - 1) / R);
+    const int step = frames_per_launch(bpf, (size_t)threads);
+    for (int f0 = 0; f0 < frames; f0 += step) {
+        const int fn = frames - f0 < step ? frames - f0 : step;
+        if (int rc = launch(R == 2 ? resize_h_yuv_kernel<2> : resize_h_yuv_kernel<1>, "resize_h_yuv_kernel launch", dim3((unsigned)fn * bpf),
+                            dim3(threads), (size_t)R * w_pad * 4, st, from_frame(src, f0), m, rows, w, W, t.bounds, t.k_taps,
+                            dst + (size_t)f0 * dst_fs, dst_fs, dst_rs))
+            return rc;
+    }
+    return IIV_OK;
+}
+
 }  // namespace
 }  // namespace iiv
 
@@ -354,6 +520,83 @@ extern "C" int iiv_resize_frames(int n, int h, int w, const uint8_t *d_src, size
             rc = launch_h(s, frame_stride, row_stride, fn, h, w, W, *th, mid, mid_fs, mid_rs, st);
             if (!rc) rc = launch_v(mid, mid_fs, mid_rs, fn, 3 * W, H, *tv, d, dst_fs, dst_rs, st);
         }
+    }
+    const int rc_free = hip_check(hipFreeAsync(mid, st), "hipFreeAsync(resize scratch)");
+    return rc ? rc : rc_free;
+}
+
+extern "C" int iiv_resize_frames_yuv420(int n, int h, int w, const uint8_t *d_y, size_t y_frame_stride, size_t y_row_stride,
+                                        const uint8_t *d_u, const uint8_t *d_v, size_t c_frame_stride, size_t c_row_stride,
+                                        int c_pixel_stride, const int32_t matrix[6], int H, int W, uint8_t *d_dst, void *stream)
+{
+    if (n < 0 || h < 1 || h > kMaxIn || w < 1 || w > kMaxIn || H < 1 || H > kMaxOut || W < 1 || W > kMaxOut)
+        return set_error(IIV_ERR_INVALID, "iiv_resize_frames_yuv420: n >= 0, h, w in 1..%d, H, W in 1..%d (got n %d, %dx%d -> %dx%d)",
+                         kMaxIn, kMaxOut, n, h, w, H, W);
+    if (c_pixel_stride != 1 && c_pixel_stride != 2)
+        return set_error(IIV_ERR_INVALID, "iiv_resize_frames_yuv420: c_pixel_stride 1 (planar) or 2 (interleaved), got %d", c_pixel_stride);
+    if (!matrix) return set_error(IIV_ERR_INVALID, "iiv_resize_frames_yuv420: matrix NULL");
+    if (matrix[0] < 0 || matrix[0] > 255) return set_error(IIV_ERR_INVALID, "iiv_resize_frames_yuv420: y_off 0..255, got %d", (int)matrix[0]);
+    for (int i = 1; i < 6; i++)
+        if (matrix[i] < -1023 || matrix[i] > 1023)
+            return set_error(IIV_ERR_INVALID, "iiv_resize_frames_yuv420: coefficients in -1023..1023, matrix[%d] is %d", i, (int)matrix[i]);
+    if (n == 0) return IIV_OK;
+    const int ch = (h + 1) / 2, cw = (w + 1) / 2;
+    const size_t y_frame = (size_t)(h - 1) * y_row_stride + (size_t)w;
+    const size_t c_row = (size_t)(cw - 1) * c_pixel_stride + 1, c_frame = (size_t)(ch - 1) * c_row_stride + c_row;
+    if (!d_y || !d_u || !d_v || !d_dst || (h > 1 && y_row_stride < (size_t)w) || (n > 1 && y_frame_stride < y_frame))
+        return set_error(IIV_ERR_INVALID, "iiv_resize_frames_yuv420: a plane or d_dst NULL, or Y rows / frames overlap (y_row_stride %zu < %d "
+                         "or y_frame_stride %zu < %zu)", y_row_stride, w, y_frame_stride, y_frame);
+    if ((ch > 1 && c_row_stride < c_row) || (n > 1 && c_frame_stride < c_frame))
+        return set_error(IIV_ERR_INVALID, "iiv_resize_frames_yuv420: chroma rows / frames overlap (c_row_stride %zu < %zu or c_frame_stride "
+                         "%zu < %zu)", c_row_stride, c_row, c_frame_stride, c_frame);
+    const hipStream_t st = (hipStream_t)stream;
+    const YuvMatrix m = {matrix[0], matrix[1], matrix[2], matrix[3], matrix[4], matrix[5]};
+    const YuvSrc src = {d_y, y_frame_stride, y_row_stride, d_u, d_v, c_frame_stride, c_row_stride, c_pixel_stride};
+    const bool resize_w = W != w, resize_h = H != h;
+    const size_t dst_rs = 3 * (size_t)W, dst_fs = (size_t)H * dst_rs;
+    const Table *th = nullptr, *tv = nullptr;
+    int rc = IIV_OK;
+    if (resize_w && (rc = get_table(w, W, &th))) return rc;
+    if ((resize_h || !resize_w) && (rc = get_table(h, H, &tv))) return rc;
+    if (!resize_w || (resize_h && h > 100 * w)) {
+        // the horizontal pass is not the first: convert a chunk of frames into scratch, then the RGB path as it is
+        const size_t rgb_rs = 3 * (size_t)((w + 3) & ~3), rgb_fs = (size_t)h * rgb_rs, n4 = (size_t)((w + 3) >> 2);
+        size_t chunk = kChunkMidBytes / rgb_fs;
+        if (chunk < 1) chunk = 1;
+        if (chunk > (size_t)n) chunk = (size_t)n;
+        uint8_t *rgb = nullptr;
+        IIV_HIP(hipMallocAsync((void **)&rgb, chunk * rgb_fs, st));
+        for (int f0 = 0; f0 < n && !rc; f0 += (int)chunk) {
+            const int fn = n - f0 < (int)chunk ? n - f0 : (int)chunk;
+            const size_t total = (size_t)fn * h * n4;   // (at most 32 MiB / 12, or one frame's 2^24)
+            rc = launch(yuv_to_rgb_kernel, "yuv_to_rgb_kernel launch", dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                        from_frame(src, f0), m, h, w, total, rgb, rgb_fs, rgb_rs);
+            if (!rc) rc = iiv_resize_frames(fn, h, w, rgb, rgb_fs, rgb_rs, H, W, d_dst + (size_t)f0 * dst_fs, stream);
+        }
+        const int rc_free = hip_check(hipFreeAsync(rgb, st), "hipFreeAsync(yuv scratch)");
+        return rc ? rc : rc_free;
+    }
+    if (!resize_h) {
+        // the horizontal pass alone, straight into d_dst
+        const int step = 65536;
+        for (int f0 = 0; f0 < n; f0 += step) {
+            const int fn = n - f0 < step ? n - f0 : step;
+            if ((rc = launch_h_yuv(from_frame(src, f0), m, fn, h, w, W, *th, d_dst + (size_t)f0 * dst_fs, dst_fs, dst_rs, st))) return rc;
+        }
+        return IIV_OK;
+    }
+    // the common path: the fused horizontal pass into the (h, W) scratch iiv_resize_frames would use, then its vertical pass
+    const size_t mid_rs = (3 * (size_t)W + 3) & ~(size_t)3, mid_fs = (size_t)h * mid_rs;
+    size_t chunk = kChunkMidBytes / mid_fs;
+    if (chunk < 1) chunk = 1;
+    if (chunk > 65536) chunk = 65536;
+    if (chunk > (size_t)n) chunk = (size_t)n;
+    uint8_t *mid = nullptr;
+    IIV_HIP(hipMallocAsync((void **)&mid, chunk * mid_fs, st));
+    for (int f0 = 0; f0 < n && !rc; f0 += (int)chunk) {
+        const int fn = n - f0 < (int)chunk ? n - f0 : (int)chunk;
+        rc = launch_h_yuv(from_frame(src, f0), m, fn, h, w, W, *th, mid, mid_fs, mid_rs, st);
+        if (!rc) rc = launch_v(mid, mid_fs, mid_rs, fn, 3 * W, H, *tv, d_dst + (size_t)f0 * dst_fs, dst_fs, dst_rs, st);
     }
     const int rc_free = hip_check(hipFreeAsync(mid, st), "hipFreeAsync(resize scratch)");
     return rc ? rc : rc_free;

@@ -151,6 +151,8 @@ _SIGNATURES = {
     "iiv_a2m_replay": (_i32, [_vp, _i32, _vp, _sz, _vp, _lg, _lg, _i32, _vp, _vp, _vp, _vp, _vp]),
     # ---- f10: direct ingest
     "iiv_frames_to_memory_maps_direct": (_i32, [_i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    # ---- f11: YUV 4:2:0 sources
+    "iiv_resize_frames_yuv420": (_i32, [_i32, _i32, _i32, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _i32, _vp, _i32, _i32, _vp, _vp]),
 }
 SYMBOLS = list(_SIGNATURES)
 
@@ -1169,4 +1171,66 @@ def resize_frames(rgb, size=RESIZE_SIZE, out=None):
     with torch.cuda.device(rgb.device):
         check(lib().iiv_resize_frames(n, h, w, dptr(rgb), int(rgb.stride(0)), int(rgb.stride(1)), H, W, dptr(out),
                                       stream_ptr()))
+    return out
+
+
+# ---- f11: YUV 4:2:0 sources ---------------------------------------------------------
+
+# (y_off, ky, rv, gu, gv, bu) of include/iivision.h f11 by name; any other matrix is such a tuple
+YUV_MATRICES = {
+    "bt601": (16, 298, 409, -100, -208, 516),   # limited range; the default: the reference's material is SD
+    "bt709": (16, 298, 459, -55, -136, 541),    # limited range
+    "jpeg": (0, 256, 359, -88, -183, 454),      # full range, JFIF
+}
+
+
+def yuv_matrix(matrix):
+    """A name of YUV_MATRICES or six integers -> the int32 array the C ABI takes (range errors are the library's)."""
+    if isinstance(matrix, str):
+        if matrix not in YUV_MATRICES:
+            raise ValueError("unknown YUV matrix %r (one of %s, or six integers)" % (matrix, ", ".join(sorted(YUV_MATRICES))))
+        matrix = YUV_MATRICES[matrix]
+    m = np.asarray(matrix)
+    if m.shape != (6,) or not np.issubdtype(m.dtype, np.integer):
+        raise ValueError("a YUV matrix is six integers (y_off, ky, rv, gu, gv, bu)")
+    return np.ascontiguousarray(m, dtype=np.int32)
+
+
+def _stride(t, dim, default):
+    """t.stride(dim) where it means something: a dimension of one element has no stride of its own"""
+    return int(t.stride(dim)) if int(t.shape[dim]) > 1 else default
+
+
+def resize_frames_yuv420(y, u, v, size=RESIZE_SIZE, matrix="bt601", out=None):
+    """resize_frames of the RGB frames that 4:2:0 planes define (include/iivision.h: iiv_resize_frames_yuv420), converted
+    inside the resize's horizontal pass.  y: CUDA uint8 (n, h, w), unit pixel stride, any row and frame strides; u, v: CUDA
+    uint8 (n, (h + 1) // 2, (w + 1) // 2) views with the same strides, pixel stride 1 (planar I420) or 2 (uv[..., 0] and
+    uv[..., 1] of an (n, ch, cw, 2) NV12 tensor; swapped for NV21).  matrix: a name of YUV_MATRICES or (y_off, ky, rv, gu,
+    gv, bu).  -> CUDA uint8 (n, H, W, 3); out, and the asynchrony on torch's current stream, exactly as resize_frames."""
+    torch = _torch()
+    H, W = (int(x) for x in size)
+    m = yuv_matrix(matrix)
+    for t, name in ((y, "y"), (u, "u"), (v, "v")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3):
+            raise ValueError("%s must be a CUDA uint8 tensor of three dimensions" % name)
+    n, h, w = (int(x) for x in y.shape)
+    chroma = (n, (h + 1) // 2, (w + 1) // 2)
+    if tuple(u.shape) != chroma or tuple(v.shape) != chroma:
+        raise ValueError("u and v have shapes %s and %s; y %s needs chroma planes %s" % (tuple(u.shape), tuple(v.shape), (n, h, w), chroma))
+    if _stride(y, 2, 1) != 1:
+        raise ValueError("y must have pixel stride 1")
+    ps = _stride(u, 2, _stride(v, 2, 1))
+    c_rs = _stride(u, 1, _stride(v, 1, chroma[2] * ps))
+    c_fs = _stride(u, 0, _stride(v, 0, chroma[1] * c_rs))
+    if (_stride(v, 2, ps), _stride(v, 1, c_rs), _stride(v, 0, c_fs)) != (ps, c_rs, c_fs):
+        raise ValueError("u and v must have the same strides")
+    if out is None:
+        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=y.device)
+    else:
+        _cuda_u8(out, "out")
+        if out.numel() != n * H * W * 3:
+            raise ValueError("out must hold n * %d * %d * 3 bytes" % (H, W))
+    with torch.cuda.device(y.device):
+        check(lib().iiv_resize_frames_yuv420(n, h, w, dptr(y), _stride(y, 0, h * _stride(y, 1, w)), _stride(y, 1, w), dptr(u), dptr(v),
+                                             c_fs, c_rs, ps, hptr(m), H, W, dptr(out), stream_ptr()))
     return out

@@ -43,6 +43,10 @@ DIFFUSION_KERNELS = {
     "buckels": (((0, 0, 0, 2, 1), (0, 1, 2, 1, 0), (0, 0, 1, 0, 0)), 8),
 }
 
+# 4:2:0 YCbCr -> RGB by name: (y_off, ky, rv, gu, gv, bu) of include/iivision.h f11 (the one table; native holds it because
+# native.resize_frames_yuv420 takes the names too).  ArrayFrameGrabber((y, u, v), ..., resize=True, yuv_matrix=<name or tuple>).
+YUV_MATRICES = native.YUV_MATRICES
+
 
 class FrameGrabber:
     """frame_grabber.py:18-24."""
@@ -53,6 +57,18 @@ class FrameGrabber:
 
     def frames(self) -> Iterator[Tuple[screen.MemoryMap, screen.MemoryMap]]:
         raise NotImplementedError
+
+
+def _upload_chroma(torch, u, v):
+    """The two chroma planes on the device.  Views of one interleaved array (NV12: v one byte behind u; NV21: in front) go up
+    as that array, once, and come back as its two views; anything else as two planar tensors."""
+    au, av = u.__array_interface__["data"][0], v.__array_interface__["data"][0]
+    if u.size and u.strides == v.strides and u.strides[2] == 2 and abs(au - av) == 1:
+        first = u if au < av else v
+        uv = np.lib.stride_tricks.as_strided(first, shape=first.shape + (2,), strides=first.strides + (1,))
+        d = torch.from_numpy(np.ascontiguousarray(uv)).cuda()
+        return (d[..., 0], d[..., 1]) if first is u else (d[..., 1], d[..., 0])
+    return torch.from_numpy(np.ascontiguousarray(u)).cuda(), torch.from_numpy(np.ascontiguousarray(v)).cuda()
 
 
 class ArrayFrameGrabber(FrameGrabber):
@@ -66,15 +82,35 @@ class ArrayFrameGrabber(FrameGrabber):
     DIFFUSION_KERNELS or (3 x 5 weights, divisor) = error diffusion with that kernel (iiv_frames_to_memory_maps_diffused;
     colour palettes only); "direct" = per screen row the bytes whose rendered dots are nearest the frame
     (iiv_frames_to_memory_maps_direct; colour palettes only), `amplitude` 0..255 the ordered dither added to its
-    target -- `amplitude` is legal with "direct" alone."""
+    target -- `amplitude` is legal with "direct" alone.
+    Frames as a decoder delivers them: a (y, u, v) triple of uint8 arrays, y (n, h, w) and u, v (n, (h + 1) // 2, (w + 1) // 2) --
+    planar I420, or uv[..., 0] and uv[..., 1] of an interleaved (n, ch, cw, 2) NV12 array, which is uploaded as it is --, with
+    resize=True and yuv_matrix a name of YUV_MATRICES or (y_off, ky, rv, gu, gv, bu): converted inside the device resize
+    (iiv_resize_frames_yuv420); frames that already have the target size go through the same call."""
 
     def __init__(self, frames_rgb, mode: VideoMode, palette: Palette = Palette.NTSC, dither=32,
-                 input_frame_rate: float = 30, batch: int = 256, resize: bool = False, amplitude: int = 0):
+                 input_frame_rate: float = 30, batch: int = 256, resize: bool = False, amplitude: int = 0, yuv_matrix="bt601"):
         super().__init__(mode)
-        rgb = np.asarray(frames_rgb)
+        self._yuv = None
+        if isinstance(frames_rgb, tuple) and len(frames_rgb) == 3:
+            if not resize:
+                raise ValueError("(y, u, v) frames are converted inside the device resize: pass resize=True")
+            y, u, v = (np.asarray(p) for p in frames_rgb)
+            if y.dtype != np.uint8 or y.ndim != 3 or u.dtype != np.uint8 or v.dtype != np.uint8:
+                raise ValueError("(y, u, v) frames must be uint8, y (n, h, w)")
+            chroma = (y.shape[0], (y.shape[1] + 1) // 2, (y.shape[2] + 1) // 2)
+            if u.shape != chroma or v.shape != chroma:
+                raise ValueError("u and v have shapes %s and %s; y %s needs chroma planes %s" % (u.shape, v.shape, y.shape, chroma))
+            self._yuv = (y, u, v)
+            self._matrix = native.yuv_matrix(yuv_matrix)
+            rgb = y   # (len() and the batching read the frame count from it)
+        else:
+            rgb = np.asarray(frames_rgb)
         mode_id = native.DHGR if mode == VideoMode.DHGR else native.HGR
         self.frame_size = native.MONO_SIZE[mode_id] if palette == Palette.MONO else native.RESIZE_SIZE   # (H, W)
-        if resize:
+        if self._yuv is not None:
+            pass   # (checked above)
+        elif resize:
             if rgb.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[3] != 3:
                 raise ValueError("frames must be uint8 (n, h, w, 3) RGB")
         elif rgb.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[1:] != self.frame_size + (3,):
@@ -115,6 +151,11 @@ class ArrayFrameGrabber(FrameGrabber):
         the reference picture screen.render_error measures a screen against."""
         import torch
         count = len(self._rgb) - first if count is None else count
+        if self._yuv is not None:
+            y, u, v = (p[first:first + count] for p in self._yuv)
+            d_u, d_v = _upload_chroma(torch, u, v)
+            return native.resize_frames_yuv420(torch.from_numpy(np.ascontiguousarray(y)).cuda(), d_u, d_v, size=self.frame_size,
+                                               matrix=self._matrix)
         rgb = torch.from_numpy(np.ascontiguousarray(self._rgb[first:first + count])).cuda()
         if self.resize and tuple(rgb.shape[1:3]) != self.frame_size:
             rgb = native.resize_frames(rgb, size=self.frame_size)   # on the same stream as the conversion behind it

@@ -799,6 +799,38 @@ int iiv_a2m_replay(const iiv_a2m_reader *reader, int n_streams, const uint8_t *d
 int iiv_frames_to_memory_maps_direct(int mode, const uint8_t palette_rgb[48], int n_frames, const uint8_t *d_rgb, int ref_width,
                                      int dither, uint8_t *d_main, uint8_t *d_aux, uint64_t *d_cost, void *stream);
 
+/* ==== f11: YUV 4:2:0 sources ================================================
+ * Decoders deliver 4:2:0 YCbCr (ffmpeg's yuv420p = I420, hardware decoders' NV12), not the packed RGB f5 takes.  This entry
+ * point is f5 on the RGB frame that the planes DEFINE, integer arithmetic only, so every implementation agrees byte for byte
+ * (tests/yuv_model.py restates it in numpy; csrc/iiv_resize.hip computes it).  For source pixel (x, y) of an
+ * h x w frame, >> arithmetic:
+ *     Yv = Y[y][x]                      Y plane: h rows of w bytes
+ *     U  = Cb[y >> 1][x >> 1]           chroma planes: (h + 1) / 2 rows of (w + 1) / 2 samples
+ *     V  = Cr[y >> 1][x >> 1]           (the NEAREST sample: no chroma interpolation, no siting -- stated, not an accident)
+ *     c  = Yv - y_off,  d = U - 128,  e = V - 128
+ *     R  = clamp((ky c        + rv e + 128) >> 8, 0, 255)
+ *     G  = clamp((ky c + gu d + gv e + 128) >> 8, 0, 255)
+ *     B  = clamp((ky c + bu d        + 128) >> 8, 0, 255)
+ * and that RGB frame goes through f5 exactly as iiv_resize_frames takes it: the same coefficients, passes, pass order and
+ * rounding.  matrix = (y_off, ky, rv, gu, gv, bu): y_off 0..255 and every coefficient in -1023..1023, else IIV_ERR_INVALID;
+ * every sum is then at most 3 * 1023 * 255 + 128 < 2^20 in magnitude -- int32 with eleven bits to spare.  BT.601 limited range
+ * is (16, 298, 409, -100, -208, 516), BT.709 limited (16, 298, 459, -55, -136, 541), full-range JFIF (0, 256, 359, -88, -183,
+ * 454) (frame_grabber.YUV_MATRICES).
+ * Planes (all strides in bytes, no alignment required; rows and frames of a plane must not overlap):
+ *     Y  of frame f, row y, pixel x   at d_y + f * y_frame_stride + y * y_row_stride + x
+ *     Cb of frame f, row j, sample i  at d_u + f * c_frame_stride + j * c_row_stride + i * c_pixel_stride, Cr the same from d_v
+ * c_pixel_stride is 1 for planar I420 / YV12 and 2 for the interleaved plane of NV12 (d_v = d_u + 1) / NV21 (d_u = d_v + 1);
+ * any other value is IIV_ERR_INVALID.  No byte outside the planes' rows influences the result.
+ * -> d_dst [n][H][W][3] contiguous.  Limits, errors (before anything is launched) and the stream contract are
+ * iiv_resize_frames' own, and so are the coefficient tables: one cache per (device, in, out) serves both entry points, the FIRST
+ * call with a size pair on a device builds and uploads them synchronously, every later call is asynchronous on `stream` with
+ * stream-ordered scratch.  `matrix` is read before the call returns.  Where the horizontal pass comes first (W != w, and not
+ * both H != h and h > 100 w -- every video shape) the conversion happens inside that pass and the full-size RGB frame never
+ * exists in memory; otherwise a conversion kernel writes a bounded chunk of RGB frames to scratch in front of the RGB path. */
+int iiv_resize_frames_yuv420(int n, int h, int w, const uint8_t *d_y, size_t y_frame_stride, size_t y_row_stride,
+                             const uint8_t *d_u, const uint8_t *d_v, size_t c_frame_stride, size_t c_row_stride, int c_pixel_stride,
+                             const int32_t matrix[6], int H, int W, uint8_t *d_dst, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

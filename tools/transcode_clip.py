@@ -9,13 +9,17 @@ cycle (`--tick`, 4..66 even: movie.py:104-107).
     python tools/transcode_clip.py --frames clip.npy --out clip.a2m --dbg /path/to/player/iivision.dbg
     python tools/transcode_clip.py --synthetic 90 --out /tmp/bars.a2m            # a moving test card
     python tools/transcode_clip.py --frames clip.npy --audio clip.wav --out clip.a2m
+    python tools/transcode_clip.py --yuv clip.yuv --size 640x480 --out clip.a2m   # ffmpeg -f rawvideo -pix_fmt yuv420p
 
 --palette MONO: the stream is encoded for a monochrome monitor: frames are taken at one pixel per dot
 (560x192 for DHGR, 280x192 for HGR; anything else is resized to that), converted by csrc/iiv_mono.hip and priced by
 palette.MonoPalette.diff_matrix().
 --frames: uint8 array (n, h, w, 3) of any size (1 <= h, w <= 8192): frames that are not 280x192 are resized on the
 device, byte for byte as the reference's Image.resize((280, 192), LANCZOS) (frame_grabber.py:75,100; csrc/iiv_resize.hip);
-a (n, 192, 280, 3) array is taken as it is.  --dbg: the player's cc65 debug file, from which the opcode entry points are read exactly as
+a (n, 192, 280, 3) array is taken as it is.
+--yuv FILE --size WxH [--pix-fmt yuv420p|nv12] [--yuv-matrix bt601|bt709|jpeg]: raw 4:2:0 frames as `ffmpeg -f rawvideo` writes
+them (yuv420p: the Y plane, then Cb, then Cr; nv12: the Y plane, then Cb and Cr interleaved), converted inside the device resize
+(include/iivision.h f11); a file that is not a whole number of frames is an error.  --dbg: the player's cc65 debug file, from which the opcode entry points are read exactly as
 opcodes._parse_symbol_table does (opcodes.py:168-185); without it the stream is written with placeholder addresses
 and is NOT playable (the tool says so).  --fourth / --joint: the two optional quality modes.
 --preview FILE.npy: also write what the stream puts on the screen, a uint8 array (frames, 192, 560, 3): the screen as it stands
@@ -47,10 +51,36 @@ def test_card(n, width=280):
     return out
 
 
+def read_yuv(path, size, pix_fmt):
+    """A raw 4:2:0 file -> (y, u, v) uint8 arrays, y (n, h, w), u / v (n, ch, cw): views of the file's bytes, NV12's interleaved"""
+    try:
+        w, h = (int(v) for v in size.lower().split("x"))
+    except ValueError:
+        raise SystemExit("--size: WxH, e.g. 640x480 (got %r)" % size)
+    if w < 1 or h < 1:
+        raise SystemExit("--size: WxH, both at least 1 (got %r)" % size)
+    ch, cw = (h + 1) // 2, (w + 1) // 2
+    frame = h * w + 2 * ch * cw
+    raw = np.fromfile(path, dtype=np.uint8)
+    if raw.size == 0 or raw.size % frame:
+        raise SystemExit("%s holds %d bytes: not a whole number of %dx%d %s frames of %d bytes (%d frames and %d bytes over)" % (
+            path, raw.size, w, h, pix_fmt, frame, raw.size // frame, raw.size % frame))
+    raw = raw.reshape(-1, frame)
+    y = raw[:, :h * w].reshape(-1, h, w)
+    if pix_fmt == "nv12":
+        uv = raw[:, h * w:].reshape(-1, ch, cw, 2)
+        return y, uv[..., 0], uv[..., 1]
+    return y, raw[:, h * w:h * w + ch * cw].reshape(-1, ch, cw), raw[:, h * w + ch * cw:].reshape(-1, ch, cw)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--frames", help=".npy file, uint8 (n, h, w, 3); resized to 280x192 on the device when not that size")
     ap.add_argument("--synthetic", type=int, default=0, help="instead of --frames: this many frames of a moving test card")
+    ap.add_argument("--yuv", help="instead of --frames: raw 4:2:0 frames (ffmpeg -f rawvideo), with --size")
+    ap.add_argument("--size", help="with --yuv: WxH of its frames")
+    ap.add_argument("--pix-fmt", choices=["yuv420p", "nv12"], default="yuv420p", help="with --yuv: the file's layout")
+    ap.add_argument("--yuv-matrix", choices=["bt601", "bt709", "jpeg"], default="bt601", help="with --yuv: YCbCr -> RGB (frame_grabber.YUV_MATRICES)")
     ap.add_argument("--out", required=True)
     ap.add_argument("--mode", choices=["DHGR", "HGR"], default="DHGR")
     ap.add_argument("--palette", choices=["NTSC", "IIGS", "MONO"], default="NTSC",
@@ -76,8 +106,10 @@ def main():
     a = ap.parse_args()
     if a.tick < 4 or a.tick > 66 or a.tick % 2:
         ap.error("--tick: 4..66, even")
-    if bool(a.frames) == bool(a.synthetic):
-        ap.error("one of --frames / --synthetic")
+    if bool(a.frames) + bool(a.synthetic) + bool(a.yuv) != 1:
+        ap.error("one of --frames / --synthetic / --yuv")
+    if bool(a.yuv) != bool(a.size):
+        ap.error("--yuv needs --size WxH (and --size goes with --yuv)")
     if a.audio and a.pcm:
         ap.error("one of --audio / --pcm")
     if bool(a.pcm) != bool(a.rate):
@@ -94,11 +126,11 @@ def main():
 
     mode = native.DHGR if a.mode == "DHGR" else native.HGR
     pal_id = palette.Palette[a.palette]
-    rgb = np.load(a.frames) if a.frames else test_card(a.synthetic, native.MONO_SIZE[mode][1] if pal_id == palette.Palette.MONO else 280)
+    rgb = read_yuv(a.yuv, a.size, a.pix_fmt) if a.yuv else np.load(a.frames) if a.frames else test_card(a.synthetic, native.MONO_SIZE[mode][1] if pal_id == palette.Palette.MONO else 280)
     t0 = time.perf_counter()
     grab = frame_grabber.ArrayFrameGrabber(rgb, video_mode.VideoMode[a.mode], pal_id,
                                            dither=int(a.dither) if a.dither.isdigit() else a.dither, resize=True,
-                                           amplitude=a.amplitude)
+                                           amplitude=a.amplitude, yuv_matrix=a.yuv_matrix)
     main_maps, aux_maps = grab.memory_maps()                       # (n, 32, 256) on the device
     dm = palette.diff_matrix(pal_id)                               # CIE2000 of the palette's colours; MONO: the dot distance
     table = native.build_table(mode, dm, True)
