@@ -1,6 +1,6 @@
 """Seeded differential fuzz of the kernels around the encoder against their numpy models: the generator that draws cases for
-resize_model, ingest_model / diffusion_model, mono_model, render_model / render_error_model, a2m_model, audio_model and
-bitmap_model (tests/fuzz_parity.py does the same for the encoder against the oracle).
+resize_model, ingest_model / diffusion_model, mono_model, render_model / render_error_model, a2m_model, audio_model,
+bitmap_model, yuv_model and direct_model (tests/fuzz_parity.py does the same for the encoder against the oracle).
 
     python tests/stage_fuzz.py [rounds] [seed] [--stage NAME] [--round K]     (on an MI355X; 200 rounds is the long run)
 
@@ -40,6 +40,20 @@ What a stage draws (sizes are the smallest at which each kernel can still go wro
              rows to subtract in [-70000, 70000]; the table is the NTSC one, on the host from the oracle
     chain    2..3 frames of a random source size through resize -> ingest -> render_rgb -> render_error (against the resized
              frames), each stage handed the very tensor the one before returned; every arrow against the models' composition
+    yuv      n 1..5 frames of 4:2:0 planes, h, w, H, W as resize draws them; every 8 rounds: same size, each one-pass form,
+             h > 100 w with W == w and with W != w (the unfused path, the vertical pass first), w > 4096 with a small h (one
+             row per workgroup); one of tests/test_gpu_yuv.py's eight plane layouts with a random fill byte around the planes;
+             a preset matrix, a random one inside the argument bounds or one at them; noise, planes of 0 and 255, or a
+             one-sample chroma checkerboard: resize_model.resize(yuv_model.to_rgb(...))
+    direct   mode, a source width of 280 or 560, a palette of ingest_model.NAMES, an ordered amplitude, n frames over a pool
+             of at most three (a frame's bytes depend on that frame alone): ingest_model.frame_set, noise, a flat frame, or a
+             frame of flat rows half-way between two palette colours, where many byte rows tie; a view at a frame offset into
+             a larger batch; d_rgb 4 bytes, the maps and d_cost 8 bytes off their buffers' alignment, in guarded buffers, through
+             the C ABI; d_cost NULL or given: bytes and costs against direct_model, and with dither 0 the cost against
+             render_error_model's level 0 of the model's maps
+    chain_yuv  2..3 frames of random 4:2:0 planes through resize_frames_yuv420 -> frames_to_memory_maps_direct -> render_rgb ->
+             render_error (against the resized frames), each handed the very tensor the one before returned; every arrow
+             against the models' composition
 
 check_ticks lets ticks differ within 1e-3 of a level boundary if fewer than 0.5 % of a stream's samples do.  That cap is a
 condition on the case: draw_audio draws again (from the same generator, so still a function of the seed) while a stream of
@@ -64,17 +78,20 @@ import audio_model  # noqa: E402
 import bitmap_model  # noqa: E402
 import device_guards  # noqa: E402
 import diffusion_model  # noqa: E402
+import direct_model  # noqa: E402
 import ingest_model  # noqa: E402
 import mono_model  # noqa: E402
 import render_error_model  # noqa: E402
 import render_model  # noqa: E402
 import resize_model  # noqa: E402
+import yuv_model  # noqa: E402
 
 SEED = 2027
-STAGES = ("resize", "ingest", "mono", "render", "a2m", "audio", "chain", "bitmap")
+STAGES = ("resize", "ingest", "mono", "render", "a2m", "audio", "chain", "bitmap", "yuv", "direct", "chain_yuv")   # (appended to: the index seeds the stage)
 STAGE_ID = {name: i for i, name in enumerate(STAGES)}
 # rounds of tests/test_gpu_stage_fuzz.py (the chain, four stages a round, runs 4)
-ROUNDS = {"resize": 12, "ingest": 12, "mono": 12, "render": 12, "a2m": 12, "audio": 12, "chain": 4, "bitmap": 12}
+ROUNDS = {"resize": 12, "ingest": 12, "mono": 12, "render": 12, "a2m": 12, "audio": 12, "chain": 4, "bitmap": 12, "yuv": 12, "direct": 12,
+          "chain_yuv": 4}
 
 HGR, DHGR = 0, 1
 DIFFUSION = 256
@@ -251,11 +268,11 @@ def _draw_dither(rng, family):
     return "kernel:%s/%d" % (",".join(str(v) for v in w), d), w, d
 
 
-def _draw_pool(rng, n, most=3):
+def _draw_pool(rng, n, most=3, kinds=7):
     """the different frames of a batch, as (kind 0..5 of ingest_model.frame_set | 6 = more noise, seed), and which one each of
     the n frames is (every one of the pool occurs)"""
     k = min(n, int(rng.integers(1, most + 1)))
-    pool = [(int(rng.integers(0, 7)), int(rng.integers(1 << 30))) for _ in range(k)]
+    pool = [(int(rng.integers(0, kinds)), int(rng.integers(1 << 30))) for _ in range(k)]
     idx = rng.integers(0, k, n)
     idx[rng.permutation(n)[:k]] = np.arange(k)
     return pool, idx
@@ -764,12 +781,202 @@ def check_bitmap(native, case):
     _same(case, "the rows after the call", rows.cpu().numpy(), case["rows"])
 
 
+# ---- 4:2:0 planes into the resize ------------------------------------------------------------------------------------------
+
+YUV_LAYOUTS = ("i420", "nv12", "nv21", "rows", "nv12_rows", "frames", "cut", "nv12_cut")      # tests/test_gpu_yuv.py: LAYOUTS
+YUV_PRESETS = ("bt601", "bt709", "jpeg")
+YUV_FORCED = ("free", "horizontal only", "vertical only", "same size", "tall", "tall and the width changes", "wide", "two passes")
+
+
+def _yuv_planes(kind, n, h, w, rng):
+    """(y, u, v): noise, planes of 0 and 255, or noise under a one-sample chroma checkerboard of 0 and 255"""
+    ch, cw = (h + 1) // 2, (w + 1) // 2
+    if kind == "noise":
+        return tuple(rng.integers(0, 256, s, dtype=np.uint8) for s in ((n, h, w), (n, ch, cw), (n, ch, cw)))
+    if kind == "extremes":
+        return tuple((rng.integers(0, 2, s) * 255).astype(np.uint8) for s in ((n, h, w), (n, ch, cw), (n, ch, cw)))
+    f, y, x = np.ogrid[0:n, 0:ch, 0:cw]
+    u = (((x + y + f) & 1) * 255).astype(np.uint8)
+    return rng.integers(0, 256, (n, h, w), dtype=np.uint8), u, (255 - u).astype(np.uint8)
+
+
+def _draw_yuv_matrix(rng):
+    kind = ("preset", "inside", "bounds")[int(rng.integers(0, 3))]
+    if kind == "preset":
+        return YUV_PRESETS[int(rng.integers(0, 3))]
+    if kind == "inside":
+        return (int(rng.integers(0, 256)),) + tuple(int(k) for k in rng.integers(-1023, 1024, 5))
+    return (int(rng.choice((0, 255))),) + tuple(int(k) for k in rng.choice((-1023, 1023), 5))
+
+
+def draw_yuv(rng, round_index=0):
+    n = int(rng.integers(1, 6))
+    h, w = _size(rng), _size(rng)
+    H, W = (192, 280) if rng.random() < 0.5 else (_size(rng), _size(rng))
+    forced = YUV_FORCED[round_index % 8]
+    if forced in ("tall", "tall and the width changes"):       # h > 100 w: the conversion alone, then the RGB path
+        w = int(rng.integers(1, 4))
+        h = int(rng.integers(100 * w + 1, 401))
+    if forced == "wide":                                        # w_pad > 4096: one row per workgroup
+        w, h = int(rng.integers(4097, 4200)), int(rng.integers(1, 5))
+        H = h if rng.random() < 0.5 else int(rng.integers(1, 9))
+    while forced in ("horizontal only", "tall and the width changes", "wide", "two passes") and W == w:
+        W = _size(rng)
+    while forced in ("vertical only", "tall", "tall and the width changes", "two passes") and H == h:
+        H = _size(rng)
+    if forced in ("horizontal only", "same size"):
+        H = h
+    if forced in ("vertical only", "same size", "tall"):
+        W = w
+    kind = ("noise", "extremes", "checker")[int(rng.integers(0, 3))]
+    planes = _yuv_planes(kind, n, h, w, rng)
+    params = dict(n=n, h=h, w=w, H=H, W=W, content=kind, layout=YUV_LAYOUTS[int(rng.integers(0, len(YUV_LAYOUTS)))],
+                  fill=int(rng.integers(0, 256)), matrix=_draw_yuv_matrix(rng))
+    return dict(stage="yuv", params=params, forced=forced, planes=planes)
+
+
+def _yuv_views(p, planes):
+    """the planes on the device in the case's layout (the layouts are tests/test_gpu_yuv.py's own)"""
+    import test_gpu_yuv
+    return test_gpu_yuv._layout(p["layout"], *planes, fill=p["fill"])
+
+
+def check_yuv(native, case):
+    p = case["params"]
+    y, u, v = case["planes"]
+    got = native.resize_frames_yuv420(*_yuv_views(p, (y, u, v)), (p["H"], p["W"]), matrix=p["matrix"])
+    _sync()
+    _same(case, "resize_frames_yuv420", got.cpu().numpy(), resize_model.resize(yuv_model.to_rgb(y, u, v, p["matrix"]), (p["H"], p["W"])))
+
+
+# ---- direct ingest ----------------------------------------------------------------------------------------------------
+
+DIRECT_WIDTHS = (280, 560)
+DIRECT_KINDS = 9          # 0..5 of ingest_model.frame_set, 6 noise, 7 a flat frame, 8 flat rows between two palette colours
+DIRECT_FORCED = (6, 7, 8, None)
+
+
+def direct_pool_frames(pool, palette_name, width):
+    pal = _palette(palette_name)
+    out = np.empty((len(pool), 192, width, 3), np.uint8)
+    for i, (kind, seed) in enumerate(pool):
+        rng = np.random.default_rng([seed, kind])
+        if kind < 6:
+            out[i] = np.repeat(ingest_model.frame_set(pal, seed)[kind], width // 280, axis=1)
+        elif kind == 6:
+            out[i] = rng.integers(0, 256, (192, width, 3))
+        elif kind == 7:
+            out[i] = rng.integers(0, 256, 3)
+        else:       # every row flat and half-way between two palette colours: both colours' rows cost the same where the sum is even
+            a, b = np.asarray(pal, np.int64)[rng.integers(0, 16, (2, 192))]
+            out[i] = ((a + b) // 2)[:, None, :]
+    return out
+
+
+def draw_direct(rng, round_index=0):
+    mode = int(rng.integers(0, 2))
+    width = DIRECT_WIDTHS[int(rng.integers(0, 2))]
+    pal = ingest_model.NAMES[int(rng.integers(0, len(ingest_model.NAMES)))]
+    dither = int(rng.choice(AMPLITUDES))
+    cost = bool(rng.integers(0, 2))
+    if round_index % 3 == 0:                              # the cost against the screen error: only without dither
+        dither, cost = 0, True
+    n = _count(rng)
+    pool, idx = _draw_pool(rng, n, kinds=DIRECT_KINDS)
+    forced = DIRECT_FORCED[round_index % 4]
+    if forced is not None:
+        pool[0] = (forced, pool[0][1])
+    params = dict(mode=mode, width=width, palette=pal, n=n, dither=dither, cost=cost, frame_offset=int(rng.integers(0, 4)),
+                  tail=int(rng.integers(0, 3)), lead_rgb=_lead(rng, 4), lead_main=_lead(rng, 8), lead_aux=_lead(rng, 8),
+                  lead_cost=_lead(rng, 8), pool=pool, junk=int(rng.integers(1 << 30)))
+    return dict(stage="direct", params=params, idx=idx)
+
+
+def check_direct(native, case):
+    import torch
+    p = case["params"]
+    mode, n, width, pal = p["mode"], p["n"], p["width"], np.ascontiguousarray(_palette(p["palette"]), dtype=np.uint8).reshape(16, 3)
+    frame_bytes = 192 * width * 3
+    pool = direct_pool_frames(p["pool"], p["palette"], width)
+    frames = pool[case["idx"]]
+    total = p["frame_offset"] + n + p["tail"]
+    big = np.random.default_rng(p["junk"]).integers(0, 256, (total, 192, width, 3), dtype=np.uint8)   # the batch the frames lie in
+    big[p["frame_offset"]:p["frame_offset"] + n] = frames
+    sbuf, sview = _guarded(total * frame_bytes, p["lead_rgb"], 16)
+    sview.copy_(torch.from_numpy(big.reshape(-1)))
+    src = sview[p["frame_offset"] * frame_bytes:(p["frame_offset"] + n) * frame_bytes]
+    bufs = [_guarded(n * 8192, p["lead_main"], 40), _guarded(n * 8192, p["lead_aux"], 40)]
+    cbuf, cview = _guarded(n * 8, p["lead_cost"], 24)
+    _require(src.data_ptr() % 4 == 0 and all(b[1].data_ptr() % 8 == 0 for b in bufs) and cview.data_ptr() % 8 == 0, case,
+             "the buffers are not at the contract's alignments")
+    hp = pal.reshape(48)
+    native.check(native.lib().iiv_frames_to_memory_maps_direct(mode, native.hptr(hp), n, native.dptr(src), width, p["dither"],
+                                                               native.dptr(bufs[0][1]), native.dptr(bufs[1][1]),
+                                                               native.dptr(cview) if p["cost"] else None, native.stream_ptr()))
+    _sync()
+    m, a, c = direct_model.frames_to_memory_maps_direct(mode, pal, pool, p["dither"])
+    idx = case["idx"]
+    _check_maps(case, "direct ingest", mode, n, bufs, (p["lead_main"], p["lead_aux"]), (m[idx], a[idx] if a is not None else None))
+    if p["cost"]:
+        _same(case, "direct ingest: d_cost", cview.cpu().numpy().view(np.uint64), c[idx])
+        _guards_kept(case, "direct ingest: d_cost", cbuf, p["lead_cost"], n * 8)
+        if p["dither"] == 0:
+            level0 = render_error_model.render_error(mode, m, a, pal, pool)[:, 0, :].sum(axis=1)
+            _same(case, "the model's cost against render_error_model's level 0", c, level0)
+    else:
+        _require(bool((cbuf.cpu().numpy() == GUARD).all()), case, "direct ingest: d_cost is NULL and the buffer was written")
+    _guards_kept(case, "direct ingest: the source", sbuf, p["lead_rgb"], total * frame_bytes)
+    _same(case, "the source after the call", sview.cpu().numpy(), big.reshape(-1))
+
+
+# ---- the chain from 4:2:0 planes --------------------------------------------------------------------------------------------
+
+def draw_chain_yuv(rng, round_index=0):
+    mode = int(rng.integers(0, 2))
+    pal = ingest_model.NAMES[int(rng.integers(0, len(ingest_model.NAMES)))]
+    n = int(rng.integers(2, 4))
+    h, w = _size(rng), _size(rng)
+    kind = ("noise", "extremes", "checker")[int(rng.integers(0, 3))]
+    planes = _yuv_planes(kind, n, h, w, rng)
+    dither = int(rng.choice(AMPLITUDES))
+    # both source widths of the direct ingest, and dither 0 (where its cost is the screen error) with each, every four rounds
+    params = dict(mode=mode, palette=pal, n=n, h=h, w=w, width=DIRECT_WIDTHS[round_index % 2], content=kind,
+                  layout=YUV_LAYOUTS[int(rng.integers(0, len(YUV_LAYOUTS)))], fill=int(rng.integers(0, 256)),
+                  matrix=YUV_PRESETS[int(rng.integers(0, 3))], dither=0 if round_index % 4 < 2 else dither)
+    return dict(stage="chain_yuv", params=params, planes=planes)
+
+
+def check_chain_yuv(native, case):
+    p = case["params"]
+    mode, n, pal, size = p["mode"], p["n"], _palette(p["palette"]), (192, p["width"])
+    small = native.resize_frames_yuv420(*_yuv_views(p, case["planes"]), size, matrix=p["matrix"])
+    main, aux, cost = native.frames_to_memory_maps_direct(mode, pal, small, p["dither"], cost=True)   # each stage takes the last one's tensor
+    rgb = native.render_rgb(mode, pal, main, aux)
+    sums = native.render_error(mode, pal, main, aux, small)
+    _sync()
+    m_small = resize_model.resize(yuv_model.to_rgb(*case["planes"], p["matrix"]), size)
+    _same(case, "chain_yuv: resize", small.cpu().numpy(), m_small)
+    m_main, m_aux, m_cost = direct_model.frames_to_memory_maps_direct(mode, pal, m_small, p["dither"])
+    _same(case, "chain_yuv: direct ingest main", main.cpu().numpy(), m_main)
+    _require((aux is None) == (m_aux is None), case, "chain_yuv: direct ingest aux")
+    if aux is not None:
+        _same(case, "chain_yuv: direct ingest aux", aux.cpu().numpy(), m_aux)
+    _same(case, "chain_yuv: direct ingest cost", cost.cpu().numpy().view(np.uint64), m_cost)
+    m_rgb = render_model.render_rgb(mode, m_main, m_aux, pal)
+    _same(case, "chain_yuv: render_rgb", rgb.cpu().numpy(), m_rgb)
+    m_sums = render_error_model.error_sums_of_screens(m_rgb, m_small)
+    _same(case, "chain_yuv: render_error", sums.cpu().numpy().view(np.uint64).reshape(n, 3, 3), m_sums)
+    if p["dither"] == 0:
+        _same(case, "chain_yuv: the cost against render_error's level 0", m_cost, m_sums[:, 0, :].sum(axis=1))
+
+
 # ---- the loop ---------------------------------------------------------------------------------------------------------
 
 DRAW = {"resize": draw_resize, "ingest": draw_ingest, "mono": draw_mono, "render": draw_render, "a2m": draw_a2m, "audio": draw_audio,
-        "chain": draw_chain, "bitmap": draw_bitmap}
+        "chain": draw_chain, "bitmap": draw_bitmap, "yuv": draw_yuv, "direct": draw_direct, "chain_yuv": draw_chain_yuv}
 CHECK = {"resize": check_resize, "ingest": check_ingest, "mono": check_mono, "render": check_render, "a2m": check_a2m,
-         "audio": check_audio, "chain": check_chain, "bitmap": check_bitmap}
+         "audio": check_audio, "chain": check_chain, "bitmap": check_bitmap, "yuv": check_yuv, "direct": check_direct,
+         "chain_yuv": check_chain_yuv}
 
 
 def _fuzz(stage, native, rng, round_index, seed=None):
@@ -811,8 +1018,20 @@ def fuzz_bitmap(native, rng, round_index, seed=None):
     return _fuzz("bitmap", native, rng, round_index, seed)
 
 
+def fuzz_yuv(native, rng, round_index, seed=None):
+    return _fuzz("yuv", native, rng, round_index, seed)
+
+
+def fuzz_direct(native, rng, round_index, seed=None):
+    return _fuzz("direct", native, rng, round_index, seed)
+
+
+def fuzz_chain_yuv(native, rng, round_index, seed=None):
+    return _fuzz("chain_yuv", native, rng, round_index, seed)
+
+
 FUZZ = {"resize": fuzz_resize, "ingest": fuzz_ingest, "mono": fuzz_mono, "render": fuzz_render, "a2m": fuzz_a2m, "audio": fuzz_audio,
-        "chain": fuzz_chain, "bitmap": fuzz_bitmap}
+        "chain": fuzz_chain, "bitmap": fuzz_bitmap, "yuv": fuzz_yuv, "direct": fuzz_direct, "chain_yuv": fuzz_chain_yuv}
 
 
 def run(rounds, seed=SEED, stages=None, side_stream=False, first_round=0, log=None):

@@ -22,7 +22,8 @@ SHAPES = [(7, 9, 5, 6, 3), (8, 33, 3, 7, 3),
           (1, 1, 1, 1, 3),
           (2, 4098, 2, 8, 1),           # w > 4096: one row per workgroup
           (48, 64, 192, 280, 3), (48, 64, 192, 560, 3),   # the real targets
-          (202, 2, 4, 2, 3)]            # h > 100 w
+          (202, 2, 4, 2, 3),            # h > 100 w
+          (202, 2, 4, 3, 3)]            # h > 100 w and the width changes too: the vertical pass first, unfused
 BOUNDS_MATRIX = (255, 1023, -1023, 1023, -1023, 1023)
 _cache = {}
 
@@ -111,7 +112,8 @@ def _layout(name, y, u, v, fill=0xFF):
 LAYOUTS = ["i420", "nv12", "nv21", "rows", "nv12_rows", "frames", "cut", "nv12_cut"]
 
 
-@pytest.mark.parametrize("h,w,H,W", [(7, 9, 5, 6), (9, 35, 4, 35), (8, 33, 8, 7)])   # fused two passes, unfused, fused one pass
+# fused two passes, unfused, fused one pass, unfused with the vertical pass first
+@pytest.mark.parametrize("h,w,H,W", [(7, 9, 5, 6), (9, 35, 4, 35), (8, 33, 8, 7), (202, 2, 4, 3)])
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_layouts(native, layout, h, w, H, W):
     y, u, v = _planes(h, w, 3)

@@ -2,6 +2,11 @@
 a refusal by accident, proves nothing.  For the committed seed and round counts: every category the stages force occurs, every
 drawn case lies inside its entry point's documented preconditions (include/iivision.h), and no audio stream sits on the level
 boundaries often enough for check_ticks' 0.5 % allowance to matter."""
+import hashlib
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -12,6 +17,7 @@ import diffusion_model
 import ingest_model
 import resize_model
 import stage_fuzz as F
+import yuv_model
 
 
 def _cases(stage, rounds=None):
@@ -24,7 +30,38 @@ def cases():
 
 
 def test_round_counts():
-    assert F.ROUNDS == {"resize": 12, "ingest": 12, "mono": 12, "render": 12, "a2m": 12, "audio": 12, "chain": 4, "bitmap": 12}
+    assert F.ROUNDS == {"resize": 12, "ingest": 12, "mono": 12, "render": 12, "a2m": 12, "audio": 12, "chain": 4, "bitmap": 12, "yuv": 12,
+                        "direct": 12, "chain_yuv": 4}
+    assert set(F.ROUNDS) == set(F.STAGES) == set(F.DRAW) == set(F.CHECK) == set(F.FUZZ)
+
+
+# round 0 of every stage that existed before yuv, direct and chain_yuv were appended, as the commit before them drew it: the
+# description and every array of the case, sha256.  A stage's generator is seeded by its index in STAGES, so a stage put in
+# front of these, or a draw added to a helper they share, would change every committed case without a test noticing.
+OLD_ROUND_0 = {
+    "resize": "95c8f9cd0b2c86c4",
+    "ingest": "6f820248f98c1a4b",
+    "mono": "d6bbb82721132994",
+    "render": "6abc0449870117a8",
+    "a2m": "8dcec69b530656d6",
+    "audio": "be48debc581a363e",
+    "chain": "1ab8fb20a47e11f3",
+    "bitmap": "d9ad8c802bccc95d",
+}
+
+
+def _digest(case):
+    h = hashlib.sha256(F.describe(case).encode())
+    for k in sorted(case):
+        if isinstance(case[k], np.ndarray):
+            h.update(k.encode())
+            h.update(np.ascontiguousarray(case[k]).tobytes())
+    return h.hexdigest()[:16]
+
+
+def test_the_old_stages_draw_what_they_drew(cases):
+    assert F.STAGES[:8] == tuple(OLD_ROUND_0) and [F.STAGE_ID[s] for s in OLD_ROUND_0] == list(range(8))
+    assert {s: _digest(cases[s][0]) for s in OLD_ROUND_0} == OLD_ROUND_0
 
 
 def test_a_case_is_a_function_of_seed_round_and_stage(cases):
@@ -255,3 +292,119 @@ def test_bitmap_draws(cases):
     first = [c["params"] for c in cases["bitmap"][:4]]
     assert [(q["mode"], q["is_aux"]) for q in first] == [(0, 0), (1, 0), (0, 0), (1, 1)] and first[0]["n"] == 1 and first[1]["n"] > 1
     assert bitmap_model.HGR == F.HGR and bitmap_model.DHGR == F.DHGR
+
+
+def test_yuv_draws(cases):
+    import test_gpu_yuv
+    assert F.YUV_LAYOUTS == tuple(test_gpu_yuv.LAYOUTS) and set(F.YUV_PRESETS) == set(yuv_model.MATRICES)
+    seen = set()
+    for r, c in enumerate(cases["yuv"]):
+        p = c["params"]
+        n, h, w, H, W = (p[k] for k in ("n", "h", "w", "H", "W"))
+        assert 1 <= n <= 5 and 1 <= h <= 8192 and 1 <= w <= 8192 and 1 <= H <= 1024 and 1 <= W <= 1024      # iiv_resize_frames_yuv420
+        y, u, v = c["planes"]
+        assert y.shape == (n, h, w) and u.shape == v.shape == (n, (h + 1) // 2, (w + 1) // 2) and {y.dtype, u.dtype, v.dtype} == {np.dtype(np.uint8)}
+        assert p["layout"] in F.YUV_LAYOUTS and 0 <= p["fill"] <= 255 and c["forced"] == F.YUV_FORCED[r % 8]
+        m = p["matrix"]
+        if isinstance(m, str):
+            assert m in yuv_model.MATRICES
+            seen.add("preset")
+        else:
+            assert len(m) == 6 and 0 <= m[0] <= 255 and all(-1023 <= k <= 1023 for k in m[1:])            # the header's bounds
+            seen.add("at the bounds" if m[0] in (0, 255) and all(abs(k) == 1023 for k in m[1:]) else "inside the bounds")
+        tall, unfused = h > 100 * w, W == w or (H != h and h > 100 * w)
+        # the path the host code takes, and the forced category really is that path
+        kind = ("same size" if (H, W) == (h, w) else "vertical only" if W == w else "horizontal only" if H == h else
+                "vertical first" if tall else "two passes")
+        seen |= {kind, p["content"], p["layout"], "unfused" if unfused else "fused"}
+        if tall:
+            seen.add("tall, W == w" if W == w else "tall, W != w")
+        if (w + 3) & ~3 > 4096:
+            assert h <= 4
+            seen.add("one row per workgroup")
+        want = {"horizontal only": "horizontal only", "vertical only": "vertical only", "same size": "same size", "tall": "vertical only",
+                "tall and the width changes": "vertical first", "two passes": ("two passes", "vertical first")}.get(c["forced"])
+        assert want is None or kind == want or kind in want, (c["forced"], kind)
+        assert c["forced"] not in ("tall", "tall and the width changes") or tall
+        assert c["forced"] != "wide" or ((w + 3) & ~3 > 4096 and W != w)
+        if p["content"] == "extremes":
+            assert set(np.unique(y)) <= {0, 255} and set(np.unique(u)) <= {0, 255}
+        if p["content"] == "checker" and u.shape[2] > 1:
+            assert (u[:, :, 1:] != u[:, :, :-1]).all() and (u.astype(int) + v == 255).all()
+    assert seen >= {"preset", "at the bounds", "inside the bounds", "same size", "vertical only", "horizontal only", "vertical first", "two passes",
+                    "tall, W == w", "tall, W != w", "one row per workgroup", "noise", "extremes", "checker", "fused", "unfused"}, seen
+    assert len(seen & set(F.YUV_LAYOUTS)) >= 4 and seen & {"nv12", "nv21", "nv12_rows", "nv12_cut"} and seen & {"i420", "rows", "frames", "cut"}, seen
+    assert sum(c["forced"] == "wide" for c in cases["yuv"]) == 1
+
+
+def test_direct_draws(cases):
+    seen = set()
+    for c in cases["direct"]:
+        p = c["params"]
+        assert p["mode"] in (0, 1) and p["width"] in (280, 560) and p["palette"] in ingest_model.NAMES and 1 <= p["n"] <= 70
+        assert p["dither"] in F.AMPLITUDES and 0 <= p["dither"] <= 255                                        # no diffusion: refused
+        # include/iivision.h f10: d_rgb 4-byte aligned, the maps and d_cost 8-byte aligned -- and here no more than that, sometimes
+        assert p["lead_rgb"] % 4 == 0 and p["lead_main"] % 8 == 0 and p["lead_aux"] % 8 == 0 and p["lead_cost"] % 8 == 0
+        assert min(p["lead_rgb"], p["lead_main"], p["lead_aux"], p["lead_cost"]) >= 4 and (p["frame_offset"] * 192 * p["width"] * 3) % 4 == 0
+        assert len(c["idx"]) == p["n"] and set(c["idx"].tolist()) == set(range(len(p["pool"]))) and len(p["pool"]) <= 3
+        assert all(0 <= k < F.DIRECT_KINDS for k, _ in p["pool"])
+        seen |= {("mode", p["mode"]), p["width"], ("cost", p["cost"]), "dither 0" if p["dither"] == 0 else "dithered"}
+        seen |= {("kind", max(k, 5)) for k, _ in p["pool"]}                  # (5: any of ingest_model.frame_set's)
+        if p["dither"] == 0 and p["cost"]:
+            seen.add("cost against the screen error")
+        if p["lead_rgb"] % 8 == 4:
+            seen.add("source at 4 and no more")
+        if p["lead_main"] % 16 == 8 or p["lead_aux"] % 16 == 8:
+            seen.add("maps at 8 and no more")
+        if p["cost"] and p["lead_cost"] % 16 == 8:
+            seen.add("cost at 8 and no more")
+        if p["frame_offset"]:
+            seen.add("a frame offset")
+    assert seen >= {("mode", 0), ("mode", 1), 280, 560, ("cost", True), ("cost", False), "dither 0", "dithered", ("kind", 5), ("kind", 6),
+                    ("kind", 7), ("kind", 8), "cost against the screen error", "source at 4 and no more", "maps at 8 and no more",
+                    "cost at 8 and no more", "a frame offset"}, seen
+    # the pool's frames: the right shape at both widths, all different, a flat frame flat, and rows that do tie in the tie frame
+    import direct_model
+    for width in (280, 560):
+        frames = F.direct_pool_frames([(k, 11) for k in range(F.DIRECT_KINDS)], "ntsc", width)
+        assert frames.shape == (F.DIRECT_KINDS, 192, width, 3) and len({f.tobytes() for f in frames}) == F.DIRECT_KINDS
+        assert (frames[7] == frames[7][0, 0]).all() and (frames[8] == frames[8][:, :1]).all() and len(np.unique(frames[8][:, 0], axis=0)) > 16
+    pal = F._palette("pairs")
+    tie = F.direct_pool_frames([(8, 5)], "pairs", 280)[0]
+    C = direct_model.window_costs(pal, direct_model.target(tie[None], 0)[0, :, :1])            # (192, 1, 16): the first dot of every row
+    assert ((C == C.min(axis=-1, keepdims=True)).sum(axis=-1) > 1).mean() > 0.5                # most rows: several windows of least cost
+
+
+def test_chain_yuv_draws(cases):
+    seen = set()
+    for c in cases["chain_yuv"]:
+        p = c["params"]
+        y, u, v = c["planes"]
+        assert p["n"] in (2, 3) and y.shape == (p["n"], p["h"], p["w"]) and 1 <= p["h"] <= 400 and 1 <= p["w"] <= 400
+        assert u.shape == v.shape == (p["n"], (p["h"] + 1) // 2, (p["w"] + 1) // 2)
+        assert p["palette"] in ingest_model.NAMES and p["matrix"] in yuv_model.MATRICES and p["layout"] in F.YUV_LAYOUTS
+        assert p["width"] in (280, 560) and 0 <= p["dither"] <= 255
+        seen |= {p["width"], (p["width"], p["dither"] == 0)}
+    assert seen >= {280, 560, (280, True), (560, True)}, seen
+
+
+@pytest.mark.parametrize("stage", ["yuv", "direct", "chain_yuv"])
+def test_the_new_stages_reproduce_one_case_from_the_command_line(stage, monkeypatch):
+    """python tests/stage_fuzz.py 1 SEED --stage STAGE --round R and IIV_STAGE_FUZZ_SIDE_STREAM=1 reach the new stages as the old
+    ones: main() hands run() that one stage, that one round and the side-stream switch (run() itself needs a device)."""
+    calls = []
+    monkeypatch.setattr(F, "run", lambda rounds, seed, stages, side, first, log=None: calls.append((rounds, seed, stages, side, first)) or [])
+    monkeypatch.setenv("IIV_STAGE_FUZZ_SIDE_STREAM", "1")
+    F.main(["1", str(F.SEED), "--stage", stage, "--round", "3"])
+    monkeypatch.delenv("IIV_STAGE_FUZZ_SIDE_STREAM")
+    F.main(["1", str(F.SEED), "--stage", stage, "--round", "3"])
+    assert calls == [(1, F.SEED, [stage], True, 3), (1, F.SEED, [stage], False, 3)]
+    case = F.DRAW[stage](F.stage_rng(F.SEED, 3, stage), 3)
+    case["seed"], case["round"] = F.SEED, 3
+    with pytest.raises(AssertionError, match=r"python tests/stage_fuzz.py 1 %d --stage %s --round 3" % (F.SEED, stage)):
+        F._same(case, "a comparison", np.zeros(2), np.ones(2))
+    assert F.describe(case) == F.describe(F.DRAW[stage](F.stage_rng(F.SEED, 3, stage), 3))
+    # the stand-alone program knows the stage (its own argument parser, in a process of its own, no device touched)
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(F.__file__)), "stage_fuzz.py"), "--help"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and stage in r.stdout
