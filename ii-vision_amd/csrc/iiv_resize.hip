@@ -9,21 +9,24 @@
 //   * the horizontal pass first (vertical first when h > 100 w), the first pass's uint8 result feeding the second; an axis
 //     whose size does not change gets no pass.
 //
-// Form: two kernels, the first pass's uint8 result in a stream-ordered HBM scratch of frames_per_chunk frames, sized so a
+// Form: two kernels, the first pass's uint8 result in a stream-ordered HBM scratch of frames_per_piece frames, sized so a
 // chunk's intermediate (at most W / w of its source) stays in the Infinity Cache between the two launches.  Source
 // bytes cross HBM once.
-//   * resize_h_kernel: a workgroup per R source rows, one thread per output column.  The rows are read with aligned
-//     dword loads and a funnel shift (any byte stride), unpacked to one dword per pixel in LDS; each tap is then one
-//     coalesced coefficient load (the table is stored tap-major), R LDS reads and 3 R 24-bit multiply-adds.
+//   * resize_h_kernel<R, Rows>: a workgroup per R source rows, one thread per output column.  A row source unpacks the rows
+//     to one dword per pixel in LDS; each tap is then one coalesced coefficient load (the table is stored tap-major), R LDS
+//     reads and 3 R 24-bit multiply-adds.  Two row sources: RgbRows (packed RGB, aligned dword loads and a funnel shift, any
+//     byte stride) and YuvRows (4:2:0 planes, iiv_resize_frames_yuv420: converted as they are unpacked).
 //   * resize_v_kernel: a workgroup per output row, one thread per four bytes of the row (the vertical pass does not care
 //     which byte is which channel); the row's coefficients are wave-uniform (scalar loads).
-// Coefficient tables are made once per (device, in, out) and kept for the life of the process.
+// One driver, resize_rows<Rows>, serves both entry points: tables, pass order, slices and chunks, scratch.  Coefficient tables
+// are made once per (device, in, out) and kept for the life of the process.
 #include "iiv_host.h"
 
 #include <math.h>
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 namespace iiv {
@@ -140,11 +143,51 @@ __device__ inline uint32_t load_unaligned(const uint8_t *p, const uint8_t *end)
     return __builtin_amdgcn_alignbyte(d1, d0, s);
 }
 
-// Horizontal pass: src rows (rows per frame, w pixels, byte strides) -> dst rows of W pixels (byte strides).  Workgroup =
-// R consecutive rows of one frame; threads = W rounded up to waves, one output pixel each.  LDS: R rows of w_pad dwords.
-template <int R>
-__global__ __launch_bounds__(1024) void resize_h_kernel(const uint8_t *__restrict__ src, size_t src_fs, size_t src_rs, int rows,
-                                                        int w, int W, const int2 *__restrict__ bounds,
+// A row source hands the horizontal pass its pixels.  fill<R>() -- every thread of the workgroup, before its barrier -- unpacks
+// rows r0 .. r0 + R - 1 of frame f into px [R][w_pad], a dword r | g << 8 | b << 16 per pixel; from_frame(f0), on the host, is the
+// same source f0 frames on; label names the launch in an error.  Two of them: RgbRows here, YuvRows below.
+
+struct RgbRows {   // packed RGB: rows of 3 w bytes at byte strides, any alignment
+    const uint8_t *__restrict__ src;
+    size_t fs, rs;
+    static constexpr const char *label = "resize_h_kernel<RgbRows> launch";
+    RgbRows from_frame(int f0) const { return {src + (size_t)f0 * fs, fs, rs}; }
+
+    template <int R>
+    __device__ inline void fill(uint32_t *px, unsigned nt, int f, int r0, int rows, int w, int w_pad) const
+    {
+        const int n4 = w_pad >> 2;
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            if (r0 + r >= rows) break;
+            const uint8_t *row = src + (size_t)f * fs + (size_t)(r0 + r) * rs;
+            const uint8_t *end = row + 3 * (size_t)w;
+            for (int g = threadIdx.x; g < n4; g += nt) {
+                // four pixels = twelve bytes from byte 12 g of the row, in aligned dwords: each one that is read starts inside
+                // the row, and an aligned dword never crosses a page, so none can fault
+                const uint8_t *p = row + 12 * (size_t)g;
+                const uintptr_t a = (uintptr_t)p & ~(uintptr_t)3;
+                const uint32_t s = (uint32_t)((uintptr_t)p & 3);
+                uint32_t d[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) d[j] = (const uint8_t *)(a + 4 * j) < end ? ((const uint32_t *)a)[j] : 0u;
+                const uint32_t e0 = __builtin_amdgcn_alignbyte(d[1], d[0], s), e1 = __builtin_amdgcn_alignbyte(d[2], d[1], s),
+                               e2 = __builtin_amdgcn_alignbyte(d[3], d[2], s);
+                uint4 q;
+                q.x = e0 & 0xffffffu;
+                q.y = (e0 >> 24) | ((e1 & 0xffffu) << 8);
+                q.z = (e1 >> 16) | ((e2 & 0xffu) << 16);
+                q.w = e2 >> 8;
+                *(uint4 *)&px[r * w_pad + 4 * g] = q;
+            }
+        }
+    }
+};
+
+// Horizontal pass: the rows of `src` (rows per frame, w pixels) -> dst rows of W pixels (byte strides).  Workgroup = R
+// consecutive rows of one frame; threads = W rounded up to waves, one output pixel each.  LDS: R rows of w_pad dwords.
+template <int R, class Rows>
+__global__ __launch_bounds__(1024) void resize_h_kernel(Rows src, int rows, int w, int W, const int2 *__restrict__ bounds,
                                                         const int32_t *__restrict__ k_taps, uint8_t *__restrict__ dst,
                                                         size_t dst_fs, size_t dst_rs)
 {
@@ -152,30 +195,7 @@ __global__ __launch_bounds__(1024) void resize_h_kernel(const uint8_t *__restric
     const int groups = (rows + R - 1) / R;
     const int f = blockIdx.x / groups, r0 = (blockIdx.x % groups) * R;
     const int w_pad = (w + 3) & ~3;
-    const int n4 = w_pad >> 2;
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        if (r0 + r >= rows) break;
-        const uint8_t *row = src + (size_t)f * src_fs + (size_t)(r0 + r) * src_rs;
-        const uint8_t *end = row + 3 * (size_t)w;
-        for (int g = threadIdx.x; g < n4; g += blockDim.x) {
-            // four pixels = twelve bytes from byte 12 g of the row
-            const uint8_t *p = row + 12 * (size_t)g;
-            const uintptr_t a = (uintptr_t)p & ~(uintptr_t)3;
-            const uint32_t s = (uint32_t)((uintptr_t)p & 3);
-            uint32_t d[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) d[j] = (const uint8_t *)(a + 4 * j) < end ? ((const uint32_t *)a)[j] : 0u;
-            const uint32_t e0 = __builtin_amdgcn_alignbyte(d[1], d[0], s), e1 = __builtin_amdgcn_alignbyte(d[2], d[1], s),
-                           e2 = __builtin_amdgcn_alignbyte(d[3], d[2], s);
-            uint4 q;
-            q.x = e0 & 0xffffffu;
-            q.y = (e0 >> 24) | ((e1 & 0xffffu) << 8);
-            q.z = (e1 >> 16) | ((e2 & 0xffu) << 16);
-            q.w = e2 >> 8;
-            *(uint4 *)&px[r * w_pad + 4 * g] = q;
-        }
-    }
+    src.template fill<R>(px, blockDim.x, f, r0, rows, w, w_pad);
     __syncthreads();
     const int x = threadIdx.x;
     if (x >= W) return;
@@ -250,8 +270,9 @@ int frames_per_launch(size_t blocks_per_frame, size_t threads)
     return f < 1 ? 1 : (f > 0x7fffffff ? 0x7fffffff : (int)f);
 }
 
-int launch_h(const uint8_t *src, size_t src_fs, size_t src_rs, int frames, int rows, int w, int W, const Table &t, uint8_t *dst,
-             size_t dst_fs, size_t dst_rs, hipStream_t st)
+template <class Rows>
+int launch_h(const Rows &src, int frames, int rows, int w, int W, const Table &t, uint8_t *dst, size_t dst_fs, size_t dst_rs,
+             hipStream_t st)
 {
     const int threads = (W + 63) & ~63;
     const int w_pad = (w + 3) & ~3;
@@ -260,34 +281,34 @@ int launch_h(const uint8_t *src, size_t src_fs, size_t src_rs, int frames, int r
     const int step = frames_per_launch(bpf, (size_t)threads);
     for (int f0 = 0; f0 < frames; f0 += step) {
         const int fn = frames - f0 < step ? frames - f0 : step;
-        const uint8_t *s = src + (size_t)f0 * src_fs;
-        uint8_t *d = dst + (size_t)f0 * dst_fs;
-        if (int rc = launch(R == 2 ? resize_h_kernel<2> : resize_h_kernel<1>, "resize_h_kernel launch", dim3((unsigned)fn * bpf), dim3(threads),
-                            (size_t)R * w_pad * 4, st, s, src_fs, src_rs, rows, w, W, t.bounds, t.k_taps, d, dst_fs, dst_rs))
+        if (int rc = launch(R == 2 ? resize_h_kernel<2, Rows> : resize_h_kernel<1, Rows>, Rows::label, dim3((unsigned)fn * bpf), dim3(threads),
+                            (size_t)R * w_pad * 4, st, src.from_frame(f0), rows, w, W, t.bounds, t.k_taps, dst + (size_t)f0 * dst_fs,
+                            dst_fs, dst_rs))
             return rc;
     }
     return IIV_OK;
 }
 
-int launch_v(const uint8_t *src, size_t src_fs, size_t src_rs, int frames, int row_bytes, int H, const Table &t, uint8_t *dst,
-             size_t dst_fs, size_t dst_rs, hipStream_t st)
+// (the vertical pass reads packed RGB rows only: a source's, or the horizontal pass's result)
+int launch_v(const RgbRows &src, int frames, int row_bytes, int H, const Table &t, uint8_t *dst, size_t dst_fs, size_t dst_rs,
+             hipStream_t st)
 {
     const int bpr = (row_bytes + 1023) / 1024;
     const unsigned bpf = (unsigned)H * (unsigned)bpr;
     const int step = frames_per_launch(bpf, 256);
     for (int f0 = 0; f0 < frames; f0 += step) {
         const int fn = frames - f0 < step ? frames - f0 : step;
-        if (int rc = launch(resize_v_kernel, "resize_v_kernel launch", dim3((unsigned)fn * bpf), dim3(256), 0, st, src + (size_t)f0 * src_fs,
-                            src_fs, src_rs, row_bytes, H, bpr, t.bounds, t.k_rows, t.ksize, dst + (size_t)f0 * dst_fs, dst_fs, dst_rs))
+        if (int rc = launch(resize_v_kernel, "resize_v_kernel launch", dim3((unsigned)fn * bpf), dim3(256), 0, st, src.from_frame(f0).src,
+                            src.fs, src.rs, row_bytes, H, bpr, t.bounds, t.k_rows, t.ksize, dst + (size_t)f0 * dst_fs, dst_fs, dst_rs))
             return rc;
     }
     return IIV_OK;
 }
 
 // ---- f11: YUV 4:2:0 sources (include/iivision.h: iiv_resize_frames_yuv420) ------------------------------------
-// The conversion is fused into the horizontal pass: resize_h_yuv_kernel is resize_h_kernel with another loader.  Where the
-// horizontal pass does not come first (same size, vertical only, h > 100 w) yuv_to_rgb_kernel writes the RGB frames of a chunk
-// into a stream-ordered scratch and iiv_resize_frames takes them from there.
+// The conversion is fused into the horizontal pass: YuvRows is resize_h_kernel's second row source.  Where the horizontal pass
+// does not come first (same size, vertical only, h > 100 w) yuv_to_rgb_kernel writes the RGB frames of a chunk into a
+// stream-ordered scratch and the RGB path takes them from there.
 
 struct YuvMatrix {   // (y_off, ky, rv, gu, gv, bu) of the header, by value in the kernel's arguments
     int32_t y_off, ky, rv, gu, gv, bu;
@@ -299,6 +320,7 @@ struct YuvSrc {   // the planes of a batch of frames: byte strides, ps = the chr
     const uint8_t *u, *v;
     size_t c_fs, c_rs;
     int ps;
+    YuvSrc from_frame(int f0) const { return {y + (size_t)f0 * y_fs, y_fs, y_rs, u + (size_t)f0 * c_fs, v + (size_t)f0 * c_fs, c_fs, c_rs, ps}; }
 };
 
 // what two neighbouring chroma samples add to R, G and B of the pixels under them, the rounding 128 included
@@ -353,56 +375,28 @@ __device__ inline ChromaTerms load_chroma(const YuvSrc &s, size_t f, int row, in
     return chroma_terms(load_unaligned(ur + at, ur + len), load_unaligned(vr + at, vr + len), s.ps, m);
 }
 
-// Horizontal pass over a 4:2:0 source: resize_h_kernel, the R rows' pixels converted as they are unpacked into LDS.  R = 2:
-// rows (2 k, 2 k + 1), which share their chroma row (an odd h leaves the last row alone).
-template <int R>
-__global__ __launch_bounds__(1024) void resize_h_yuv_kernel(YuvSrc s, YuvMatrix m, int rows, int w, int W,
-                                                            const int2 *__restrict__ bounds, const int32_t *__restrict__ k_taps,
-                                                            uint8_t *__restrict__ dst, size_t dst_fs, size_t dst_rs)
-{
-    extern __shared__ uint32_t px[];   // [R][w_pad] pixels, r | g << 8 | b << 16
-    const int groups = (rows + R - 1) / R;
-    const int f = blockIdx.x / groups, r0 = (blockIdx.x % groups) * R;
-    const int w_pad = (w + 3) & ~3;
-    const int n4 = w_pad >> 2;
-    for (int g = threadIdx.x; g < n4; g += blockDim.x) {
-        const ChromaTerms t = load_chroma(s, (size_t)f, r0, g, w, m);
+struct YuvRows {   // 4:2:0 planes, each pixel converted as it is unpacked; the matrix by value: the host copy may change at once
+    YuvSrc s;
+    YuvMatrix m;
+    static constexpr const char *label = "resize_h_kernel<YuvRows> launch";
+    YuvRows from_frame(int f0) const { return {s.from_frame(f0), m}; }
+
+    // R = 2: rows (2 k, 2 k + 1), which share their chroma row and its terms (an odd h leaves the last row alone)
+    template <int R>
+    __device__ inline void fill(uint32_t *px, unsigned nt, int f, int r0, int rows, int w, int w_pad) const
+    {
+        const int n4 = w_pad >> 2;
+        for (int g = threadIdx.x; g < n4; g += nt) {
+            const ChromaTerms t = load_chroma(s, (size_t)f, r0, g, w, m);
 #pragma unroll
-        for (int r = 0; r < R; r++) {
-            if (r0 + r >= rows) break;
-            const uint8_t *row = s.y + (size_t)f * s.y_fs + (size_t)(r0 + r) * s.y_rs;
-            *(uint4 *)&px[r * w_pad + 4 * g] = yuv_to_rgb4(load_unaligned(row + 4 * (size_t)g, row + w), t, m);
+            for (int r = 0; r < R; r++) {
+                if (r0 + r >= rows) break;
+                const uint8_t *row = s.y + (size_t)f * s.y_fs + (size_t)(r0 + r) * s.y_rs;
+                *(uint4 *)&px[r * w_pad + 4 * g] = yuv_to_rgb4(load_unaligned(row + 4 * (size_t)g, row + w), t, m);
+            }
         }
     }
-    __syncthreads();
-    const int x = threadIdx.x;
-    if (x >= W) return;
-    const int2 bd = bounds[x];
-    int32_t acc[R][3];
-#pragma unroll
-    for (int r = 0; r < R; r++) acc[r][0] = acc[r][1] = acc[r][2] = 1 << (kPrecisionBits - 1);
-    const uint32_t *pr = px + bd.x;
-    const int32_t *kp = k_taps + x;
-#pragma unroll 4
-    for (int j = 0; j < bd.y; j++) {
-        const int32_t c = kp[(size_t)j * W];
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const uint32_t v = pr[r * w_pad + j];
-            acc[r][0] += __mul24((int)(v & 0xffu), c);
-            acc[r][1] += __mul24((int)((v >> 8) & 0xffu), c);
-            acc[r][2] += __mul24((int)(v >> 16), c);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        if (r0 + r >= rows) break;
-        uint8_t *o = dst + (size_t)f * dst_fs + (size_t)(r0 + r) * dst_rs + 3 * (size_t)x;
-        o[0] = (uint8_t)clamp_shift(acc[r][0]);
-        o[1] = (uint8_t)clamp_shift(acc[r][1]);
-        o[2] = (uint8_t)clamp_shift(acc[r][2]);
-    }
-}
+};
 
 // The conversion alone: thread = four pixels of one row -> twelve bytes of dst [frames][rows][dst_rs], dst 4-byte aligned
 // and dst_rs = 3 w_pad (the last group's pad pixels land inside the row's stride).  `total` = frames * rows * w_pad / 4.
@@ -424,30 +418,84 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(YuvSrc s, YuvMatrix m, 
     o[2] = (q.z >> 16) | (q.w << 8);
 }
 
-YuvSrc from_frame(YuvSrc s, int f0)
+// ---- the host side both entry points share ------------------------------------------------------------------------------------
+
+int check_sizes(const char *entry, int n, int h, int w, int H, int W)
 {
-    s.y += (size_t)f0 * s.y_fs;
-    s.u += (size_t)f0 * s.c_fs;
-    s.v += (size_t)f0 * s.c_fs;
-    return s;
+    if (n < 0 || h < 1 || h > kMaxIn || w < 1 || w > kMaxIn || H < 1 || H > kMaxOut || W < 1 || W > kMaxOut)
+        return set_error(IIV_ERR_INVALID, "%s: n >= 0, h, w in 1..%d, H, W in 1..%d (got n %d, %dx%d -> %dx%d)", entry, kMaxIn, kMaxOut, n,
+                         h, w, H, W);
+    return IIV_OK;
 }
 
-int launch_h_yuv(const YuvSrc &src, const YuvMatrix &m, int frames, int rows, int w, int W, const Table &t, uint8_t *dst,
-                 size_t dst_fs, size_t dst_rs, hipStream_t st)
+// the frames of one piece of a batch: what kChunkMidBytes hold of `frame_bytes` each, at least 1, at most `cap` (0: none) and n
+int frames_per_piece(size_t frame_bytes, size_t cap, int n)
 {
-    const int threads = (W + 63) & ~63;
-    const int w_pad = (w + 3) & ~3;
-    const int R = w_pad <= 4096 ? 2 : 1;
-    const unsigned bpf = (unsigned)((rows + R - 1) / R);
-    const int step = frames_per_launch(bpf, (size_t)threads);
-    for (int f0 = 0; f0 < frames; f0 += step) {
-        const int fn = frames - f0 < step ? frames - f0 : step;
-        if (int rc = launch(R == 2 ? resize_h_yuv_kernel<2> : resize_h_yuv_kernel<1>, "resize_h_yuv_kernel launch", dim3((unsigned)fn * bpf),
-                            dim3(threads), (size_t)R * w_pad * 4, st, from_frame(src, f0), m, rows, w, W, t.bounds, t.k_taps,
-                            dst + (size_t)f0 * dst_fs, dst_fs, dst_rs))
-            return rc;
+    size_t c = kChunkMidBytes / frame_bytes;
+    if (c < 1) c = 1;
+    if (cap && c > cap) c = cap;
+    return c > (size_t)n ? n : (int)c;
+}
+
+// Stream-ordered scratch for the length of one call: freed behind the work on its stream.  done(rc, ..) frees it and returns the
+// work's status rc, or the free's when the work succeeded; a call that leaves earlier frees it without a report.
+class StreamScratch {
+public:
+    explicit StreamScratch(hipStream_t st) : st_(st) {}
+    StreamScratch(const StreamScratch &) = delete;
+    StreamScratch &operator=(const StreamScratch &) = delete;
+    ~StreamScratch() { if (p_) (void)hipFreeAsync(p_, st_); }
+    int alloc(size_t bytes, const char *what) { return hip_check(hipMallocAsync((void **)&p_, bytes, st_), what); }
+    int done(int rc, const char *what)
+    {
+        const int rc_free = p_ ? hip_check(hipFreeAsync(p_, st_), what) : IIV_OK;
+        p_ = nullptr;
+        return rc ? rc : rc_free;
     }
-    return IIV_OK;
+    uint8_t *get() const { return p_; }
+
+private:
+    hipStream_t st_;
+    uint8_t *p_ = nullptr;
+};
+
+// Pillow's order: the horizontal pass first, unless there is none or the frame is more than a hundred times as tall as wide
+bool horizontal_first(int h, int w, int H, int W) { return W != w && !(H != h && h > 100 * w); }
+
+// n frames of `src` (h, w) -> d_dst (H, W), packed.  One pass goes straight into d_dst, in slices of frames that keep the grid
+// within range; two go through a stream-ordered scratch, a chunk of frames at a time: (h, W) after a horizontal first pass,
+// (H, w) after a vertical one.  The vertical pass reads packed RGB rows only, so it comes first for RgbRows alone.
+template <class Rows>
+int resize_rows(const Rows &src, int n, int h, int w, int H, int W, uint8_t *d_dst, hipStream_t st)
+{
+    constexpr bool packed = std::is_same<Rows, RgbRows>::value;
+    const bool resize_w = W != w, resize_h = H != h, two = resize_w && resize_h, h_first = horizontal_first(h, w, H, W);
+    if (!packed && !h_first) return set_error(IIV_ERR_INVALID, "resize_rows: only packed RGB rows can take the vertical pass first");
+    const size_t dst_rs = 3 * (size_t)W, dst_fs = (size_t)H * dst_rs;
+    const Table *th = nullptr, *tv = nullptr;
+    int rc = IIV_OK;
+    // (same size: Pillow copies; the vertical pass with the in == out table -- one unit tap per row -- is that copy)
+    if (resize_w && (rc = get_table(w, W, &th))) return rc;
+    if ((resize_h || !resize_w) && (rc = get_table(h, H, &tv))) return rc;
+    const size_t mid_rs = (3 * (size_t)(h_first ? W : w) + 3) & ~(size_t)3, mid_fs = (size_t)(h_first ? h : H) * mid_rs;
+    const int piece = two ? frames_per_piece(mid_fs, 65536, n) : 65536;
+    StreamScratch mid(st);
+    if (two && (rc = mid.alloc((size_t)piece * mid_fs, "hipMallocAsync(resize scratch)"))) return rc;
+    const RgbRows mid_rows = {mid.get(), mid_fs, mid_rs};
+    const size_t fs1 = two ? mid_fs : dst_fs, rs1 = two ? mid_rs : dst_rs;   // where the first pass writes
+    for (int f0 = 0; f0 < n && !rc; f0 += piece) {
+        const int fn = n - f0 < piece ? n - f0 : piece;
+        const Rows s = src.from_frame(f0);
+        uint8_t *d = d_dst + (size_t)f0 * dst_fs, *d1 = two ? mid.get() : d;
+        if (h_first) {
+            rc = launch_h(s, fn, h, w, W, *th, d1, fs1, rs1, st);
+            if (two && !rc) rc = launch_v(mid_rows, fn, 3 * W, H, *tv, d, dst_fs, dst_rs, st);
+        } else if constexpr (packed) {
+            rc = launch_v(s, fn, 3 * w, H, *tv, d1, fs1, rs1, st);
+            if (two && !rc) rc = launch_h(mid_rows, fn, H, w, W, *th, d, dst_fs, dst_rs, st);
+        }
+    }
+    return mid.done(rc, "hipFreeAsync(resize scratch)");
 }
 
 }  // namespace
@@ -470,68 +518,20 @@ extern "C" int iiv_resize_coeffs(int in_size, int out_size, int *ksize, int32_t 
 extern "C" int iiv_resize_frames(int n, int h, int w, const uint8_t *d_src, size_t frame_stride, size_t row_stride, int H, int W,
                                  uint8_t *d_dst, void *stream)
 {
-    if (n < 0 || h < 1 || h > kMaxIn || w < 1 || w > kMaxIn || H < 1 || H > kMaxOut || W < 1 || W > kMaxOut)
-        return set_error(IIV_ERR_INVALID, "iiv_resize_frames: n >= 0, h, w in 1..%d, H, W in 1..%d (got n %d, %dx%d -> %dx%d)", kMaxIn,
-                         kMaxOut, n, h, w, H, W);
+    if (int rc = check_sizes("iiv_resize_frames", n, h, w, H, W)) return rc;
     if (n == 0) return IIV_OK;
     const size_t src_row = 3 * (size_t)w, src_frame = (size_t)(h - 1) * row_stride + src_row;
     if (!d_src || !d_dst || row_stride < (h > 1 ? src_row : 0) || (n > 1 && frame_stride < src_frame))
         return set_error(IIV_ERR_INVALID, "iiv_resize_frames: d_src / d_dst NULL, or rows / frames overlap (row_stride %zu < %zu or "
                          "frame_stride %zu < %zu)", row_stride, src_row, frame_stride, src_frame);
-    const hipStream_t st = (hipStream_t)stream;
-    const bool resize_w = W != w, resize_h = H != h;
-    const size_t dst_rs = 3 * (size_t)W, dst_fs = (size_t)H * dst_rs;
-    const Table *th = nullptr, *tv = nullptr;
-    int rc;
-    // (same size: Pillow copies; the vertical pass with the in == out table -- one unit tap per row -- is that copy)
-    if (resize_w && (rc = get_table(w, W, &th))) return rc;
-    if ((resize_h || !resize_w) && (rc = get_table(h, H, &tv))) return rc;
-    if (!(resize_w && resize_h)) {
-        // one pass, straight into d_dst, in slices of frames that keep the grid within range
-        const int step = 65536;
-        for (int f0 = 0; f0 < n; f0 += step) {
-            const int fn = n - f0 < step ? n - f0 : step;
-            const uint8_t *s = d_src + (size_t)f0 * frame_stride;
-            uint8_t *d = d_dst + (size_t)f0 * dst_fs;
-            rc = resize_w ? launch_h(s, frame_stride, row_stride, fn, h, w, W, *th, d, dst_fs, dst_rs, st)
-                          : launch_v(s, frame_stride, row_stride, fn, 3 * w, H, *tv, d, dst_fs, dst_rs, st);
-            if (rc) return rc;
-        }
-        return IIV_OK;
-    }
-    // two passes through a stream-ordered scratch: (h, W) after a horizontal first pass, (H, w) after a vertical one
-    const bool v_first = h > 100 * w;
-    const size_t mid_rs = ((v_first ? 3 * (size_t)w : 3 * (size_t)W) + 3) & ~(size_t)3;
-    const size_t mid_fs = (size_t)(v_first ? H : h) * mid_rs;
-    size_t chunk = kChunkMidBytes / mid_fs;
-    if (chunk < 1) chunk = 1;
-    if (chunk > 65536) chunk = 65536;
-    if (chunk > (size_t)n) chunk = (size_t)n;
-    uint8_t *mid = nullptr;
-    IIV_HIP(hipMallocAsync((void **)&mid, chunk * mid_fs, st));
-    for (int f0 = 0; f0 < n && !rc; f0 += (int)chunk) {
-        const int fn = n - f0 < (int)chunk ? n - f0 : (int)chunk;
-        const uint8_t *s = d_src + (size_t)f0 * frame_stride;
-        uint8_t *d = d_dst + (size_t)f0 * dst_fs;
-        if (v_first) {
-            rc = launch_v(s, frame_stride, row_stride, fn, 3 * w, H, *tv, mid, mid_fs, mid_rs, st);
-            if (!rc) rc = launch_h(mid, mid_fs, mid_rs, fn, H, w, W, *th, d, dst_fs, dst_rs, st);
-        } else {
-            rc = launch_h(s, frame_stride, row_stride, fn, h, w, W, *th, mid, mid_fs, mid_rs, st);
-            if (!rc) rc = launch_v(mid, mid_fs, mid_rs, fn, 3 * W, H, *tv, d, dst_fs, dst_rs, st);
-        }
-    }
-    const int rc_free = hip_check(hipFreeAsync(mid, st), "hipFreeAsync(resize scratch)");
-    return rc ? rc : rc_free;
+    return resize_rows(RgbRows{d_src, frame_stride, row_stride}, n, h, w, H, W, d_dst, (hipStream_t)stream);
 }
 
 extern "C" int iiv_resize_frames_yuv420(int n, int h, int w, const uint8_t *d_y, size_t y_frame_stride, size_t y_row_stride,
                                         const uint8_t *d_u, const uint8_t *d_v, size_t c_frame_stride, size_t c_row_stride,
                                         int c_pixel_stride, const int32_t matrix[6], int H, int W, uint8_t *d_dst, void *stream)
 {
-    if (n < 0 || h < 1 || h > kMaxIn || w < 1 || w > kMaxIn || H < 1 || H > kMaxOut || W < 1 || W > kMaxOut)
-        return set_error(IIV_ERR_INVALID, "iiv_resize_frames_yuv420: n >= 0, h, w in 1..%d, H, W in 1..%d (got n %d, %dx%d -> %dx%d)",
-                         kMaxIn, kMaxOut, n, h, w, H, W);
+    if (int rc = check_sizes("iiv_resize_frames_yuv420", n, h, w, H, W)) return rc;
     if (c_pixel_stride != 1 && c_pixel_stride != 2)
         return set_error(IIV_ERR_INVALID, "iiv_resize_frames_yuv420: c_pixel_stride 1 (planar) or 2 (interleaved), got %d", c_pixel_stride);
     if (!matrix) return set_error(IIV_ERR_INVALID, "iiv_resize_frames_yuv420: matrix NULL");
@@ -550,54 +550,21 @@ extern "C" int iiv_resize_frames_yuv420(int n, int h, int w, const uint8_t *d_y,
         return set_error(IIV_ERR_INVALID, "iiv_resize_frames_yuv420: chroma rows / frames overlap (c_row_stride %zu < %zu or c_frame_stride "
                          "%zu < %zu)", c_row_stride, c_row, c_frame_stride, c_frame);
     const hipStream_t st = (hipStream_t)stream;
-    const YuvMatrix m = {matrix[0], matrix[1], matrix[2], matrix[3], matrix[4], matrix[5]};
-    const YuvSrc src = {d_y, y_frame_stride, y_row_stride, d_u, d_v, c_frame_stride, c_row_stride, c_pixel_stride};
-    const bool resize_w = W != w, resize_h = H != h;
-    const size_t dst_rs = 3 * (size_t)W, dst_fs = (size_t)H * dst_rs;
-    const Table *th = nullptr, *tv = nullptr;
-    int rc = IIV_OK;
-    if (resize_w && (rc = get_table(w, W, &th))) return rc;
-    if ((resize_h || !resize_w) && (rc = get_table(h, H, &tv))) return rc;
-    if (!resize_w || (resize_h && h > 100 * w)) {
-        // the horizontal pass is not the first: convert a chunk of frames into scratch, then the RGB path as it is
-        const size_t rgb_rs = 3 * (size_t)((w + 3) & ~3), rgb_fs = (size_t)h * rgb_rs, n4 = (size_t)((w + 3) >> 2);
-        size_t chunk = kChunkMidBytes / rgb_fs;
-        if (chunk < 1) chunk = 1;
-        if (chunk > (size_t)n) chunk = (size_t)n;
-        uint8_t *rgb = nullptr;
-        IIV_HIP(hipMallocAsync((void **)&rgb, chunk * rgb_fs, st));
-        for (int f0 = 0; f0 < n && !rc; f0 += (int)chunk) {
-            const int fn = n - f0 < (int)chunk ? n - f0 : (int)chunk;
-            const size_t total = (size_t)fn * h * n4;   // (at most 32 MiB / 12, or one frame's 2^24)
-            rc = launch(yuv_to_rgb_kernel, "yuv_to_rgb_kernel launch", dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                        from_frame(src, f0), m, h, w, total, rgb, rgb_fs, rgb_rs);
-            if (!rc) rc = iiv_resize_frames(fn, h, w, rgb, rgb_fs, rgb_rs, H, W, d_dst + (size_t)f0 * dst_fs, stream);
-        }
-        const int rc_free = hip_check(hipFreeAsync(rgb, st), "hipFreeAsync(yuv scratch)");
-        return rc ? rc : rc_free;
+    const YuvRows src = {{d_y, y_frame_stride, y_row_stride, d_u, d_v, c_frame_stride, c_row_stride, c_pixel_stride},
+                         {matrix[0], matrix[1], matrix[2], matrix[3], matrix[4], matrix[5]}};
+    if (horizontal_first(h, w, H, W)) return resize_rows(src, n, h, w, H, W, d_dst, st);
+    // the horizontal pass is not the first: convert a chunk of frames into scratch, then the RGB path as it is
+    const size_t rgb_rs = 3 * (size_t)((w + 3) & ~3), rgb_fs = (size_t)h * rgb_rs, n4 = (size_t)((w + 3) >> 2);
+    const int piece = frames_per_piece(rgb_fs, 0, n);
+    StreamScratch rgb(st);
+    int rc = rgb.alloc((size_t)piece * rgb_fs, "hipMallocAsync(yuv scratch)");
+    if (rc) return rc;
+    for (int f0 = 0; f0 < n && !rc; f0 += piece) {
+        const int fn = n - f0 < piece ? n - f0 : piece;
+        const size_t total = (size_t)fn * h * n4;   // (at most 32 MiB / 12, or one frame's 2^24)
+        rc = launch(yuv_to_rgb_kernel, "yuv_to_rgb_kernel launch", dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                    src.s.from_frame(f0), src.m, h, w, total, rgb.get(), rgb_fs, rgb_rs);
+        if (!rc) rc = resize_rows(RgbRows{rgb.get(), rgb_fs, rgb_rs}, fn, h, w, H, W, d_dst + (size_t)f0 * 3 * H * W, st);
     }
-    if (!resize_h) {
-        // the horizontal pass alone, straight into d_dst
-        const int step = 65536;
-        for (int f0 = 0; f0 < n; f0 += step) {
-            const int fn = n - f0 < step ? n - f0 : step;
-            if ((rc = launch_h_yuv(from_frame(src, f0), m, fn, h, w, W, *th, d_dst + (size_t)f0 * dst_fs, dst_fs, dst_rs, st))) return rc;
-        }
-        return IIV_OK;
-    }
-    // the common path: the fused horizontal pass into the (h, W) scratch iiv_resize_frames would use, then its vertical pass
-    const size_t mid_rs = (3 * (size_t)W + 3) & ~(size_t)3, mid_fs = (size_t)h * mid_rs;
-    size_t chunk = kChunkMidBytes / mid_fs;
-    if (chunk < 1) chunk = 1;
-    if (chunk > 65536) chunk = 65536;
-    if (chunk > (size_t)n) chunk = (size_t)n;
-    uint8_t *mid = nullptr;
-    IIV_HIP(hipMallocAsync((void **)&mid, chunk * mid_fs, st));
-    for (int f0 = 0; f0 < n && !rc; f0 += (int)chunk) {
-        const int fn = n - f0 < (int)chunk ? n - f0 : (int)chunk;
-        rc = launch_h_yuv(from_frame(src, f0), m, fn, h, w, W, *th, mid, mid_fs, mid_rs, st);
-        if (!rc) rc = launch_v(mid, mid_fs, mid_rs, fn, 3 * W, H, *tv, d_dst + (size_t)f0 * dst_fs, dst_fs, dst_rs, st);
-    }
-    const int rc_free = hip_check(hipFreeAsync(mid, st), "hipFreeAsync(resize scratch)");
-    return rc ? rc : rc_free;
+    return rgb.done(rc, "hipFreeAsync(yuv scratch)");
 }

@@ -1,12 +1,14 @@
 """GPU: iiv_resize_frames_yuv420 (csrc/iiv_resize.hip) past the first piece of each of its host loops, as
-tests/test_gpu_resize_batches.py does for iiv_resize_frames.  The entry point cuts a call into frames three times over, and each
-loop moves three plane pointers with from_frame -- luma by y_frame_stride, both chroma planes by c_frame_stride:
+tests/test_gpu_resize_batches.py does for iiv_resize_frames.  A call is cut into frames in three places -- the entry point's
+conversion chunks, and the slices and chunks of resize_rows, the driver it shares with iiv_resize_frames -- and each moves three
+plane pointers with from_frame -- luma by y_frame_stride, both chroma planes by c_frame_stride:
 
     unfused    (W == w, or H != h and h > 100 w) yuv_to_rgb_kernel converts chunks of 32 MiB // (h * 3 * w_pad) frames, no cap,
-               into scratch and hands each chunk to iiv_resize_frames (which slices and chunks it again on its own)
-    fused      (both axes change, horizontal first) resize_h_yuv_kernel fills the (h, W) intermediate in chunks of
+               into scratch and hands each chunk to resize_rows<RgbRows>, iiv_resize_frames' driver (which slices and chunks it
+               again on its own)
+    fused      (both axes change, horizontal first) resize_h_kernel<R, YuvRows> fills the (h, W) intermediate in chunks of
                min(32 MiB // (h * mid_rs), 65536) frames
-    one pass   (H == h) resize_h_yuv_kernel straight to the output in slices of 65536 frames
+    one pass   (H == h) resize_h_kernel<R, YuvRows> straight to the output in slices of 65536 frames
 
 Frame i of every plane is base[i % 7], gathered on the device; the model -- resize_model.resize(yuv_model.to_rgb(base)) -- runs
 on the seven, and every frame of the batch is compared on the device.  Every piece length is prime to 7, so a piece that reads or
@@ -14,8 +16,8 @@ writes the wrong frames, or reads one plane's frames at another plane's stride, 
 with padding rows behind every plane's frame (c_frame_stride is neither y_frame_stride / 4 nor ch * cw), and interleaved NV12 cut
 out of a larger allocation (chroma pixel stride 2); everything outside the planes holds a fill byte.
 
-launch_h_yuv's own frames_per_launch step is not reached here, and cannot be at a size a test can hold.  A launch takes up to
-2^32 - 1 work-items; launch_h_yuv is handed fn <= 65536 frames of bpf = ceil(h / R) workgroups of T = W rounded up to 64
+launch_h<YuvRows>'s own frames_per_launch step is not reached here, and cannot be at a size a test can hold.  A launch takes up to
+2^32 - 1 work-items; launch_h<YuvRows> is handed fn <= 65536 frames of bpf = ceil(h / R) workgroups of T = W rounded up to 64
 threads, so the step acts only where fn * bpf * T >= 2^32.
     fused     fn <= 32 MiB / (h * mid_rs) with mid_rs >= max(3 W, 4) and bpf <= h: fn * bpf * T <= 32 MiB * T / mid_rs, which is
               2^25 * 64 / 4 = 2^29 up to W = 64 and less than 2^25 * (W + 63) / (3 W) < 2^25 beyond it.  Never.
@@ -23,7 +25,8 @@ threads, so the step acts only where fn * bpf * T >= 2^32.
               (w <= 4096) bpf <= 512, so T >= 128, W >= 65, and the output is 65536 * h * 3 W bytes with h >= 2 bpf - 1: the
               least is 65536 * 1023 * 195 = 13 GB at W = 65 (24 GB at T = 1024, W = 961).  With one row a workgroup (w > 4096)
               bpf = h = 1024 and T = 64 do, but the luma plane alone is 65536 * 1024 * 4097 bytes = 275 GB.
-The step is the function the RGB path uses (test_gpu_resize_batches.test_grid_limit crosses it through the vertical pass)."""
+The launch loop is the one the RGB rows go through (test_gpu_resize_batches.test_grid_limit crosses the step through the
+vertical pass)."""
 import numpy as np
 import pytest
 
@@ -37,7 +40,7 @@ FILL = 0xC7
 
 
 def path(h, w, H, W):
-    """which of iiv_resize_frames_yuv420's three loops a shape takes (iiv_resize.hip: the path choice)"""
+    """which of the three ways through iiv_resize_frames_yuv420 a shape takes (iiv_resize.hip: horizontal_first, resize_rows)"""
     resize_w, resize_h = W != w, H != h
     if not resize_w or (resize_h and h > 100 * w):
         return "unfused"

@@ -5,9 +5,9 @@ once, that every preset puts each of -1, 0, 255 and 256 in front of the clamp in
 matrices reach the extremes of the contract).  What a packed clamp would do wrong shows here as a wrong byte.
 
     B1  yuv_to_rgb_kernel: 16 same-size frames of 1024 x 1024, every triple in one pixel; expected yuv_model.to_rgb of the planes
-    B2  the loader of resize_h_yuv_kernel<2>: 16384 frames of 1024 constant rows, 4 -> 2 pixels wide, H == h: the horizontal
+    B2  the loader of resize_h_kernel<2, YuvRows>: 16384 frames of 1024 constant rows, 4 -> 2 pixels wide, H == h: the horizontal
         pass alone, which a constant row passes unchanged, so every output byte is the loader's conversion
-    B3  the loader of resize_h_yuv_kernel<1> (w = 4100 > 4096): 4096 constant rows, a seeded sample of the triples next to the
+    B3  the loader of resize_h_kernel<1, YuvRows> (w = 4100 > 4096): 4096 constant rows, a seeded sample of the triples next to the
         clamps joined with a uniform one
 For B2 and B3 the expected output is yuv_model.to_rgb of one column of the rows, repeated W times: that this is
 resize_model.resize(to_rgb(...)) for 4 -> 2 and 4100 -> 2 is test_yuv_model.test_a_constant_row_passes_the_horizontal_pass_unchanged.
@@ -75,7 +75,7 @@ def test_same_size_frames_over_all_triples(native, matrix):
 
 @pytest.mark.parametrize("matrix", MATRICES, ids=IDS)
 def test_two_row_loader_over_all_triples(native, matrix):
-    """B2: resize_h_yuv_kernel<2>, every triple a constant row"""
+    """B2: resize_h_kernel<2, YuvRows>, every triple a constant row"""
     import torch
     cy, cu, cv = _cached("b2", E.b2_columns)
     n, h = E.B2_SHAPE
@@ -91,7 +91,7 @@ def test_two_row_loader_over_all_triples(native, matrix):
 
 @pytest.mark.parametrize("matrix", MATRICES, ids=IDS)
 def test_one_row_loader_on_the_boundary_sample(native, matrix):
-    """B3: resize_h_yuv_kernel<1>"""
+    """B3: resize_h_kernel<1, YuvRows>"""
     cy, cu, cv = E.b3_columns(matrix)
     w, W = E.B3_WIDTH, 2
     assert ((w + 3) & ~3) > 4096 and cy.shape[0] * cy.shape[1] == 4096

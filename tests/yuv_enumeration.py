@@ -4,7 +4,7 @@ tests run (tests/test_gpu_yuv_exhaustive.py on the device, tests/test_yuv_model.
 
     B1  same-size frames (yuv_to_rgb_kernel): 16 frames of 1024 x 1024.  The 2 x 2 chroma block b = 0 .. 2^22 - 1, numbered by
         frame, chroma row, chroma column, carries U = b & 255, V = (b >> 8) & 255 and the four luma samples 4 (b >> 16) + 2 dy + dx.
-    B2  constant rows (the fused loader of resize_h_yuv_kernel<2>): 16384 frames of 1024 rows (the horizontal pass alone needs
+    B2  constant rows (the fused loader of resize_h_kernel<2, YuvRows>): 16384 frames of 1024 rows (the horizontal pass alone needs
         H == h, and H is at most 1024).  Row pair p = 0 .. 2^23 - 1, numbered by frame, chroma row, carries (U, V) = (p & 255,
         (p >> 8) & 255); its rows carry Y = 2 (p >> 16) + dy.  The planes are one column wide here; widen() repeats it.
     B3  constant rows for the one-row form (w > 4096): frames of two rows; half of them hold a triple on the boundary of a clamp

@@ -83,8 +83,8 @@ def main():
             times.append(e0.elapsed_time(e1) / 1e3)
         t = min(times)
         floor = a.frames * h * w * 3 / (HBM_MEASURED_READ_GBS * 1e9)
-        line = "%4dx%-4d n=%d: %.3f ms (median %.3f) = %.2f M frames/s, %.0f GB/s of source; read floor %.3f ms -> %.2f of it" % (
-            w, h, a.frames, t * 1e3, sorted(times)[len(times) // 2] * 1e3, a.frames / t / 1e6, a.frames * h * w * 3 / t / 1e9,
+        line = "%4dx%-4d n=%d: %.3f ms (median %.3f, max %.3f) = %.2f M frames/s, %.0f GB/s of source; read floor %.3f ms -> %.2f of it" % (
+            w, h, a.frames, t * 1e3, sorted(times)[len(times) // 2] * 1e3, max(times) * 1e3, a.frames / t / 1e6, a.frames * h * w * 3 / t / 1e9,
             floor * 1e3, floor / t)
         if pil:
             host = src[:48].cpu().numpy()
