@@ -128,22 +128,30 @@ class Probe:
         n = int(np.prod(shape)) * np.dtype(dtype).itemsize
         return np.full(n, SENTINEL_B, np.uint8).view(dtype).reshape(shape)
 
-    def run(self, call, asynchronous=True):
-        """call(stream_pointer) makes the call(s) under test and returns what the caller wants back.
-        asynchronous=False: a synchronising entry point -- same protocol, no `busy` condition."""
-        import ctypes
+    def begin(self, null_sleep=0, synchronize=True):
+        """The probe up to the call under test, enqueued on the side stream: the sleep, the marker, the real inputs, sentinel B.
+        null_sleep: cycles of a second sleep put on the NULL stream behind the marker (tests/test_gpu_cold_paths.py: what a
+        first use issues on the null stream then runs late instead of early).  synchronize=False: another probe is already
+        asleep on its own stream (two encoders side by side)."""
         t = self.torch
-        t.cuda.synchronize()
-        st = ctypes.c_void_p(self.side.cuda_stream)
+        if synchronize:
+            t.cuda.synchronize()
         with t.cuda.stream(self.side):
             t.cuda._sleep(SLEEP_CYCLES)
             # the null stream runs beside this stream NOW, under this probe's own sleep: what the call issues on it runs ahead
             self.beside = _null_overtakes(self.side, self._marker)
+            if null_sleep:
+                with t.cuda.stream(t.cuda.default_stream()):
+                    t.cuda._sleep(null_sleep)
             for live, real, _, _ in self._inputs:
                 live.copy_(real, non_blocking=True)
             for out in self._outputs:
                 self.bytes_of(out).fill_(SENTINEL_B)
-            result = call(st)
+
+    def end(self, asynchronous=True):
+        """Right after the call(s) returned: the scribbles, the decoys back, `busy`, the synchronise and the probe's own conditions."""
+        t = self.torch
+        with t.cuda.stream(self.side):
             for a, s in self._host:
                 a[...] = s
             for fn in self._scribbles:
@@ -157,4 +165,13 @@ class Probe:
         assert self.beside, "a null-stream operation did not run ahead of the sleeping side stream: the probe would be blind"
         if asynchronous:
             assert self.busy, "the side stream had drained when the call returned: the call synchronised, or the sleep is too short"
+
+    def run(self, call, asynchronous=True, null_sleep=0):
+        """call(stream_pointer) makes the call(s) under test and returns what the caller wants back.
+        asynchronous=False: a synchronising entry point -- same protocol, no `busy` condition."""
+        import ctypes
+        self.begin(null_sleep)
+        with self.torch.cuda.stream(self.side):
+            result = call(ctypes.c_void_p(self.side.cuda_stream))
+        self.end(asynchronous)
         return result
