@@ -1,6 +1,6 @@
 """Seeded differential fuzz of the kernels around the encoder against their numpy models: the generator that draws cases for
 resize_model, ingest_model / diffusion_model, mono_model, render_model / render_error_model, a2m_model, audio_model,
-bitmap_model, yuv_model and direct_model (tests/fuzz_parity.py does the same for the encoder against the oracle).
+bitmap_model, yuv_model, direct_model and colour_model (tests/fuzz_parity.py does the same for the encoder against the oracle).
 
     python tests/stage_fuzz.py [rounds] [seed] [--stage NAME] [--round K]     (on an MI355X; 200 rounds is the long run)
 
@@ -54,6 +54,11 @@ What a stage draws (sizes are the smallest at which each kernel can still go wro
     chain_yuv  2..3 frames of random 4:2:0 planes through resize_frames_yuv420 -> frames_to_memory_maps_direct -> render_rgb ->
              render_error (against the resized frames), each handed the very tensor the one before returned; every arrow
              against the models' composition
+    colour   a palette by turns uniform, dark (bytes 0..27: both linear segments' ends), grey-ish (a grey and -2..2 a channel)
+             or with k rows repeated, through iiv_cie2000_matrix: floats within colour_model.T of colour_model, ints equal;
+             n of COUNTS or 100..700 Lab pairs, uniform over [0, 100] x [-128, 128]^2 mixed with the palette's own, through
+             iiv_delta_e_cie2000 within T.  Conditions on the case, as on the committed set of tests/colour_cases.py: no
+             delta-E of the palette within 1e-6 of an integer, no pair within 1e-6 degrees of a discontinuity of the formula
 
 check_ticks lets ticks differ within 1e-3 of a level boundary if fewer than 0.5 % of a stream's samples do.  That cap is a
 condition on the case: draw_audio draws again (from the same generator, so still a function of the seed) while a stream of
@@ -76,6 +81,8 @@ for _p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "ii-vision_amd
 import a2m_model  # noqa: E402
 import audio_model  # noqa: E402
 import bitmap_model  # noqa: E402
+import colour_cases  # noqa: E402
+import colour_model  # noqa: E402
 import device_guards  # noqa: E402
 import diffusion_model  # noqa: E402
 import direct_model  # noqa: E402
@@ -87,11 +94,12 @@ import resize_model  # noqa: E402
 import yuv_model  # noqa: E402
 
 SEED = 2027
-STAGES = ("resize", "ingest", "mono", "render", "a2m", "audio", "chain", "bitmap", "yuv", "direct", "chain_yuv")   # (appended to: the index seeds the stage)
+STAGES = ("resize", "ingest", "mono", "render", "a2m", "audio", "chain", "bitmap", "yuv", "direct", "chain_yuv",
+          "colour")   # (appended to: the index seeds the stage)
 STAGE_ID = {name: i for i, name in enumerate(STAGES)}
 # rounds of tests/test_gpu_stage_fuzz.py (the chain, four stages a round, runs 4)
 ROUNDS = {"resize": 12, "ingest": 12, "mono": 12, "render": 12, "a2m": 12, "audio": 12, "chain": 4, "bitmap": 12, "yuv": 12, "direct": 12,
-          "chain_yuv": 4}
+          "chain_yuv": 4, "colour": 12}
 
 HGR, DHGR = 0, 1
 DIFFUSION = 256
@@ -970,13 +978,78 @@ def check_chain_yuv(native, case):
         _same(case, "chain_yuv: the cost against render_error's level 0", m_cost, m_sums[:, 0, :].sum(axis=1))
 
 
+# ---- palette bytes -> delta-E matrix, Lab pairs -> delta-E ------------------------------------------------------------------
+
+COLOUR_KINDS = ("uniform", "dark", "greyish", "duplicates")
+
+
+def _colour_palette(rng, kind):
+    if kind == "dark":
+        return rng.integers(0, 28, (16, 3))
+    if kind == "greyish":
+        return np.clip(rng.integers(0, 256, (16, 1)) + rng.integers(-2, 3, (16, 3)), 0, 255)
+    pal = rng.integers(0, 256, (16, 3))
+    if kind == "duplicates":
+        k = int(rng.integers(1, 16))
+        rows = rng.permutation(16)
+        pal[rows[:k]] = pal[rows[k:]][rng.integers(0, 16 - k, k)]
+    return pal
+
+
+def draw_colour(rng, round_index=0):
+    kind = COLOUR_KINDS[round_index % 4]
+    pal, redraws = colour_cases.draw_palette(rng, lambda g: _colour_palette(g, kind))
+    n = int(rng.choice(COUNTS)) if rng.random() < 0.5 else int(rng.integers(100, 701))
+    own = [colour_model.lab_double(row) for row in pal]
+    pairs, own_pairs = [], 0
+    while len(pairs) < n:
+        if rng.random() < 0.3:
+            i, j = (int(v) for v in rng.integers(0, 16, 2))
+            a, b, mine = own[i], own[j], 1
+        else:
+            a, b = (tuple(float(v) for v in rng.uniform((0, -128, -128), (100, 128, 128))) for _ in range(2))
+            mine = 0
+        if colour_cases.pair_allowed(a, b):
+            pairs.append((a, b))
+            own_pairs += mine
+        else:
+            redraws += 1
+    lab = np.array(pairs, dtype=np.float64).reshape(n, 2, 3)
+    params = dict(palette=kind, n=n, own_pairs=own_pairs, different=len(np.unique(pal, axis=0)), redraws=redraws,
+                  first="%02x%02x%02x" % tuple(pal[0]))
+    return dict(stage="colour", params=params, rgb=pal, lab1=np.ascontiguousarray(lab[:, 0]), lab2=np.ascontiguousarray(lab[:, 1]))
+
+
+def colour_wants(case):
+    """colour_model's values of a case: (the matrix as doubles, its floor, the pairs' delta-E as doubles)"""
+    f, i = colour_cases.matrix_of(case["rgb"].tobytes())
+    pairs = np.array([float(colour_model.delta_e(tuple(a.tolist()), tuple(b.tolist()))) for a, b in zip(case["lab1"], case["lab2"])])
+    return f, i, pairs
+
+
+def check_colour(native, case):
+    T = colour_model.T
+    want_f, want_i, want_pairs = colour_wants(case)
+    f, i = native.cie2000_matrix(case["rgb"])
+    _require(not np.isnan(f).any(), case, "cie2000_matrix: a NaN")
+    err = np.abs(f - want_f)
+    _require(err.max() <= T, case, lambda: "cie2000_matrix: %g from the model at %s (T = %g)" % (err.max(), divmod(int(err.argmax()), 16), T))
+    _same(case, "cie2000_matrix, the ints", i, want_i)
+    same = (case["rgb"][:, None, :] == case["rgb"][None, :, :]).all(axis=2)
+    _require(not f[same].any() and not np.signbit(f[same]).any(), case, "cie2000_matrix: a colour against itself is not 0.0")
+    got = native.delta_e_cie2000(case["lab1"], case["lab2"])
+    _require(got.shape == want_pairs.shape and not np.isnan(got).any(), case, "delta_e_cie2000: shape %s or a NaN" % (got.shape,))
+    err = np.abs(got - want_pairs)
+    _require(err.max() <= T, case, lambda: "delta_e_cie2000: %g from the model at pair %d (T = %g)" % (err.max(), int(err.argmax()), T))
+
+
 # ---- the loop ---------------------------------------------------------------------------------------------------------
 
 DRAW = {"resize": draw_resize, "ingest": draw_ingest, "mono": draw_mono, "render": draw_render, "a2m": draw_a2m, "audio": draw_audio,
-        "chain": draw_chain, "bitmap": draw_bitmap, "yuv": draw_yuv, "direct": draw_direct, "chain_yuv": draw_chain_yuv}
+        "chain": draw_chain, "bitmap": draw_bitmap, "yuv": draw_yuv, "direct": draw_direct, "chain_yuv": draw_chain_yuv, "colour": draw_colour}
 CHECK = {"resize": check_resize, "ingest": check_ingest, "mono": check_mono, "render": check_render, "a2m": check_a2m,
          "audio": check_audio, "chain": check_chain, "bitmap": check_bitmap, "yuv": check_yuv, "direct": check_direct,
-         "chain_yuv": check_chain_yuv}
+         "chain_yuv": check_chain_yuv, "colour": check_colour}
 
 
 def _fuzz(stage, native, rng, round_index, seed=None):
@@ -1030,8 +1103,13 @@ def fuzz_chain_yuv(native, rng, round_index, seed=None):
     return _fuzz("chain_yuv", native, rng, round_index, seed)
 
 
+def fuzz_colour(native, rng, round_index, seed=None):
+    return _fuzz("colour", native, rng, round_index, seed)
+
+
 FUZZ = {"resize": fuzz_resize, "ingest": fuzz_ingest, "mono": fuzz_mono, "render": fuzz_render, "a2m": fuzz_a2m, "audio": fuzz_audio,
-        "chain": fuzz_chain, "bitmap": fuzz_bitmap, "yuv": fuzz_yuv, "direct": fuzz_direct, "chain_yuv": fuzz_chain_yuv}
+        "chain": fuzz_chain, "bitmap": fuzz_bitmap, "yuv": fuzz_yuv, "direct": fuzz_direct, "chain_yuv": fuzz_chain_yuv,
+        "colour": fuzz_colour}
 
 
 def run(rounds, seed=SEED, stages=None, side_stream=False, first_round=0, log=None):

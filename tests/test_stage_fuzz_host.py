@@ -13,6 +13,7 @@ import pytest
 import a2m_model
 import audio_model
 import bitmap_model
+import colour_cases
 import diffusion_model
 import ingest_model
 import resize_model
@@ -31,7 +32,7 @@ def cases():
 
 def test_round_counts():
     assert F.ROUNDS == {"resize": 12, "ingest": 12, "mono": 12, "render": 12, "a2m": 12, "audio": 12, "chain": 4, "bitmap": 12, "yuv": 12,
-                        "direct": 12, "chain_yuv": 4}
+                        "direct": 12, "chain_yuv": 4, "colour": 12}
     assert set(F.ROUNDS) == set(F.STAGES) == set(F.DRAW) == set(F.CHECK) == set(F.FUZZ)
 
 
@@ -388,7 +389,34 @@ def test_chain_yuv_draws(cases):
     assert seen >= {280, 560, (280, True), (560, True)}, seen
 
 
-@pytest.mark.parametrize("stage", ["yuv", "direct", "chain_yuv"])
+def test_colour_draws(cases):
+    seen = set()
+    for r, case in enumerate(cases["colour"]):
+        p = case["params"]
+        assert case["rgb"].shape == (16, 3) and case["rgb"].dtype == np.uint8                       # any 48 bytes are a palette
+        assert case["lab1"].shape == case["lab2"].shape == (p["n"], 3) and case["lab1"].dtype == case["lab2"].dtype == np.float64
+        assert case["lab1"].flags.c_contiguous and case["lab2"].flags.c_contiguous
+        assert p["n"] in F.COUNTS or 100 <= p["n"] <= 700
+        # the two conditions of tests/colour_cases.py hold for what was kept, whatever was drawn again
+        assert colour_cases.knife_edges_kept(colour_cases.matrix_of(case["rgb"].tobytes())[0]), r
+        for a, b in zip(case["lab1"], case["lab2"]):
+            assert colour_cases.pair_allowed(tuple(a.tolist()), tuple(b.tolist())), r
+        assert p["palette"] == F.COLOUR_KINDS[r % 4] and p["different"] == len(np.unique(case["rgb"], axis=0))
+        if p["palette"] == "dark":
+            assert case["rgb"].max() <= 27
+        if p["palette"] == "greyish":
+            assert (case["rgb"].max(axis=1).astype(int) - case["rgb"].min(axis=1) <= 4).all()
+        if p["palette"] == "duplicates":
+            assert p["different"] < 16
+        seen |= {p["palette"], "one workgroup" if p["n"] <= 64 else "several workgroups", "own pairs" if p["own_pairs"] else "no own pairs"}
+        if p["n"] % 64:
+            seen.add("a last workgroup that is not full")
+    assert seen >= set(F.COLOUR_KINDS) | {"one workgroup", "several workgroups", "own pairs", "a last workgroup that is not full"}, seen
+    dark = np.concatenate([c["rgb"].reshape(-1) for c in cases["colour"] if c["params"]["palette"] == "dark"])
+    assert {10, 11, 23, 24} <= set(dark.tolist())                                                    # both segments' ends, both sides
+
+
+@pytest.mark.parametrize("stage", ["yuv", "direct", "chain_yuv", "colour"])
 def test_the_new_stages_reproduce_one_case_from_the_command_line(stage, monkeypatch):
     """python tests/stage_fuzz.py 1 SEED --stage STAGE --round R and IIV_STAGE_FUZZ_SIDE_STREAM=1 reach the new stages as the old
     ones: main() hands run() that one stage, that one round and the side-stream switch (run() itself needs a device)."""
