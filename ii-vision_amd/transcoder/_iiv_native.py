@@ -153,6 +153,11 @@ _SIGNATURES = {
     "iiv_frames_to_memory_maps_direct": (_i32, [_i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     # ---- f11: YUV 4:2:0 sources
     "iiv_resize_frames_yuv420": (_i32, [_i32, _i32, _i32, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _i32, _vp, _i32, _i32, _vp, _vp]),
+    # ---- f12: boxed resize, letterbox and crop
+    "iiv_resize_coeffs_box": (_i32, [_i32, _vp, _i32, C.POINTER(C.c_int), _vp, _vp]),
+    "iiv_resize_frames_fit": (_i32, [_i32, _i32, _i32, _vp, _sz, _sz, _vp, _i32, _i32, _vp, C.c_uint32, _vp, _vp]),
+    "iiv_resize_frames_yuv420_fit": (_i32, [_i32, _i32, _i32, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _i32, _vp, _vp, _i32, _i32, _vp,
+                                            C.c_uint32, _vp, _vp]),
 }
 SYMBOLS = list(_SIGNATURES)
 
@@ -1150,18 +1155,66 @@ def resize_coeffs(in_size, out_size):
     return bounds, k
 
 
-def resize_frames(rgb, size=RESIZE_SIZE, out=None):
+def resize_coeffs_box(in_size, in0, in1, out_size):
+    """resize_coeffs for the box [in0, in1) of an axis of in_size samples, as Pillow's Image.resize(box=) builds it
+    (include/iivision.h f12): in0 and in1 are rounded to float32 first.  Host only -> (bounds, coefficients)."""
+    box = np.array([in0, in1], np.float32)
+    ks = C.c_int(0)
+    check(lib().iiv_resize_coeffs_box(int(in_size), hptr(box), int(out_size), C.byref(ks), None, None))
+    bounds = np.zeros((int(out_size), 2), np.int32)
+    k = np.zeros((int(out_size), ks.value), np.int32)
+    check(lib().iiv_resize_coeffs_box(int(in_size), hptr(box), int(out_size), C.byref(ks), hptr(bounds), hptr(k)))
+    return bounds, k
+
+
+def fit_args(h, w, H, W, box=None, rect=None, fill=(0, 0, 0)):
+    """The three keywords of resize_frames / resize_frames_yuv420 as the C ABI takes them (include/iivision.h f12): None when
+    all three are at their defaults (the plain entry points), else (box float32 (4,), rect int32 (4,), fill r | g << 8 | b << 16)
+    with box = None the whole h x w frame and rect = None the whole H x W destination.  ValueError for a malformed keyword, a
+    box that is not 0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h as float32, or a rect that is not inside the destination."""
+    try:
+        f = tuple(int(c) for c in fill)
+        if len(f) != 3 or any(c < 0 or c > 255 or c != v for c, v in zip(f, fill)):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("fill is three integers 0..255 (r, g, b), got %r" % (fill,)) from None
+    if box is None and rect is None and f == (0, 0, 0):
+        return None
+    try:
+        b = np.array((0, 0, w, h) if box is None else box, dtype=np.float32)
+        if b.shape != (4,) or not np.isfinite(b).all():
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("box is four finite numbers (x0, y0, x1, y1), got %r" % (box,)) from None
+    if not (0 <= b[0] < b[2] <= w and 0 <= b[1] < b[3] <= h):
+        raise ValueError("box %s needs 0 <= x0 < x1 <= %d and 0 <= y0 < y1 <= %d (as float32)" % (tuple(float(v) for v in b), w, h))
+    try:
+        r = tuple(int(v) for v in ((0, 0, W, H) if rect is None else rect))
+        if len(r) != 4 or any(v != q for v, q in zip(r, (0, 0, W, H) if rect is None else rect)):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("rect is four integers (rx, ry, rw, rh), got %r" % (rect,)) from None
+    if r[0] < 0 or r[1] < 0 or r[2] < 1 or r[3] < 1 or r[0] + r[2] > W or r[1] + r[3] > H:
+        raise ValueError("rect %s must lie inside the %dx%d destination with rw, rh >= 1" % (r, W, H))
+    return b, np.array(r, np.int32), f[0] | f[1] << 8 | f[2] << 16
+
+
+def resize_frames(rgb, size=RESIZE_SIZE, out=None, box=None, rect=None, fill=(0, 0, 0)):
     """Image.resize((W, H), LANCZOS) of every frame, byte-exact: rgb CUDA uint8 (n, h, w, 3) with unit channel stride and
     pixel stride 3 (any frame and row strides: a crop or a letterbox cut is passed as a view) -> CUDA uint8 (n, H, W, 3).
     out: a contiguous CUDA uint8 tensor of n * H * W * 3 bytes to write into.  Asynchronous on torch's current stream once a
     size pair has been used on the device (the first call with it uploads its coefficient tables and synchronises); `rgb`
-    and `out` must stay alive and untouched until that stream has reached this call (as for frames_to_memory_maps)."""
+    and `out` must stay alive and untouched until that stream has reached this call (as for frames_to_memory_maps).
+    box, rect, fill (include/iivision.h f12, fit_args): the box (x0, y0, x1, y1) of each frame, in source pixels, is resized as
+    Image.resize((rw, rh), LANCZOS, box=box) into the rectangle rect = (rx, ry, rw, rh) of the destination, and the rest of the
+    destination is the colour fill = (r, g, b); all three at their defaults is the plain iiv_resize_frames."""
     torch = _torch()
     H, W = (int(v) for v in size)
     if not (rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 4 and rgb.shape[3] == 3 and rgb.stride(3) == 1
             and rgb.stride(2) == 3):
         raise ValueError("rgb must be a CUDA uint8 tensor (n, h, w, 3) with channel stride 1 and pixel stride 3")
     n, h, w = (int(v) for v in rgb.shape[:3])
+    fit = fit_args(h, w, H, W, box, rect, fill)
     if out is None:
         out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=rgb.device)
     else:
@@ -1169,8 +1222,12 @@ def resize_frames(rgb, size=RESIZE_SIZE, out=None):
         if out.numel() != n * H * W * 3:
             raise ValueError("out must hold n * %d * %d * 3 bytes" % (H, W))
     with torch.cuda.device(rgb.device):
-        check(lib().iiv_resize_frames(n, h, w, dptr(rgb), int(rgb.stride(0)), int(rgb.stride(1)), H, W, dptr(out),
-                                      stream_ptr()))
+        if fit is None:
+            check(lib().iiv_resize_frames(n, h, w, dptr(rgb), int(rgb.stride(0)), int(rgb.stride(1)), H, W, dptr(out),
+                                          stream_ptr()))
+        else:
+            check(lib().iiv_resize_frames_fit(n, h, w, dptr(rgb), int(rgb.stride(0)), int(rgb.stride(1)), hptr(fit[0]), H, W,
+                                              hptr(fit[1]), fit[2], dptr(out), stream_ptr()))
     return out
 
 
@@ -1201,12 +1258,13 @@ def _stride(t, dim, default):
     return int(t.stride(dim)) if int(t.shape[dim]) > 1 else default
 
 
-def resize_frames_yuv420(y, u, v, size=RESIZE_SIZE, matrix="bt601", out=None):
+def resize_frames_yuv420(y, u, v, size=RESIZE_SIZE, matrix="bt601", out=None, box=None, rect=None, fill=(0, 0, 0)):
     """resize_frames of the RGB frames that 4:2:0 planes define (include/iivision.h: iiv_resize_frames_yuv420), converted
     inside the resize's horizontal pass.  y: CUDA uint8 (n, h, w), unit pixel stride, any row and frame strides; u, v: CUDA
     uint8 (n, (h + 1) // 2, (w + 1) // 2) views with the same strides, pixel stride 1 (planar I420) or 2 (uv[..., 0] and
     uv[..., 1] of an (n, ch, cw, 2) NV12 tensor; swapped for NV21).  matrix: a name of YUV_MATRICES or (y_off, ky, rv, gu,
-    gv, bu).  -> CUDA uint8 (n, H, W, 3); out, and the asynchrony on torch's current stream, exactly as resize_frames."""
+    gv, bu).  -> CUDA uint8 (n, H, W, 3); out, and the asynchrony on torch's current stream, exactly as resize_frames.
+    box, rect, fill: as resize_frames', the box in pixels of the whole frame the planes define (odd offsets included)."""
     torch = _torch()
     H, W = (int(x) for x in size)
     m = yuv_matrix(matrix)
@@ -1224,13 +1282,17 @@ def resize_frames_yuv420(y, u, v, size=RESIZE_SIZE, matrix="bt601", out=None):
     c_fs = _stride(u, 0, _stride(v, 0, chroma[1] * c_rs))
     if (_stride(v, 2, ps), _stride(v, 1, c_rs), _stride(v, 0, c_fs)) != (ps, c_rs, c_fs):
         raise ValueError("u and v must have the same strides")
+    fit = fit_args(h, w, H, W, box, rect, fill)
     if out is None:
         out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=y.device)
     else:
         _cuda_u8(out, "out")
         if out.numel() != n * H * W * 3:
             raise ValueError("out must hold n * %d * %d * 3 bytes" % (H, W))
+    planes = (n, h, w, dptr(y), _stride(y, 0, h * _stride(y, 1, w)), _stride(y, 1, w), dptr(u), dptr(v), c_fs, c_rs, ps, hptr(m))
     with torch.cuda.device(y.device):
-        check(lib().iiv_resize_frames_yuv420(n, h, w, dptr(y), _stride(y, 0, h * _stride(y, 1, w)), _stride(y, 1, w), dptr(u), dptr(v),
-                                             c_fs, c_rs, ps, hptr(m), H, W, dptr(out), stream_ptr()))
+        if fit is None:
+            check(lib().iiv_resize_frames_yuv420(*planes, H, W, dptr(out), stream_ptr()))
+        else:
+            check(lib().iiv_resize_frames_yuv420_fit(*planes, hptr(fit[0]), H, W, hptr(fit[1]), fit[2], dptr(out), stream_ptr()))
     return out

@@ -15,6 +15,7 @@ reference's source, so its output cannot be matched: the conversion is specified
 include/iivision.h (iiv_frames_to_memory_maps) and the tests hold the kernel to it.
 """
 
+from fractions import Fraction
 from typing import Iterator, Tuple
 
 import numpy as np
@@ -46,6 +47,53 @@ DIFFUSION_KERNELS = {
 # 4:2:0 YCbCr -> RGB by name: (y_off, ky, rv, gu, gv, bu) of include/iivision.h f11 (the one table; native holds it because
 # native.resize_frames_yuv420 takes the names too).  ArrayFrameGrabber((y, u, v), ..., resize=True, yuv_matrix=<name or tuple>).
 YUV_MATRICES = native.YUV_MATRICES
+
+
+FITS = ("stretch", "letterbox", "crop")
+
+
+def _float32(q):
+    """the float32 nearest the rational q (ties to even), as a Python float: from q itself, not from its float64 rounding"""
+    near = np.float32(float(q))
+    best = min((near, np.nextafter(near, np.float32(-np.inf)), np.nextafter(near, np.float32(np.inf))),
+               key=lambda c: (abs(Fraction(float(c)) - q), c != near))
+    return float(best)
+
+
+def fit_geometry(h, w, H, W, fit, sar=(1, 1)):
+    """How an h x w source with pixel aspect ratio sar = (num, den) goes onto the H x W screen -> (box, rect) for
+    native.resize_frames(box=, rect=) (include/iivision.h f12).  The full screen is a 4:3 picture whatever H
+    and W are (280 and 560 dots across show the same picture), so only the source's display aspect w sar / h against 4:3
+    counts.  Rationals throughout; the box is rounded to float32, as Pillow holds it, at the very end.
+      "stretch"    the whole frame over the whole screen: the reference's resize((280, 192))
+      "letterbox"  the whole frame into a centred rectangle of its own display aspect, as large as fits: the side that does not
+                   fill the screen is rounded half up -- a width to the nearest even number, so that no colour pixel (two dots)
+                   is split --, at least 1 (a width: 2), and centred with the odd pixel, if any, on the far side
+      "crop"       the centred box of display aspect 4:3, as large as fits, over the whole screen
+    A source that is 4:3 on display gets the whole frame and the whole screen whatever `fit` is."""
+    h, w, H, W = int(h), int(w), int(H), int(W)
+    sn, sd = (int(v) for v in sar)
+    if fit not in FITS:
+        raise ValueError("fit must be one of %s, got %r" % (", ".join(FITS), fit))
+    if min(h, w, H, W) < 1 or sn < 1 or sd < 1:
+        raise ValueError("sizes and both terms of sar must be positive")
+    display = Fraction(w * sn, h * sd)
+    screen_aspect = Fraction(4, 3)
+    box = (Fraction(0), Fraction(0), Fraction(w), Fraction(h))
+    rect = (0, 0, W, H)
+    if fit == "letterbox" and display > screen_aspect:     # bars above and below
+        rh = max(int(Fraction(H) * screen_aspect / display + Fraction(1, 2)), 1)
+        rect = (0, (H - rh) // 2, W, rh)
+    elif fit == "letterbox" and display < screen_aspect:   # bars left and right
+        rw = min(max(2 * int(Fraction(W) * display / screen_aspect / 2 + Fraction(1, 2)), 2), W)
+        rect = ((W - rw) // 2, 0, rw, H)
+    elif fit == "crop" and display > screen_aspect:        # the sides go
+        bw = Fraction(w) * screen_aspect / display
+        box = ((w - bw) / 2, Fraction(0), (w + bw) / 2, Fraction(h))
+    elif fit == "crop" and display < screen_aspect:        # top and bottom go
+        bh = Fraction(h) * display / screen_aspect
+        box = (Fraction(0), (h - bh) / 2, Fraction(w), (h + bh) / 2)
+    return tuple(_float32(q) for q in box), rect
 
 
 class FrameGrabber:
@@ -86,11 +134,19 @@ class ArrayFrameGrabber(FrameGrabber):
     Frames as a decoder delivers them: a (y, u, v) triple of uint8 arrays, y (n, h, w) and u, v (n, (h + 1) // 2, (w + 1) // 2) --
     planar I420, or uv[..., 0] and uv[..., 1] of an interleaved (n, ch, cw, 2) NV12 array, which is uploaded as it is --, with
     resize=True and yuv_matrix a name of YUV_MATRICES or (y_off, ky, rv, gu, gv, bu): converted inside the device resize
-    (iiv_resize_frames_yuv420); frames that already have the target size go through the same call."""
+    (iiv_resize_frames_yuv420); frames that already have the target size go through the same call.
+    fit, sar, fill (with resize=True; fit_geometry): "stretch" -- the default, the reference's resize and today's
+    bytes -- pulls every source over the whole screen; "letterbox" keeps the whole frame and pads the screen with the colour
+    fill = (r, g, b); "crop" fills the screen with the frame's centred 4:3 part; sar = the source's pixel aspect ratio (num, den)."""
 
     def __init__(self, frames_rgb, mode: VideoMode, palette: Palette = Palette.NTSC, dither=32,
-                 input_frame_rate: float = 30, batch: int = 256, resize: bool = False, amplitude: int = 0, yuv_matrix="bt601"):
+                 input_frame_rate: float = 30, batch: int = 256, resize: bool = False, amplitude: int = 0, yuv_matrix="bt601",
+                 fit: str = "stretch", sar=(1, 1), fill=(0, 0, 0)):
         super().__init__(mode)
+        if fit not in FITS:
+            raise ValueError("fit must be one of %s, got %r" % (", ".join(FITS), fit))
+        if fit != "stretch" and not resize:
+            raise ValueError("fit=%r is the device resize's: pass resize=True" % (fit,))
         self._yuv = None
         if isinstance(frames_rgb, tuple) and len(frames_rgb) == 3:
             if not resize:
@@ -118,6 +174,13 @@ class ArrayFrameGrabber(FrameGrabber):
                 " (one pixel per dot of a monochrome screen)" if palette == Palette.MONO else " (frame_grabber.py:75: 280x192 RGB)",)))
         self._rgb = rgb
         self.resize = bool(resize)
+        self.fit = fit
+        # (box, rect, fill) for the resize, or {} where the plain stretch does it
+        self._fit = {}
+        if fit != "stretch":
+            box, rect = fit_geometry(rgb.shape[1], rgb.shape[2], self.frame_size[0], self.frame_size[1], fit, sar)
+            native.fit_args(rgb.shape[1], rgb.shape[2], self.frame_size[0], self.frame_size[1], box, rect, fill)   # (refuses a bad fill now)
+            self._fit = dict(box=box, rect=rect, fill=tuple(int(c) for c in fill))
         self.palette = palette
         # 0..255: amplitude of the 4x4 ordered dither; "diffusion" (= native.DITHER_DIFFUSION): Floyd-Steinberg error
         # diffusion, the kind of dither the reference asks bmp2dhr for (D9, frame_grabber.py:80-82,106-108)
@@ -155,10 +218,10 @@ class ArrayFrameGrabber(FrameGrabber):
             y, u, v = (p[first:first + count] for p in self._yuv)
             d_u, d_v = _upload_chroma(torch, u, v)
             return native.resize_frames_yuv420(torch.from_numpy(np.ascontiguousarray(y)).cuda(), d_u, d_v, size=self.frame_size,
-                                               matrix=self._matrix)
+                                               matrix=self._matrix, **self._fit)
         rgb = torch.from_numpy(np.ascontiguousarray(self._rgb[first:first + count])).cuda()
-        if self.resize and tuple(rgb.shape[1:3]) != self.frame_size:
-            rgb = native.resize_frames(rgb, size=self.frame_size)   # on the same stream as the conversion behind it
+        if self.resize and (self._fit or tuple(rgb.shape[1:3]) != self.frame_size):
+            rgb = native.resize_frames(rgb, size=self.frame_size, **self._fit)   # on the same stream as the conversion behind it
         return rgb
 
     def memory_maps(self, first=0, count=None):

@@ -831,6 +831,43 @@ int iiv_resize_frames_yuv420(int n, int h, int w, const uint8_t *d_y, size_t y_f
                              const uint8_t *d_u, const uint8_t *d_v, size_t c_frame_stride, size_t c_row_stride, int c_pixel_stride,
                              const int32_t matrix[6], int H, int W, uint8_t *d_dst, void *stream);
 
+/* ==== f12: fitting a frame to the screen: boxed resize, letterbox and crop ======
+ * f5 stretches every source over the whole destination.  These entry points resize a BOX of the source into a RECTANGLE of the
+ * destination and give the rest of the destination a fill colour, byte for byte as Pillow's
+ * Image.resize((rw, rh), LANCZOS, box=(x0, y0, x1, y1)) pasted at (rx, ry) onto a canvas of the fill colour (DESIGN.md 28;
+ * tests/fit_model.py restates it; observed on Pillow 12.2.0).  What the box changes in f5, per axis (in = the frame's size on
+ * that axis, in0 / in1 = the box's ends, out = rw or rh):
+ *   1. the box is four float32 values: anything wider is rounded to float32 first;
+ *   2. scale = (double)(in1 - in0) / out, the subtraction IN FLOAT32 and only then widened;
+ *   3. center = in0 + (xx + 0.5) scale in float64 (in0 the float32 value widened); filterscale, support, ksize, the weights,
+ *      their normalisation and the 22-bit rounding as in f5 with that scale; xmin is clamped at 0 and xmin + count at `in`,
+ *      the FRAME's size, not at the box: taps reach past the box into the picture around it;
+ *   4. an axis gets a pass when out != in or in0 != 0 or in1 != in; the horizontal pass comes first, the vertical one when the
+ *      frame (not the box) has h > 100 w; an integer-aligned box of the rectangle's own size yields identity coefficients (Pillow
+ *      crops; the pass gives the same bytes).
+ * box = (x0, y0, x1, y1) with 0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h as float32 (an empty box, which Pillow accepts, is
+ * refused); rect = (rx, ry, rw, rh) inside the H x W destination with rw, rh >= 1; fill = r | g << 8 | b << 16 (< 2^24); any
+ * other value is IIV_ERR_INVALID before anything is launched.  box = (0, 0, w, h) with rect = (0, 0, W, H) is f5 itself, byte
+ * for byte.  Only the source columns and rows that the two tables touch are read.  Limits, the stream contract and the
+ * stream-ordered scratch are iiv_resize_frames' own; the coefficient cache is keyed by (device, in, bits of in0, bits of in1, out)
+ * and serves all four entry points: the FIRST call with a geometry on a device is synchronous, every later one asynchronous. */
+
+/* iiv_resize_coeffs for the box [in_box[0], in_box[1]) of an axis of in_size samples (rules 1 to 3), host only (no device).
+ * 0 <= in_box[0] < in_box[1] <= in_size, else IIV_ERR_INVALID.  in_box = (0, in_size) gives iiv_resize_coeffs' table. */
+int iiv_resize_coeffs_box(int in_size, const float in_box[2], int out_size, int *ksize, int32_t *bounds, int32_t *coeffs);
+
+/* iiv_resize_frames of the box into the rectangle: d_dst [n][H][W][3] contiguous holds, inside rect, the boxed resize of source
+ * frame f and the fill colour everywhere else (nothing extra is launched when rect is the whole destination). */
+int iiv_resize_frames_fit(int n, int h, int w, const uint8_t *d_src, size_t frame_stride, size_t row_stride, const float box[4],
+                          int H, int W, const int rect[4], uint32_t fill, uint8_t *d_dst, void *stream);
+
+/* The same for 4:2:0 planes (f11): the planes define an RGB frame over the WHOLE h x w source, chroma taken at (y >> 1, x >> 1)
+ * of absolute source coordinates, and the box is applied to that frame -- an odd x0 or y0 is well defined. */
+int iiv_resize_frames_yuv420_fit(int n, int h, int w, const uint8_t *d_y, size_t y_frame_stride, size_t y_row_stride,
+                                 const uint8_t *d_u, const uint8_t *d_v, size_t c_frame_stride, size_t c_row_stride,
+                                 int c_pixel_stride, const int32_t matrix[6], const float box[4], int H, int W, const int rect[4],
+                                 uint32_t fill, uint8_t *d_dst, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,10 @@ after each source frame's opcodes, drawn on the device from the encoder's own sc
 --quality FILE.json: also measure that screen against the frame that went into the ingest (after any resize: 280 wide, 560
 for --palette MONO in DHGR), on the device (csrc/iiv_render_error.hip): per source frame the nine exact sums of
 squared differences [level][channel] -- per dot, per quad of four dots, per unit of sixteen -- and the overall PSNR of each
-level (screen.psnr).  The .a2m bytes and the --preview array are the same with and without it."""
+level (screen.psnr).  The .a2m bytes and the --preview array are the same with and without it.
+--fit letterbox / crop (with --sar N:D, --fill R,G,B): a source that is not 4:3 on display keeps its shape -- whole, between bars of
+the fill colour, or cropped to its centred 4:3 part (frame_grabber.fit_geometry) -- instead of being stretched over the
+screen as the reference does; --preview shows it and --quality measures against the fitted frame, the one the ingest saw."""
 import argparse
 import os
 import sys
@@ -81,6 +84,11 @@ def main():
     ap.add_argument("--size", help="with --yuv: WxH of its frames")
     ap.add_argument("--pix-fmt", choices=["yuv420p", "nv12"], default="yuv420p", help="with --yuv: the file's layout")
     ap.add_argument("--yuv-matrix", choices=["bt601", "bt709", "jpeg"], default="bt601", help="with --yuv: YCbCr -> RGB (frame_grabber.YUV_MATRICES)")
+    ap.add_argument("--fit", choices=["stretch", "letterbox", "crop"], default="stretch",
+                    help="how a source that is not 4:3 goes onto the 4:3 screen (frame_grabber.fit_geometry): stretched over it (the "
+                         "reference), whole between bars, or its centred 4:3 part; --synthetic is then a 16:9 card, 192x341")
+    ap.add_argument("--sar", default="1:1", metavar="N:D", help="with --fit: the source's pixel aspect ratio")
+    ap.add_argument("--fill", default="0,0,0", metavar="R,G,B", help="with --fit letterbox: the bars' colour")
     ap.add_argument("--out", required=True)
     ap.add_argument("--mode", choices=["DHGR", "HGR"], default="DHGR")
     ap.add_argument("--palette", choices=["NTSC", "IIGS", "MONO"], default="NTSC",
@@ -114,6 +122,13 @@ def main():
         ap.error("one of --audio / --pcm")
     if bool(a.pcm) != bool(a.rate):
         ap.error("--pcm needs --rate (and --rate goes with --pcm)")
+    try:
+        sar = tuple(int(v) for v in a.sar.split(":"))
+        fill = tuple(int(v) for v in a.fill.split(","))
+        if len(sar) != 2 or min(sar) < 1 or len(fill) != 3 or min(fill) < 0 or max(fill) > 255:
+            raise ValueError
+    except ValueError:
+        ap.error("--sar N:D with positive integers, --fill R,G,B with 0..255")
 
     import torch
     import _iiv_native as native
@@ -126,11 +141,11 @@ def main():
 
     mode = native.DHGR if a.mode == "DHGR" else native.HGR
     pal_id = palette.Palette[a.palette]
-    rgb = read_yuv(a.yuv, a.size, a.pix_fmt) if a.yuv else np.load(a.frames) if a.frames else test_card(a.synthetic, native.MONO_SIZE[mode][1] if pal_id == palette.Palette.MONO else 280)
+    rgb = read_yuv(a.yuv, a.size, a.pix_fmt) if a.yuv else np.load(a.frames) if a.frames else test_card(a.synthetic, 341 if a.fit != "stretch" else native.MONO_SIZE[mode][1] if pal_id == palette.Palette.MONO else 280)
     t0 = time.perf_counter()
     grab = frame_grabber.ArrayFrameGrabber(rgb, video_mode.VideoMode[a.mode], pal_id,
                                            dither=int(a.dither) if a.dither.isdigit() else a.dither, resize=True,
-                                           amplitude=a.amplitude, yuv_matrix=a.yuv_matrix)
+                                           amplitude=a.amplitude, yuv_matrix=a.yuv_matrix, fit=a.fit, sar=sar, fill=fill)
     main_maps, aux_maps = grab.memory_maps()                       # (n, 32, 256) on the device
     dm = palette.diff_matrix(pal_id)                               # CIE2000 of the palette's colours; MONO: the dot distance
     table = native.build_table(mode, dm, True)
