@@ -25,8 +25,11 @@
 //     s = 15 + ceil(log2 divisor), M = ceil(2^s / divisor): checked here for every divisor over the whole range before the
 //     first launch (div_table), and in tests/test_diffusion_model.py.
 // Integer sums commute, so the schedule changes nothing: the result is the raster-order definition bit for bit.
-// The palette's linear forms, the arg-min and the screen-hole kernel are restated from iiv_ingest.hip rather than shared
-// with it: that file's kernels are to stay instruction for instruction what they are.
+// The palette's linear forms, the arg-min over them, mean_of and the screen-hole launch are
+// iiv_frontend.h's, shared with iiv_ingest.hip; both files' kernels compile to the instructions they had with a copy each
+// (profiles/frontend_isa_identity.txt).  The staged source stream below is still spelt here as it is there: as one shared
+// type it did not compile to the same code (the same record).
+#include "iiv_frontend.h"
 #include "iiv_host.h"
 #include "iiv_stream.h"
 #include <type_traits>
@@ -34,33 +37,8 @@
 namespace iiv {
 namespace diffuse {
 
-__device__ __host__ static inline int y_to_offset(int y)  // y_to_base_addr(y, 0) - 0x2000 (screen.py:16-22)
-{
-    return 1024 * (y % 8) + 128 * ((y % 64) / 8) + 40 * (y / 64);
-}
-
-// The palette as the kernel uses it (iiv_ingest.hip: IngestPalette): key_c = 16 (K_c - 4 R_c r - 8 G_c g - 6 B_c b) + c
-struct Palette {
-    int32_t k[16];        // 16 (2 R^2 + 4 G^2 + 3 B^2) + colour value
-    int32_t a[16], b[16], c[16];   // -16 * 4 R, -16 * 8 G, -16 * 6 B
-    uint32_t bc[16];      // the last two as a pair of 16-bit halves: v_dot2c_i32_i16's operand
-    uint32_t rgb[16];     // R | G << 8 | B << 16
-};
-
-static Palette make_palette(const uint8_t pal[48])
-{
-    Palette p;
-    for (int c = 0; c < 16; c++) {
-        const int R = pal[3 * c], G = pal[3 * c + 1], B = pal[3 * c + 2];
-        p.k[c] = 16 * (2 * R * R + 4 * G * G + 3 * B * B) + c;
-        p.a[c] = -64 * R;
-        p.b[c] = -128 * G;
-        p.c[c] = -96 * B;
-        p.bc[c] = (uint32_t)(uint16_t)(int16_t)(-128 * G) | ((uint32_t)(uint16_t)(int16_t)(-96 * B) << 16);
-        p.rgb[c] = (uint32_t)R | ((uint32_t)G << 8) | ((uint32_t)B << 16);
-    }
-    return p;
-}
+// The palette as the kernel takes it: the linear forms alone.  (A type of its own name: the kernel's symbol carries it.)
+struct Palette : PaletteForms {};
 
 // The diffusion kernel as the device kernel takes it: wave-uniform, by value
 struct Weights {
@@ -99,55 +77,6 @@ static DivTable make_div_table()
     return t;
 }
 
-struct Kv {
-    int k[16];
-};
-__device__ static inline Kv kv_of(const Palette &P)   // the sixteen K_c in vector registers (iiv_ingest.hip: IngestKv)
-{
-    Kv v;
-#pragma unroll
-    for (int c = 0; c < 16; c++) {
-        v.k[c] = P.k[c];
-        asm volatile("" : "+v"(v.k[c]));
-    }
-    return v;
-}
-
-typedef short v2s __attribute__((ext_vector_type(2)));
-__device__ static inline int dist_key(const Palette &P, int kc, int c, int r, v2s gb)
-{
-    return __builtin_amdgcn_sdot2(gb, __builtin_bit_cast(v2s, P.bc[c]), __mul24(r, P.a[c]) + kc, false);
-}
-// DHGR: the nearest of the sixteen colours, ties to the lower colour value: three rounds of sixteen independent multiply-adds
-// (iiv_ingest.hip: nearest16_mad, and why not the dot form here)
-__device__ static inline int nearest16_mad(const Palette &P, const Kv &kv, int r, int g, int b)
-{
-    int t[16];
-#pragma unroll
-    for (int c = 0; c < 16; c++) t[c] = __mul24(r, P.a[c]) + kv.k[c];
-    asm("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]), "+v"(t[8]), "+v"(t[9]),
-             "+v"(t[10]), "+v"(t[11]), "+v"(t[12]), "+v"(t[13]), "+v"(t[14]), "+v"(t[15]));
-#pragma unroll
-    for (int c = 0; c < 16; c++) t[c] = __mul24(g, P.b[c]) + t[c];
-    asm("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]), "+v"(t[8]), "+v"(t[9]),
-             "+v"(t[10]), "+v"(t[11]), "+v"(t[12]), "+v"(t[13]), "+v"(t[14]), "+v"(t[15]));
-    int m = 0x7fffffff;
-#pragma unroll
-    for (int c = 0; c < 16; c++) m = min(m, __mul24(b, P.c[c]) + t[c]);
-    return m & 15;
-}
-
-__global__ __launch_bounds__(256) void holes_kernel(int n_banks, uint8_t *__restrict__ main_mem, uint8_t *__restrict__ aux_mem)
-{
-    // the screen holes of every page (offsets 120..127, 248..255) start as zero
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;   // one 8-byte hole each: 64 per bank
-    if (i >= (size_t)n_banks * 64) return;
-    const size_t bank = i >> 6;
-    const int h = (int)(i & 63);
-    uint8_t *base = (aux_mem && (bank & 1)) ? aux_mem + (bank >> 1) * 8192 : main_mem + (aux_mem ? bank >> 1 : bank) * 8192;
-    *reinterpret_cast<uint2 *>(base + (h >> 1) * 256 + ((h & 1) ? 248 : 120)) = make_uint2(0, 0);
-}
-
 constexpr int kWaves = 2;        // waves per block
 constexpr int kRows = 20;        // rows of a frame a wave works on at a time: 19 x 7 = 133 < 140, a lane goes on to row r + 20 without waiting
 constexpr int kFrames = 3;       // frames per wave: 3 x 20 lanes, 4 idle
@@ -175,7 +104,7 @@ __global__ __launch_bounds__(64 * kWaves, 3) void ingest_diffused_kernel(int n, 
     int (*ring)[8] = ring_s[wv][slot3 < kFrames ? slot3 : 0];
     const uint8_t *frame = rgb_frames + (lane_ok ? f : 0) * (size_t)(192 * 280 * 3);
     const Kv kv = MODE == kDHGR ? kv_of(P) : Kv{};
-    // HGR: the six colours it can show, their K in vector registers
+    // HGR: the six colours it can show, their K in vector registers (iiv_frontend.h: Kv)
     int kv0 = P.k[0], kv3 = P.k[3], kv12 = P.k[12], kv15 = P.k[15], kv6 = P.k[6], kv9 = P.k[9];
     asm volatile("" : "+v"(kv0), "+v"(kv3), "+v"(kv12), "+v"(kv15), "+v"(kv6), "+v"(kv9));
     struct F6 {
@@ -197,14 +126,6 @@ __global__ __launch_bounds__(64 * kWaves, 3) void ingest_diffused_kernel(int n, 
     uint32_t cur[11], nxt[11];            // the source bytes of the current / next 7-pixel group, funnel-shifted to start at byte 0
     int pbA = 0, pbB = 0;
     uint32_t bytesAB = 0;                 // HGR: the two screen bytes of the group, as they fill; DHGR: its 28 dots
-    // mean of the two source pixels of group pixel GP, three channels in one v_lerp_u8: bytes 6 GP .. 6 GP + 5 of cur
-    auto mean_of = [&](auto GPc) -> uint32_t {
-        constexpr int GP = decltype(GPc)::value;
-        constexpr int oa = 6 * GP, ob = 6 * GP + 3;
-        const uint32_t A = (oa & 3) ? __builtin_amdgcn_alignbit(cur[(oa >> 2) + 1], cur[oa >> 2], (oa & 3) * 8) : cur[oa >> 2];
-        const uint32_t B = (ob & 3) ? __builtin_amdgcn_alignbit(cur[(ob >> 2) + 1 > 10 ? 10 : (ob >> 2) + 1], cur[ob >> 2], (ob & 3) * 8) : cur[ob >> 2];
-        return __builtin_amdgcn_lerp(A, B, 0x01010101u);
-    };
     auto quot = [&](int acc) -> int {     // floor(acc / divisor), |acc| <= 255 x 64
         return (int)(__umul24((uint32_t)(acc + W.bias), W.mul) >> W.shift) - W.bias_q;
     };
@@ -323,7 +244,7 @@ __global__ __launch_bounds__(64 * kWaves, 3) void ingest_diffused_kernel(int n, 
         int e[3] = {0, 0, 0};
         if (active) {
             int r, g, b;
-            value_of(mean_of(Pc), Aq[PH][0] + __mul24(W.r1, z1[0]) + __mul24(W.r2, z2[0]), Aq[PH][1] + __mul24(W.r1, z1[1]) + __mul24(W.r2, z2[1]),
+            value_of(mean_of<PH>(cur), Aq[PH][0] + __mul24(W.r1, z1[0]) + __mul24(W.r2, z2[0]), Aq[PH][1] + __mul24(W.r1, z1[1]) + __mul24(W.r2, z2[1]),
                      Aq[PH][2] + __mul24(W.r1, z1[2]) + __mul24(W.r2, z2[2]), r, g, b);
             if constexpr (MODE == kDHGR) {
                 // the nearest of the sixteen colours; its value IS the pixel's dot quad
@@ -351,9 +272,9 @@ __global__ __launch_bounds__(64 * kWaves, 3) void ingest_diffused_kernel(int n, 
                         constexpr int Q = decltype(Qc)::value;
                         int r2, g2, b2;
                         if (Q == PH + 1)
-                            value_of(mean_of(Qc), Aq[Q][0] + __mul24(W.r2, z1[0]), Aq[Q][1] + __mul24(W.r2, z1[1]), Aq[Q][2] + __mul24(W.r2, z1[2]), r2, g2, b2);
+                            value_of(mean_of<Q>(cur), Aq[Q][0] + __mul24(W.r2, z1[0]), Aq[Q][1] + __mul24(W.r2, z1[1]), Aq[Q][2] + __mul24(W.r2, z1[2]), r2, g2, b2);
                         else
-                            value_of(mean_of(Qc), Aq[Q][0], Aq[Q][1], Aq[Q][2], r2, g2, b2);
+                            value_of(mean_of<Q>(cur), Aq[Q][0], Aq[Q][1], Aq[Q][2], r2, g2, b2);
                         const F6 fa = f6(r2, g2, b2);
                         s0 += __mul24(w, min(min(fa.f0, fa.f3), min(fa.f12, fa.f15)));   // (|f| < 2^21)
                         s1 += __mul24(w, min(min(fa.f0, fa.f6), min(fa.f9, fa.f15)));
@@ -454,11 +375,8 @@ __global__ __launch_bounds__(64 * kWaves, 3) void ingest_diffused_kernel(int n, 
 static int frames_to_memory_maps_diffused(int mode, const uint8_t palette_rgb[48], int n, const uint8_t *d_rgb, const Weights &W,
                                           uint8_t *d_main, uint8_t *d_aux, hipStream_t st)
 {
-    const Palette P = make_palette(palette_rgb);
-    const int n_banks = mode == kDHGR ? 2 * n : n;
-    if (int rc = launch(holes_kernel, "diffuse holes_kernel launch", dim3((unsigned)(((size_t)n_banks * 64 + 255) / 256)), dim3(256), 0, st,
-                        n_banks, d_main, mode == kDHGR ? d_aux : (uint8_t *)nullptr))
-        return rc;
+    const Palette P{make_palette_forms(palette_rgb)};
+    if (int rc = zero_screen_holes(mode, n, d_main, d_aux, st)) return rc;
     const dim3 grid((unsigned)((n + kFrames * kWaves - 1) / (kFrames * kWaves)));
     return launch(by_mode(mode, ingest_diffused_kernel<kDHGR>, ingest_diffused_kernel<kHGR>), "ingest_diffused_kernel launch", grid,
                   dim3(64 * kWaves), 0, st, n, d_rgb, P, W, d_main, d_aux);

@@ -22,6 +22,7 @@
 //     sum); the call zeroes the sums on the stream in front of the kernel.  The screen holes are written by the frame's
 //     first 64 rows.
 // No allocation, no scratch (profiles/direct_resource_usage.txt), no barrier.
+#include "iiv_frontend.h"
 #include "iiv_render.h"
 #include <utility>
 
@@ -37,13 +38,12 @@ struct DirectPalette {
 
 static DirectPalette make_direct_palette(const uint8_t pal[48], int dither)
 {
-    static const int bayer[16] = {0, 8, 2, 10, 12, 4, 14, 6, 3, 11, 1, 9, 15, 7, 13, 5};
     DirectPalette p;
+    dither_offsets(dither, p.dither);
     for (int v = 0; v < 16; v++) {
         const int R = pal[3 * v], G = pal[3 * v + 1], B = pal[3 * v + 2];
         p.k[v] = R * R + G * G + B * B;
         p.r[v] = -2 * R, p.g[v] = -2 * G, p.b[v] = -2 * B;
-        p.dither[v] = ((2 * bayer[v] - 15) * dither + 16 * 256) / 16 - 256;   // floor towards minus infinity
     }
     return p;
 }

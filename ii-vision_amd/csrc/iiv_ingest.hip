@@ -23,6 +23,7 @@
 //     period, so HGR's palette-bit decisions and the stores are uniform and phase-indexed state is static.
 //   * No allocation, no synchronisation: the palette's linear forms travel as a kernel argument, the screen
 //     holes are zeroed by a kernel on the same stream.
+#include "iiv_frontend.h"
 #include "iiv_host.h"
 #include "iiv_stream.h"
 #include <stdlib.h>
@@ -30,112 +31,20 @@
 
 namespace iiv {
 
-__device__ __host__ static inline int y_to_offset(int y)  // y_to_base_addr(y, 0) - 0x2000 (screen.py:16-22)
-{
-    return 1024 * (y % 8) + 128 * ((y % 64) / 8) + 40 * (y / 64);
-}
-
-// The palette as the kernels use it (built on the host per call, passed by value).
-struct IngestPalette {
-    int32_t k[16];        // 16 (2 R^2 + 4 G^2 + 3 B^2) + colour value
-    int32_t a[16], b[16], c[16];   // -16 * 4 R, -16 * 8 G, -16 * 6 B
-    uint32_t bc[16];      // the last two as a pair of 16-bit halves (both fit: 128 x 255, 96 x 255 < 2^15): v_dot2c_i32_i16's operand
-    uint32_t rgb[16];     // R | G << 8 | B << 16
-    int32_t dither[16];   // ordered-dither offset of (y & 3) * 4 + (k & 3): floor((2 Bayer - 15) * amplitude / 16)
+// The palette as the kernels use it (built on the host per call, passed by value): its linear forms (iiv_frontend.h, with the
+// arg-min over them) and the ordered dither's table
+struct IngestPalette : PaletteForms {
+    int32_t dither[16];   // ordered-dither offset of (y & 3) * 4 + (k & 3): floor((2 Bayer - 15) * amplitude / 16); error diffusion: 0
 };
 
 static IngestPalette make_palette(const uint8_t pal[48], int dither)
 {
-    static const int bayer[16] = {0, 8, 2, 10, 12, 4, 14, 6, 3, 11, 1, 9, 15, 7, 13, 5};
-    IngestPalette p;
-    for (int c = 0; c < 16; c++) {
-        const int R = pal[3 * c], G = pal[3 * c + 1], B = pal[3 * c + 2];
-        p.k[c] = 16 * (2 * R * R + 4 * G * G + 3 * B * B) + c;
-        p.a[c] = -64 * R;
-        p.b[c] = -128 * G;
-        p.c[c] = -96 * B;
-        p.bc[c] = (uint32_t)(uint16_t)(int16_t)(-128 * G) | ((uint32_t)(uint16_t)(int16_t)(-96 * B) << 16);
-        p.rgb[c] = (uint32_t)R | ((uint32_t)G << 8) | ((uint32_t)B << 16);
-        p.dither[c] = dither == IIV_DITHER_DIFFUSION ? 0 : ((2 * bayer[c] - 15) * dither + 16 * 256) / 16 - 256;
-    }
+    IngestPalette p{make_palette_forms(pal), {}};
+    if (dither != IIV_DITHER_DIFFUSION) dither_offsets(dither, p.dither);
     return p;
 }
 
-// The sixteen K_c in vector registers: a VOP3 instruction reads ONE scalar register, so mad(r, A_c, K_c) with both constants
-// in SGPRs costs a v_mov besides -- with K_c in a VGPR a colour is exactly three v_mad_i32_i24 (the compiler otherwise
-// builds it from two multiplies, a multiply-add and a three-operand add plus the moves: 4.5 instructions and 2.6 moves)
-struct IngestKv {
-    int k[16];
-};
-__device__ static inline IngestKv ingest_kv(const IngestPalette &P)
-{
-    IngestKv v;
-#pragma unroll
-    for (int c = 0; c < 16; c++) {
-        v.k[c] = P.k[c];
-        asm volatile("" : "+v"(v.k[c]));
-    }
-    return v;
-}
-
-// key of colour c for the pixel (r, g, b) = 16 * (distance - the term common to all colours) + c
-//     = (K_c + r * (-64 R_c)) + (g, b) . (-128 G_c, -96 B_c):
-// a v_mad_i32_i24 into a fresh register and a v_dot2c_i32_i16 that accumulates in place (16-bit pairs, exact 32-bit sum; g, b
-// are clamped to 0..255, the coefficients fit 16 bits) -- two instructions instead of three multiply-adds.  (Both products
-// in dot form, (r, g) . (..) + (b, 0) . (..), compile to the accumulate-in-place form too and then need a copy of K_c each:
-// three again.)  DHGR: the nearest of the sixteen colours (ties to the lower colour value).
-typedef short ingest_v2s __attribute__((ext_vector_type(2)));
-__device__ static inline int dist_key(const IngestPalette &P, int kc, int c, int r, ingest_v2s gb)
-{
-    return __builtin_amdgcn_sdot2(gb, __builtin_bit_cast(ingest_v2s, P.bc[c]), __mul24(r, P.a[c]) + kc, false);
-}
-__device__ static inline int nearest16(const IngestPalette &P, const IngestKv &kv, int r, int g, int b)
-{
-    const ingest_v2s gb = __builtin_bit_cast(ingest_v2s, (uint32_t)g | ((uint32_t)b << 16));
-    int m = 0x7fffffff;
-#pragma unroll
-    for (int c = 0; c < 16; c++) m = min(m, dist_key(P, kv.k[c], c, r, gb));
-    return m & 15;
-}
-// The same with three v_mad_i32_i24 per colour, for the error-diffusion kernel: a lane's pixels there are one dependent chain,
-// and the wait states between a v_dot2c and the minimum that reads it cost that kernel more (1.6 %, same-box A/B) than the
-// sixteen instructions save.  Three rounds of sixteen independent multiply-adds with ONE compiler barrier between rounds (the
-// barrier keeps the compiler from re-associating a colour's chain into mad + 2 mul + add3; one asm statement per round rather
-// than per colour, because the hazard recogniser puts an s_nop behind every inline-asm statement)
-__device__ static inline int nearest16_mad(const IngestPalette &P, const IngestKv &kv, int r, int g, int b)
-{
-    int t[16];
-#pragma unroll
-    for (int c = 0; c < 16; c++) t[c] = __mul24(r, P.a[c]) + kv.k[c];
-    asm("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]), "+v"(t[8]), "+v"(t[9]),
-             "+v"(t[10]), "+v"(t[11]), "+v"(t[12]), "+v"(t[13]), "+v"(t[14]), "+v"(t[15]));
-#pragma unroll
-    for (int c = 0; c < 16; c++) t[c] = __mul24(g, P.b[c]) + t[c];
-    asm("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]), "+v"(t[8]), "+v"(t[9]),
-             "+v"(t[10]), "+v"(t[11]), "+v"(t[12]), "+v"(t[13]), "+v"(t[14]), "+v"(t[15]));
-    int m = 0x7fffffff;
-#pragma unroll
-    for (int c = 0; c < 16; c++) m = min(m, __mul24(b, P.c[c]) + t[c]);
-    return m & 15;
-}
-
-// HGR: for both palette bits, (distance term << 2 | pattern) of the nearest of the four colours the bit allows
-// (black 0, violet 3 | blue 6, green 12 | orange 9, white 15; ties to the lower pattern)
-__device__ static inline void nearest4x2(const IngestPalette &P, const IngestKv &kv, int r, int g, int b, int &key0, int &key1)
-{
-    // the six colours HGR can show
-    constexpr int col[6] = {0, 3, 12, 15, 6, 9};
-    const ingest_v2s gb = __builtin_bit_cast(ingest_v2s, (uint32_t)g | ((uint32_t)b << 16));
-    int t[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) t[j] = dist_key(P, kv.k[col[j]], col[j], r, gb) >> 4;   // (>> 4: the colour value leaves, the distance term stays exact)
-    const int f0 = t[0], f3 = t[1], f12 = t[2], f15 = t[3], f6 = t[4], f9 = t[5];
-    const int b0 = f0 * 4, w3 = f15 * 4 + 3;
-    key0 = min(min(b0, f3 * 4 + 1), min(f12 * 4 + 2, w3));
-    key1 = min(min(b0, f6 * 4 + 1), min(f9 * 4 + 2, w3));
-}
-
-__global__ __launch_bounds__(256) void ingest_holes_kernel(int n_banks, uint8_t *__restrict__ main_mem, uint8_t *__restrict__ aux_mem)
+__global__ __launch_bounds__(256) void screen_holes_kernel(int n_banks, uint8_t *__restrict__ main_mem, uint8_t *__restrict__ aux_mem)
 {
     // the screen holes of every page (offsets 120..127, 248..255) start as zero, as bmp2dhr's files hold them
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;   // one 8-byte hole each: 64 per bank
@@ -144,6 +53,13 @@ __global__ __launch_bounds__(256) void ingest_holes_kernel(int n_banks, uint8_t 
     const int h = (int)(i & 63);
     uint8_t *base = (aux_mem && (bank & 1)) ? aux_mem + (bank >> 1) * 8192 : main_mem + (aux_mem ? bank >> 1 : bank) * 8192;
     *reinterpret_cast<uint2 *>(base + (h >> 1) * 256 + ((h & 1) ? 248 : 120)) = make_uint2(0, 0);
+}
+
+int zero_screen_holes(int mode, int n_frames, uint8_t *d_main, uint8_t *d_aux, hipStream_t st)
+{
+    const int n_banks = mode == kDHGR ? 2 * n_frames : n_frames;
+    return launch(screen_holes_kernel, "screen_holes_kernel launch", dim3((unsigned)(((size_t)n_banks * 64 + 255) / 256)), dim3(256), 0, st, n_banks,
+                  d_main, mode == kDHGR ? d_aux : (uint8_t *)nullptr);
 }
 
 // Ordered dither (or none): thread T of a frame owns colour pixels 7 g .. 7 g + 6 of row y, T = 20 y + g -- the
@@ -159,27 +75,17 @@ __global__ __launch_bounds__(256) void ingest_kernel(int n, const uint8_t *__res
     if (idx >= (size_t)n * 3840) return;
     const size_t f = idx / 3840;
     const int T = (int)(idx - f * 3840), y = T / 20, g = T - 20 * y;
-    // 42 bytes at 42 T: aligned dwords from (42 T) & ~3, then a funnel shift by 0 or 16 bits
-    const uint8_t *src = rgb_frames + f * (size_t)(192 * 280 * 3) + (size_t)(42 * T);
-    const uint32_t *w32 = reinterpret_cast<const uint32_t *>(src - ((42 * T) & 2));
-    uint32_t w[11];
-#pragma unroll
-    for (int i = 0; i < 11; i++) w[i] = w32[i];
-    const uint32_t sh = ((uint32_t)(42 * T) & 2u) * 8u;
-    uint32_t q[11];
-#pragma unroll
-    for (int i = 0; i < 10; i++) q[i] = __builtin_amdgcn_alignbit(w[i + 1], w[i], sh);
-    q[10] = w[10] >> sh;
-    auto byte_at = [&](int nb) -> int { return (int)((q[nb >> 2] >> (8 * (nb & 3))) & 255u); };
+    SourceBytes<11> src;   // the 42 bytes at 42 T
+    load_group42(rgb_frames + f * (size_t)(192 * 280 * 3), 42 * T, src.q);
     const int drow = (y & 3) * 4;
-    const IngestKv kv = ingest_kv(P);
+    const Kv kv = kv_of(P);
     int colour[7], k0[7], k1[7];
 #pragma unroll
     for (int i = 0; i < 7; i++) {
         const int d = dtab[drow + ((7 * g + i) & 3)];
-        const int r = min(max(((byte_at(6 * i) + byte_at(6 * i + 3) + 1) >> 1) + d, 0), 255);
-        const int gg = min(max(((byte_at(6 * i + 1) + byte_at(6 * i + 4) + 1) >> 1) + d, 0), 255);
-        const int b = min(max(((byte_at(6 * i + 2) + byte_at(6 * i + 5) + 1) >> 1) + d, 0), 255);
+        const int r = min(max(((src.byte_at(6 * i) + src.byte_at(6 * i + 3) + 1) >> 1) + d, 0), 255);
+        const int gg = min(max(((src.byte_at(6 * i + 1) + src.byte_at(6 * i + 4) + 1) >> 1) + d, 0), 255);
+        const int b = min(max(((src.byte_at(6 * i + 2) + src.byte_at(6 * i + 5) + 1) >> 1) + d, 0), 255);
         if (MODE == kDHGR)
             colour[i] = nearest16(P, kv, r, gg, b);
         else
@@ -232,29 +138,21 @@ constexpr int kDiffWaves = 2;   // waves per block
 // Round 6: the source rows come through LDS.  A lane walks its row 42 bytes per seven steps, and sixty lanes of a wave
 // walk sixty rows: every load instruction touched sixty cache lines, each line was fetched again for each of the ~3
 // groups it holds (a CU's waves keep 150 KB of lines in use, its L1 holds 32), and the kernel ran at half the rate it has
-// when every lane reads the same row (4.0 against 7.6 M DHGR frames/s: profiles/r06_diffusion_experiments.txt).  Now a
+// when every lane reads the same row (4.0 against 7.6 M DHGR frames/s: profiles/r06_diffusion_experiments.txt, which also
+// keeps the measurements of the form that read the rows straight from memory).  Now a
 // lane's row is a stream of 64-byte blocks (aligned relative to the frame, whose size is a multiple of 64): three of
 // them -- the one its next group starts in and the two behind it -- are in LDS, filled by LDS-DMA loads
 // (global_load_lds_dwordx4: sixteen bytes per lane and instruction straight into LDS, no registers), a block requested
 // whole and at once, at least one seven-step iteration before the first group that needs it.  One instruction's
 // destination is wave-uniform (base + lane x 16), so the layout is [slot 0..2][16-byte chunk 0..3][lane][16 B] and the
-// lanes that fill the same slot in an iteration go together under an execution mask.  12 KiB per wave.
-#ifndef IIV_DIFF_STAGE
-#define IIV_DIFF_STAGE 1
-#endif
-// waves per SIMD the error-diffusion kernel's registers are held to: DHGR runs 11 % faster at five (96 VGPRs, six dwords
-// spilled) than at the four it gets unasked (110 VGPRs); HGR does not (-1 %); six (80 VGPRs) costs both a quarter
-#ifndef IIV_DIFF_OCC
-#define IIV_DIFF_OCC(MODE) (IIV_DIFF_STAGE ? 3 : (MODE) == kDHGR ? 5 : 4)   // (staged: 12 KiB of LDS per wave hold it to three anyway)
-#endif
+// lanes that fill the same slot in an iteration go together under an execution mask.  12 KiB per wave, which hold the
+// kernel to three waves per SIMD.
 template <int MODE>
-__global__ __launch_bounds__(64 * kDiffWaves, IIV_DIFF_OCC(MODE)) void ingest_diffusion_kernel(int n, const uint8_t *__restrict__ rgb_frames, const IngestPalette P,
+__global__ __launch_bounds__(64 * kDiffWaves, 3) void ingest_diffusion_kernel(int n, const uint8_t *__restrict__ rgb_frames, const IngestPalette P,
                                                                            uint8_t *__restrict__ main_mem, uint8_t *__restrict__ aux_mem)
 {
     __shared__ int ring_s[kDiffWaves][3][16][4];
-#if IIV_DIFF_STAGE
     __shared__ __attribute__((aligned(16))) uint32_t stage_s[kDiffWaves][12][64][4];   // [slot x 4 + chunk][lane][16 B]
-#endif
     __shared__ uint32_t pal_s[16];    // DHGR: R | G << 8 | B << 16 of the sixteen colour values
     __shared__ uint32_t rgb_s[8];     // R | G << 8 | B << 16 of colour4[pb][pattern]: black, violet | blue, green | orange, white
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -269,15 +167,15 @@ __global__ __launch_bounds__(64 * kDiffWaves, IIV_DIFF_OCC(MODE)) void ingest_di
     const bool lane_ok = slot3 < 3 && f < (size_t)n;
     int (*ring)[4] = ring_s[wv][slot3 < 3 ? slot3 : 0];
     const uint8_t *frame = rgb_frames + (lane_ok ? f : 0) * (size_t)(192 * 280 * 3);
-    const IngestKv kv = MODE == kDHGR ? ingest_kv(P) : IngestKv{};
-    // HGR: the six colours it can show, their K in vector registers (see IngestKv)
+    const Kv kv = MODE == kDHGR ? kv_of(P) : Kv{};
+    // HGR: the six colours it can show, their K in vector registers (iiv_frontend.h: Kv)
     int kv0 = P.k[0], kv3 = P.k[3], kv12 = P.k[12], kv15 = P.k[15], kv6 = P.k[6], kv9 = P.k[9];
     asm volatile("" : "+v"(kv0), "+v"(kv3), "+v"(kv12), "+v"(kv15), "+v"(kv6), "+v"(kv9));
     struct F6 {
         int f0, f3, f12, f15, f6, f9;
     };
     auto f6 = [&](int r, int g, int b) -> F6 {   // the distance terms of the six colours (dist_key)
-        const ingest_v2s gb = __builtin_bit_cast(ingest_v2s, (uint32_t)g | ((uint32_t)b << 16));
+        const v2s gb = __builtin_bit_cast(v2s, (uint32_t)g | ((uint32_t)b << 16));
         return F6{dist_key(P, kv0, 0, r, gb) >> 4, dist_key(P, kv3, 3, r, gb) >> 4, dist_key(P, kv12, 12, r, gb) >> 4,
                   dist_key(P, kv15, 15, r, gb) >> 4, dist_key(P, kv6, 6, r, gb) >> 4, dist_key(P, kv9, 9, r, gb) >> 4};
     };
@@ -291,35 +189,6 @@ __global__ __launch_bounds__(64 * kDiffWaves, IIV_DIFF_OCC(MODE)) void ingest_di
     uint32_t cur[11], nxt[11];            // the source bytes of the current / next 7-pixel group, funnel-shifted to start at byte 0
     int pbA = 0, pbB = 0;
     uint32_t bytesAB = 0;                 // HGR: the two screen bytes of the group, as they fill; DHGR: its 28 dots
-    // source group of sequence position tt (clamped into the frame)
-    [[maybe_unused]] auto load_group = [&](int tt, uint32_t (&w)[11]) {
-        int v = tt < 0 ? 0 : tt;
-        int qq = v / 20, gg = v - 20 * qq;
-        int rw = 20 * qq + i;
-        if (rw > 191) rw = 191, gg = 0;
-#ifdef IIV_EXP_DIFF_SAMEROW
-        rw = 0;   // (timing experiment only: every lane reads row 0 -- what the kernel costs without its row-strided reads)
-#endif
-        const size_t off = (size_t)rw * 840 + (size_t)gg * 42;
-        const uint32_t *p32 = reinterpret_cast<const uint32_t *>(frame + (off & ~(size_t)3));
-        uint32_t raw[11];
-#pragma unroll
-        for (int j = 0; j < 11; j++) raw[j] = p32[j];
-        const uint32_t sh = ((uint32_t)off & 2u) * 8u;
-#pragma unroll
-        for (int j = 0; j < 10; j++) w[j] = __builtin_amdgcn_alignbit(raw[j + 1], raw[j], sh);
-        w[10] = raw[10] >> sh;
-    };
-    // (eleven dwords from the aligned base never leave the row: a group at an odd halfword is the row's last or has 42 bytes
-    // behind it; positions beyond the frame are clamped to row 191's first group)
-    // mean of the two source pixels of group pixel GP, three channels in one v_lerp_u8: bytes 6 GP .. 6 GP + 5 of cur
-    auto mean_of = [&](auto GPc) -> uint32_t {
-        constexpr int GP = decltype(GPc)::value;
-        constexpr int oa = 6 * GP, ob = 6 * GP + 3;
-        const uint32_t A = (oa & 3) ? __builtin_amdgcn_alignbit(cur[(oa >> 2) + 1], cur[oa >> 2], (oa & 3) * 8) : cur[oa >> 2];
-        const uint32_t B = (ob & 3) ? __builtin_amdgcn_alignbit(cur[(ob >> 2) + 1 > 10 ? 10 : (ob >> 2) + 1], cur[ob >> 2], (ob & 3) * 8) : cur[ob >> 2];
-        return __builtin_amdgcn_lerp(A, B, 0x01010101u);
-    };
     auto value_of = [&](uint32_t m, int ar, int ag, int ab, int &r, int &g, int &b) {   // clamp(mean + floor(acc / 16))
         r = min(max((int)(m & 255u) + (ar >> 4), 0), 255);
         g = min(max((int)((m >> 8) & 255u) + (ag >> 4), 0), 255);
@@ -329,7 +198,6 @@ __global__ __launch_bounds__(64 * kDiffWaves, IIV_DIFF_OCC(MODE)) void ingest_di
     bool active = false;
     int row = i;
     size_t outp = 0;
-#if IIV_DIFF_STAGE
     // ---- the staged source stream of this lane (byte offsets are relative to its frame; blocks = 64 bytes)
     // reader: where the group it reads next starts, and the slot of that byte's block; what it has moved past is refilled
     uint32_t (*stage)[64][4] = stage_s[wv];
@@ -425,10 +293,6 @@ __global__ __launch_bounds__(64 * kDiffWaves, IIV_DIFF_OCC(MODE)) void ingest_di
     advance_reader(tt + 2);
     fetch_round();
     fetch_round();
-#else
-    load_group(tt, cur);
-    load_group(tt + 1, nxt);
-#endif
     auto step = [&](auto Pc) {
         constexpr int PH = decltype(Pc)::value;
         // what arrived: D(pixel + 5) of the row above, into its slot; lane 0 of a frame slot takes it from the ring
@@ -456,7 +320,7 @@ __global__ __launch_bounds__(64 * kDiffWaves, IIV_DIFF_OCC(MODE)) void ingest_di
             // 7 e + D as (e << 3) + (D - e): two full-rate instructions (a plain 7 * e + D becomes the quarter-rate v_mad_u64_u32)
             int tr = Dq[PH][0] - e0r, tg = Dq[PH][1] - e0g, tb = Dq[PH][2] - e0b;
             asm("" : "+v"(tr), "+v"(tg), "+v"(tb));
-            value_of(mean_of(Pc), (e0r << 3) + tr, (e0g << 3) + tg, (e0b << 3) + tb, r, g, b);
+            value_of(mean_of<PH>(cur), (e0r << 3) + tr, (e0g << 3) + tg, (e0b << 3) + tb, r, g, b);
             if constexpr (MODE == kDHGR) {
                 // the nearest of the sixteen colours; its value IS the pixel's dot quad
                 const int col = nearest16_mad(P, kv, r, g, b);
@@ -481,7 +345,7 @@ __global__ __launch_bounds__(64 * kDiffWaves, IIV_DIFF_OCC(MODE)) void ingest_di
                 auto ahead = [&](auto Qc, int w) {
                     constexpr int Q = decltype(Qc)::value;
                     int r2, g2, b2;
-                    value_of(mean_of(Qc), Dq[Q][0], Dq[Q][1], Dq[Q][2], r2, g2, b2);
+                    value_of(mean_of<Q>(cur), Dq[Q][0], Dq[Q][1], Dq[Q][2], r2, g2, b2);
                     const F6 fa = f6(r2, g2, b2);
                     s0 += __mul24(w, min(min(fa.f0, fa.f3), min(fa.f12, fa.f15)));   // (|f| < 2^21)
                     s1 += __mul24(w, min(min(fa.f0, fa.f6), min(fa.f9, fa.f15)));
@@ -549,23 +413,17 @@ __global__ __launch_bounds__(64 * kDiffWaves, IIV_DIFF_OCC(MODE)) void ingest_di
         step(std::integral_constant<int, 3>{});
         step(std::integral_constant<int, 4>{});
         step(std::integral_constant<int, 5>{});
-#if IIV_DIFF_STAGE
         // what was requested at the end of the previous iteration has landed by now (six steps later).  HERE, not at the read
         // below: behind step 6 the wait would also cover the row's stores that step has just issued
         staged_wait();
-#endif
         step(std::integral_constant<int, 6>{});
 #pragma unroll
         for (int j = 0; j < 11; j++) cur[j] = nxt[j];
         tt++;
-#if IIV_DIFF_STAGE
         read_group(nxt);          // group tt + 1: where the reader stands (its blocks: waited for in front of step 6)
         advance_reader(tt + 2);
         fetch_round();            // the blocks left behind: at most two per lane (a row's end)
         if (__ballot(fe_need > 0) != 0ull) fetch_round();
-#else
-        load_group(tt + 1, nxt);
-#endif
     }
 }
 
@@ -573,10 +431,7 @@ int frames_to_memory_maps(int mode, const uint8_t palette_rgb[48], int n, const 
                           uint8_t *d_aux, hipStream_t st)
 {
     const IngestPalette P = make_palette(palette_rgb, dither);
-    const int n_banks = mode == kDHGR ? 2 * n : n;
-    if (int rc = launch(ingest_holes_kernel, "ingest_holes_kernel launch", dim3((unsigned)(((size_t)n_banks * 64 + 255) / 256)), dim3(256), 0, st,
-                        n_banks, d_main, mode == kDHGR ? d_aux : (uint8_t *)nullptr))
-        return rc;
+    if (int rc = zero_screen_holes(mode, n, d_main, d_aux, st)) return rc;
     if (dither == IIV_DITHER_DIFFUSION) {
         const dim3 grid((unsigned)((n + 3 * kDiffWaves - 1) / (3 * kDiffWaves)));
         // (IIV_EXP_DIFF_LDS_PAD: timing experiments only -- extra dynamic LDS per workgroup caps the waves resident per CU)

@@ -5,8 +5,8 @@
 // include/iivision.h (iiv_frames_to_memory_maps_mono); tests/mono_model.py restates it and the tests hold these kernels
 // to that restatement byte for byte.
 //   * Ordered dither: one thread per FOURTEEN dots = two screen bytes (DHGR: the aux and the main byte of a column;
-//     HGR: two main bytes): its 42 source bytes are eleven aligned dword loads and a funnel shift, as in ingest_kernel
-//     (iiv_ingest.hip).  No dot is evaluated twice, nothing is exchanged.
+//     HGR: two main bytes): its 42 source bytes are eleven aligned dword loads and a funnel shift (iiv_frontend.h:
+//     load_group42, which ingest_kernel shares).  No dot is evaluated twice, nothing is exchanged.
 //   * Error diffusion: lanes are ROWS, a wave is a frame.  Lane r works on rows r, 64 + r, 128 + r one after the other,
 //     two dots behind lane r - 1: at step t it is at position s = t - 2 r of its 3 W dots.  What a row hands down,
 //     D(j) = e(j - 1) + 5 e(j) + 3 e(j + 1), is final once dot j + 1 is done -- exactly one step before the lane below
@@ -19,16 +19,12 @@
 //     steps, 1 KiB contiguous per wave (sixty-four lanes walking sixty-four rows would touch sixty-four cache lines per
 //     load: what bound the colour kernel).  The pre-pass writes into stream-ordered scratch, a chunk of
 //     frames at a time.
+#include "iiv_frontend.h"
 #include "iiv_host.h"
 #include <stdlib.h>
 
 namespace iiv {
 namespace {
-
-__device__ __host__ inline int mono_y_to_offset(int y)  // y_to_base_addr(y, 0) - 0x2000 (screen.py:16-22)
-{
-    return 1024 * (y % 8) + 128 * ((y % 64) / 8) + 40 * (y / 64);
-}
 
 template <int MODE> struct MonoGeom {
     static constexpr int W = MODE == kDHGR ? 560 : 280;          // dots per row = source pixels per row
@@ -45,24 +41,12 @@ struct MonoDither {
 
 MonoDither make_dither(int dither)
 {
-    static const int bayer[16] = {0, 8, 2, 10, 12, 4, 14, 6, 3, 11, 1, 9, 15, 7, 13, 5};
     MonoDither p;
-    for (int c = 0; c < 16; c++) p.d[c] = ((2 * bayer[c] - 15) * dither + 16 * 256) / 16 - 256;
+    dither_offsets(dither, p.d);
     return p;
 }
 
 __device__ inline int mono_luma(int r, int g, int b) { return (77 * r + 150 * g + 29 * b + 128) >> 8; }
-
-__global__ __launch_bounds__(256) void mono_holes_kernel(int n_banks, uint8_t *__restrict__ main_mem, uint8_t *__restrict__ aux_mem)
-{
-    // the screen holes of every page (offsets 120..127, 248..255) are written as zero
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;   // one 8-byte hole each: 64 per bank
-    if (i >= (size_t)n_banks * 64) return;
-    const size_t bank = i >> 6;
-    const int h = (int)(i & 63);
-    uint8_t *base = (aux_mem && (bank & 1)) ? aux_mem + (bank >> 1) * 8192 : main_mem + (aux_mem ? bank >> 1 : bank) * 8192;
-    *reinterpret_cast<uint2 *>(base + (h >> 1) * 256 + ((h & 1) ? 248 : 120)) = make_uint2(0, 0);
-}
 
 // Ordered dither (or none): thread T of a frame owns dots 14 g .. 14 g + 13 of row y, T = (W / 14) y + g -- the frame's
 // source bytes are 42 contiguous bytes per thread in thread order.  (Eleven dwords from the aligned base never leave the
@@ -80,33 +64,24 @@ __global__ __launch_bounds__(256) void mono_ordered_kernel(int n, const uint8_t 
     if (idx >= (size_t)n * TPF) return;
     const size_t f = idx / TPF;
     const int T = (int)(idx - f * TPF), y = T / TPR, g = T - TPR * y;
-    const uint8_t *src = rgb_frames + f * (size_t)G::kFrameBytes + (size_t)(42 * T);
-    const uint32_t *w32 = reinterpret_cast<const uint32_t *>(src - ((42 * T) & 2));
-    uint32_t w[11];
-#pragma unroll
-    for (int i = 0; i < 11; i++) w[i] = w32[i];
-    const uint32_t sh = ((uint32_t)(42 * T) & 2u) * 8u;
-    uint32_t q[11];
-#pragma unroll
-    for (int i = 0; i < 10; i++) q[i] = __builtin_amdgcn_alignbit(w[i + 1], w[i], sh);
-    q[10] = w[10] >> sh;
-    auto byte_at = [&](int nb) -> int { return (int)((q[nb >> 2] >> (8 * (nb & 3))) & 255u); };
+    SourceBytes<11> src;   // the 42 bytes at 42 T
+    load_group42(rgb_frames + f * (size_t)G::kFrameBytes, 42 * T, src.q);
     const int drow = (y & 3) * 4;
     uint32_t dots = 0;
 #pragma unroll
     for (int i = 0; i < 14; i++) {
         const int d = dtab[drow + ((14 * g + i) & 3)];
-        const int v = min(max(mono_luma(byte_at(3 * i), byte_at(3 * i + 1), byte_at(3 * i + 2)) + d, 0), 255);
+        const int v = min(max(mono_luma(src.byte_at(3 * i), src.byte_at(3 * i + 1), src.byte_at(3 * i + 2)) + d, 0), 255);
         dots |= (uint32_t)(v >= 128 ? 1 : 0) << i;
     }
     const uint32_t A = dots & 0x7fu, B = (dots >> 7) & 0x7fu;   // bytes 2 g and 2 g + 1 of the row
     if (MODE == kDHGR) {
         // even bytes of the row's 80 -> aux, odd -> main, column X / 14 (screen.py:822-826)
-        const size_t out = f * 8192 + (size_t)(mono_y_to_offset(y) + g);
+        const size_t out = f * 8192 + (size_t)(y_to_offset(y) + g);
         aux_mem[out] = (uint8_t)A;
         main_mem[out] = (uint8_t)B;
     } else {
-        const size_t out = f * 8192 + (size_t)(mono_y_to_offset(y) + 2 * g);
+        const size_t out = f * 8192 + (size_t)(y_to_offset(y) + 2 * g);
         *reinterpret_cast<uint16_t *>(main_mem + out) = (uint16_t)(A | (B << 8));
     }
 }
@@ -137,13 +112,12 @@ __global__ __launch_bounds__(256) void mono_luma_skew_kernel(int n, const uint8_
 #pragma unroll
         for (int j = 0; j < 12; j++) w[j] = p[j];
         w[12] = sh ? p[12] : 0u;
-        uint32_t q[12];
+        SourceBytes<12> src;
 #pragma unroll
-        for (int j = 0; j < 12; j++) q[j] = __builtin_amdgcn_alignbit(w[j + 1], w[j], sh);
-        auto byte_at = [&](int nb) -> int { return (int)((q[nb >> 2] >> (8 * (nb & 3))) & 255u); };
+        for (int j = 0; j < 12; j++) src.q[j] = __builtin_amdgcn_alignbit(w[j + 1], w[j], sh);
 #pragma unroll
         for (int i = 0; i < 16; i++)
-            o[i >> 2] |= (uint32_t)mono_luma(byte_at(3 * i), byte_at(3 * i + 1), byte_at(3 * i + 2)) << (8 * (i & 3));
+            o[i >> 2] |= (uint32_t)mono_luma(src.byte_at(3 * i), src.byte_at(3 * i + 1), src.byte_at(3 * i + 2)) << (8 * (i & 3));
     } else {
 #pragma unroll
         for (int i = 0; i < 16; i++) {
@@ -229,9 +203,9 @@ __global__ __launch_bounds__(64 * kMonoWaves) void mono_diffusion_kernel(int n, 
             if (nb >= 7) {
                 const uint8_t b = (uint8_t)(bits & 0x7fu);
                 if (MODE == kDHGR)
-                    ((ob & 1) ? out_main : out_aux)[mono_y_to_offset(orow) + (ob >> 1)] = b;
+                    ((ob & 1) ? out_main : out_aux)[y_to_offset(orow) + (ob >> 1)] = b;
                 else
-                    out_main[mono_y_to_offset(orow) + ob] = b;
+                    out_main[y_to_offset(orow) + ob] = b;
                 bits >>= 7;
                 nb -= 7;
                 if (++ob == G::kRowBytes) ob = 0, orow += 64;
@@ -288,10 +262,7 @@ extern "C" int iiv_frames_to_memory_maps_mono(int mode, int n_frames, const uint
         return iiv::set_error(IIV_ERR_INVALID, "iiv_frames_to_memory_maps_mono: d_rgb must be 4-byte aligned, d_main / d_aux 8-byte aligned");
     if (n_frames == 0) return IIV_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int n_banks = mode == IIV_DHGR ? 2 * n_frames : n_frames;
-    if (int rc = iiv::launch(iiv::mono_holes_kernel, "mono_holes_kernel launch", dim3((unsigned)(((size_t)n_banks * 64 + 255) / 256)), dim3(256),
-                             0, st, n_banks, d_main, mode == IIV_DHGR ? d_aux : (uint8_t *)nullptr))
-        return rc;
+    if (int rc = iiv::zero_screen_holes(mode, n_frames, d_main, d_aux, st)) return rc;
     return mode == IIV_DHGR ? iiv::mono_frames<iiv::kDHGR>(n_frames, d_rgb, dither, d_main, d_aux, st)
                             : iiv::mono_frames<iiv::kHGR>(n_frames, d_rgb, dither, d_main, d_aux, st);
 }
