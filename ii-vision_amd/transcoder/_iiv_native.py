@@ -158,6 +158,10 @@ _SIGNATURES = {
     "iiv_resize_frames_fit": (_i32, [_i32, _i32, _i32, _vp, _sz, _sz, _vp, _i32, _i32, _vp, C.c_uint32, _vp, _vp]),
     "iiv_resize_frames_yuv420_fit": (_i32, [_i32, _i32, _i32, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _i32, _vp, _vp, _i32, _i32, _vp,
                                             C.c_uint32, _vp, _vp]),
+    # ---- f13: speaker preview
+    "iiv_speaker_periods": (_lg, [_lg]),
+    "iiv_speaker_sample_count": (_lg, [_lg, _i32]),
+    "iiv_speaker_pcm": (_i32, [_i32, _vp, _sz, _vp, _sz, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
 }
 SYMBOLS = list(_SIGNATURES)
 
@@ -1051,6 +1055,65 @@ class A2mReaderHandle:
             check(lib().iiv_a2m_replay(self._h, S, dptr(data), stride, dptr(info), min(first, 2 ** 62), min(every, 2 ** 62), n,
                                        dptr(im), dptr(ia), dptr(main), dptr(aux), stream_ptr()))
         return main, aux
+
+
+# ---- f13: speaker preview -------------------------------------------------------------
+
+SPEAKER_DECIM, SPEAKER_ORDER, SPEAKER_GAIN = 23, 3, 16384   # the defaults of every speaker_pcm: 1020484 / 23 = 44 369 Hz
+
+
+def speaker_periods(n_ops):
+    """73-cycle periods a stream of n_ops opcodes plays: the opcodes and two per ACK (iiv_speaker_periods).  Host only."""
+    return int(lib().iiv_speaker_periods(int(n_ops)))
+
+
+def speaker_sample_count(n_ops, decim=SPEAKER_DECIM):
+    """PCM samples of a stream of n_ops opcodes at one sample per `decim` cycles (iiv_speaker_sample_count).  Host only."""
+    n = lib().iiv_speaker_sample_count(int(n_ops), int(decim))
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def speaker_pcm(ticks, counts=None, decim=SPEAKER_DECIM, order=SPEAKER_ORDER, gain=SPEAKER_GAIN, out=None, d_err=None):
+    """What the ticks of S streams sound like: ticks CUDA uint8 (S, n) with contiguous rows (audio_ticks' or A2mReaderHandle.decode's
+    output) -> (CUDA int16 (S, pcm_stride), int64 numpy sample counts M(s)); row s is written up to M(s) and left as it was -- zero
+    in a new tensor -- behind it (include/iivision.h: iiv_speaker_pcm).  counts: the opcode count of every stream, None = n for all;
+    a sequence or numpy array, or a CUDA int64 tensor that is handed over as it is -- a scan's info[:, 2] view, stride 4,
+    included -- and then costs the one device-to-host copy that the returned counts need.  out: a CUDA int16 (S, >=
+    speaker_sample_count(n, decim)) tensor with contiguous rows.  d_err: a CUDA int32 tensor of one element that is set to 1 if a
+    tick byte is not an even number in 4..66 (never cleared).  Asynchronous on torch's current stream."""
+    torch = _torch()
+    if not (isinstance(ticks, torch.Tensor) and ticks.is_cuda and ticks.dtype == torch.uint8 and ticks.dim() == 2
+            and (ticks.shape[1] == 0 or ticks.stride(1) == 1)):
+        raise ValueError("ticks must be a CUDA uint8 tensor (n_streams, n) with contiguous rows")
+    S, n = int(ticks.shape[0]), int(ticks.shape[1])
+    if S > 1 and int(ticks.stride(0)) != n:   # (the C ABI takes the row stride as the bound of every count)
+        ticks = ticks.contiguous()
+    if isinstance(counts, torch.Tensor):
+        if not (counts.is_cuda and counts.dtype == torch.int64 and counts.dim() == 1 and int(counts.shape[0]) == S):
+            raise ValueError("counts must be a CUDA int64 tensor (%d,)" % S)
+        d_counts, host = counts, None
+    else:
+        host = np.ascontiguousarray(np.broadcast_to(np.asarray(n if counts is None else counts, dtype=np.int64), (S,)))
+        d_counts = torch.from_numpy(host.copy()).cuda()
+    if not (1 <= int(decim) <= 73 and 1 <= int(order) <= 4 and 0 <= int(gain) <= 32767):
+        raise ValueError("speaker_pcm: decim 1..73, order 1..4, gain 0..32767")
+    width = speaker_sample_count(n, decim)
+    if out is None:
+        out = torch.zeros((S, max(-(-width // 8) * 8, 8)), dtype=torch.int16, device="cuda")   # rows start 16-byte aligned
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int16 and out.dim() == 2 and int(out.shape[0]) == S
+              and int(out.shape[1]) >= width and out.stride(1) == 1):
+        raise ValueError("out must be a CUDA int16 tensor (n_streams, >= %d) with contiguous rows" % width)
+    if d_err is not None and not (isinstance(d_err, torch.Tensor) and d_err.is_cuda and d_err.dtype == torch.int32 and d_err.numel() == 1):
+        raise ValueError("d_err must be a CUDA int32 tensor of one element")
+    if S and n:
+        check(lib().iiv_speaker_pcm(S, dptr(ticks), n, dptr(d_counts),
+                                    int(d_counts.stride(0)) if S > 1 else 1, int(decim), int(order), int(gain), dptr(out),
+                                    int(out.stride(0)) if S > 1 else int(out.shape[1]), dptr(d_err), stream_ptr()))
+    if host is None:
+        host = d_counts.cpu().numpy()   # (behind the launch: nothing waits for the host in front of the kernel)
+    return out, np.array([speaker_sample_count(c, decim) for c in np.clip(host, 0, n)], dtype=np.int64)
 
 
 # ---- f4: the audio track ------------------------------------------------------------

@@ -126,6 +126,16 @@ class A2mReader:
         data, info, _ = self._scanned(streams, lengths, strict)
         return self._reader.replay(data, info, first, every, n, init)
 
+    def speaker_pcm(self, streams, decim=native.SPEAKER_DECIM, order=native.SPEAKER_ORDER, gain=native.SPEAKER_GAIN, lengths=None,
+                    strict=True):
+        """-> one CUDA int16 vector per stream: what its ticks sound like on the machine, at audio.speaker_rate(decim) samples a
+        second (include/iivision.h f13).  Scan, decode and the speaker kernel follow each other on the device: the kernel takes
+        its opcode counts from the scan's own output."""
+        data, info, host = self._scanned(streams, lengths, strict)
+        _, ticks, _ = self._reader.decode(data, info)
+        pcm, _ = native.speaker_pcm(ticks, info[:, 2], decim, order, gain)
+        return [pcm[i, :native.speaker_sample_count(int(host[i, 2]), decim)] for i in range(len(host))]
+
 
 def retarget(stream, old_addresses, new_addresses):
     """One stream written for the player build of old_addresses -> the same movie for new_addresses (CUDA uint8, 1-D):

@@ -18,6 +18,13 @@ import _iiv_native as native
 
 BITRATE = native.AUDIO_BITRATE
 BLOCK_FRAMES = native.AUDIO_BLOCK_FRAMES
+CLOCK = 1020484   # cycles a second of the Apple II the player runs on (NTSC: 14.31818 MHz * 65 / 912)
+
+
+def speaker_rate(decim=native.SPEAKER_DECIM, clock=CLOCK):
+    """Samples a second of speaker_pcm at one sample per `decim` cycles: the one place where the machine's clock enters (the
+    kernel counts cycles only).  decim = 23 gives 44 369 Hz."""
+    return int(round(clock / decim))
 
 
 def read_wav(filename):
@@ -35,6 +42,15 @@ def read_wav(filename):
         raw = w.readframes(n)
     pcm = np.frombuffer(raw, dtype="<i2").astype(np.int16).reshape(-1, ch)
     return pcm, rate
+
+
+def write_wav(filename, pcm, rate):
+    """int16 (n,) -> a 16-bit mono PCM .wav at `rate` Hz"""
+    with wave.open(filename, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(int(rate))
+        w.writeframes(np.ascontiguousarray(pcm, dtype="<i2").tobytes())
 
 
 class ArrayAudio:
@@ -73,6 +89,14 @@ class ArrayAudio:
         t, _ = native.audio_ticks(self.pcm, self.n_frames, self.channels, self.rate, self.normalization, self.bitrate,
                                   self.block_frames, out)
         return t
+
+    def speaker_pcm(self, decim=native.SPEAKER_DECIM, order=native.SPEAKER_ORDER, gain=native.SPEAKER_GAIN):
+        """CUDA int16 (n_streams, speaker_sample_count(tick_count(), decim)): what the ticks of ticks() will sound like on the
+        machine, before anything is encoded -- the player's pulses through a CIC decimator, at speaker_rate(decim) samples a
+        second (include/iivision.h f13).  Asynchronous on torch's current stream."""
+        n = self.tick_count()
+        pcm, _ = native.speaker_pcm(self.ticks()[:, :n].contiguous(), None, decim, order, gain)
+        return pcm[:, :native.speaker_sample_count(n, decim)]
 
     def audio_stream(self, stream=0) -> Iterator[int]:
         """audio.Audio.audio_stream: the samples -15 .. 16 of one stream"""

@@ -868,6 +868,45 @@ int iiv_resize_frames_yuv420_fit(int n, int h, int w, const uint8_t *d_y, size_t
                                  int c_pixel_stride, const int32_t matrix[6], const float box[4], int H, int W, const int rect[4],
                                  uint32_t fill, uint8_t *d_dst, void *stream);
 
+/* ==== f13: speaker preview ==================================================
+ * What a stream's ticks sound like: the 1-bit signal the player's speaker toggles make, taken down to 16-bit PCM by a CIC
+ * decimator -- f7 for the ear.  Integer arithmetic only, so every implementation agrees sample for sample
+ * (tests/speaker_model.py restates this section cycle by cycle; csrc/iiv_speaker.hip computes it).
+ *   Periods.  Time is cut into periods of 73 cycles (the player's opcode, player/main.s).  Tick opcode k is one period: the
+ *   speaker is toggled at its start and width(tick) cycles later, so the level is high for width cycles and low for the rest.
+ *   width(t) = t for the even t in 4..66, except width(22) = 21 and width(40) = 41 (the two opcodes whose pulse is a cycle
+ *   off).  A tick byte that is not an even number in 4..66 has width 0 and sets *d_err = 1 (d_err: device int, may be NULL, as
+ *   for iiv_emit_chunk; the call never clears it).
+ *   ACKs.  By f9's layout an ACK follows opcodes 290, 582, 874, ...; it is two more periods of width 34 each.  The ACKs in
+ *   front of opcode k: A(k) = 0 for k < 291, 1 + (k - 291) / 292 otherwise.  Opcode k is period q(k) = k + 2 A(k); a stream of n
+ *   opcodes has Q(n) = n + 2 A(n) periods.  W[p] is the width of period p.
+ *   Left out on purpose: the header, NOP and Terminate opcodes, the player's wait loop when the network is late, and the
+ *   key-press pause are not part of the signal.
+ *   Signal.  x(c) = +1 if 0 <= c < 73 Q and c % 73 < W[c / 73], else -1, for every integer c: before and after the stream the
+ *   speaker rests low.
+ *   Filter.  h_1 is `decim` ones, h_r = h_(r-1) * h_1 (convolution): r (decim - 1) + 1 taps that sum to decim^r.
+ *     acc[m] = sum over i of h_order[i] * x(m * decim + decim - 1 - i)     for 0 <= m < M = ceil(73 Q / decim), M = 0 when n = 0
+ *   Scaling.  pcm[m] = clamp(floor(acc[m] * gain / decim^order), -32768, 32767), the floor towards minus infinity, the product
+ *   in 64 bits (73^4 * 32767 does not fit 32).
+ *   Limits.  1 <= decim <= 73, 1 <= order <= 4, 0 <= gain <= 32767.
+ * The output rate is the machine's clock over decim; the clock itself is the caller's business (audio.speaker_rate). */
+
+/* Q(n_ops) and M(n_ops, decim): host only, closed forms.  n_ops < 0 counts as 0; a decim outside 1..73 is IIV_ERR_INVALID. */
+long iiv_speaker_periods(long n_ops);
+long iiv_speaker_sample_count(long n_ops, int decim);
+
+/* The PCM of n_streams streams: stream s has the tick bytes d_ticks + s * ticks_stride (what iiv_a2m_decode and iiv_audio_ticks
+ * write), its opcode count at d_counts[s * counts_stride] -- a device int64, 8-byte aligned, so a scan's d_info + 2 with stride 4
+ * goes in as it is; a negative count is read as 0, one above ticks_stride as ticks_stride -- and gets its M(s) samples at
+ * d_pcm + s * pcm_stride (in samples; 2-byte aligned; rows that start 16-byte aligned are written 16 bytes a lane).  Samples past
+ * M(s) are left alone.  pcm_stride >= iiv_speaker_sample_count(ticks_stride, decim), so that no count can take a write out of a
+ * row.  Asynchronous on `stream`; nothing is allocated, nothing synchronised, no host memory is read after the call returns (the
+ * filter's running sum, at most 290 ints, goes to the kernel by value).  n_streams == 0 succeeds and writes nothing.
+ * IIV_ERR_INVALID before anything is launched, with nothing written: a limit above, n_streams < 0, a NULL d_ticks, d_counts or
+ * d_pcm, a bad alignment, a ticks_stride above 2^48, a pcm_stride that is too small. */
+int iiv_speaker_pcm(int n_streams, const uint8_t *d_ticks, size_t ticks_stride, const int64_t *d_counts, size_t counts_stride,
+                    int decim, int order, int gain, int16_t *d_pcm, size_t pcm_stride, int *d_err, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

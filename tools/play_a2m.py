@@ -3,6 +3,7 @@
     python tools/play_a2m.py clip.a2m --check
     python tools/play_a2m.py clip.a2m --every 490 --preview screens.npy
     python tools/play_a2m.py clip.a2m --every 490 --ref frames.npy --quality quality.json
+    python tools/play_a2m.py clip.a2m --audio out.wav [--decim 23] [--order 3] [--gain 16384] [--clock 1020484]
 
 The file may come from tools/transcode_clip.py, from the reference's transcoder or from an older build: the reader works
 from the bytes alone (include/iivision.h section f9; csrc/iiv_a2m_read.hip).  --dbg: the player's cc65 debug file the
@@ -13,7 +14,10 @@ one at the end of the stream; snapshot j holds the first min((j + 1) * OPS, n_op
 --preview OUT.npy: the snapshots drawn through the colour model (csrc/iiv_render.hip), uint8 (snapshots, 192, 560, 3).
 --ref FRAMES.npy --quality OUT.json: the snapshots measured against one reference frame each, uint8 (snapshots, 192, 280 or
 560, 3), on the device (csrc/iiv_render_error.hip): the nine exact sums of squared differences and three PSNRs per snapshot,
-in the layout tools/transcode_clip.py --quality writes."""
+in the layout tools/transcode_clip.py --quality writes.
+--audio OUT.wav: what the stream's ticks sound like, 16-bit mono PCM: the speaker's pulses, the ACKs' two periods included, through
+a CIC decimator of --order stages that keeps one sample per --decim cycles, scaled by --gain / 32768 of full scale
+(csrc/iiv_speaker.hip; include/iivision.h section f13).  The rate written is --clock / --decim, rounded (audio.speaker_rate)."""
 import argparse
 import json
 import os
@@ -34,17 +38,25 @@ def main():
     ap.add_argument("--ref", metavar="FRAMES.npy")
     ap.add_argument("--quality", metavar="OUT.json")
     ap.add_argument("--check", action="store_true")
+    ap.add_argument("--audio", metavar="OUT.wav")
+    ap.add_argument("--decim", type=int, default=23, help="cycles per sample, 1..73")
+    ap.add_argument("--order", type=int, default=3, help="CIC stages, 1..4")
+    ap.add_argument("--gain", type=int, default=16384, help="0..32767")
+    ap.add_argument("--clock", type=int, default=1020484, help="cycles a second of the machine")
     a = ap.parse_args()
     if bool(a.ref) != bool(a.quality):
         ap.error("--ref and --quality go together")
     if (a.preview or a.quality) and (a.every is None or a.every < 1):
         ap.error("--preview / --quality need --every OPS >= 1")
-    if not (a.check or a.preview or a.quality):
-        ap.error("nothing to do: one of --check, --preview, --quality")
+    if not (a.check or a.preview or a.quality or a.audio):
+        ap.error("nothing to do: one of --check, --preview, --quality, --audio")
+    if not (1 <= a.decim <= 73 and 1 <= a.order <= 4 and 0 <= a.gain <= 32767 and a.clock >= 1):
+        ap.error("--decim 1..73, --order 1..4, --gain 0..32767, --clock >= 1")
 
     import torch
     import _iiv_native as native
     import a2m
+    import audio
     import palette
     import screen
 
@@ -83,6 +95,11 @@ def main():
                                        "psnr_db": [float(db[level][i]) for level in range(3)]} for i in range(n)]}, f, indent=1)
             print("screen against reference, mean PSNR over %d snapshots: dot %.2f dB, quad %.2f dB, unit %.2f dB -> %s" % (
                 n, *(float(np.mean(d)) for d in db), a.quality))
+    if a.audio:
+        pcm = reader.speaker_pcm([data], a.decim, a.order, a.gain)[0].cpu().numpy()
+        rate = audio.speaker_rate(a.decim, a.clock)
+        audio.write_wav(a.audio, pcm, rate)
+        print("%d samples at %d Hz (%.2f s) -> %s" % (len(pcm), rate, len(pcm) / rate, a.audio))
     reader.close()
     return 0
 

@@ -31,7 +31,10 @@ squared differences [level][channel] -- per dot, per quad of four dots, per unit
 level (screen.psnr).  The .a2m bytes and the --preview array are the same with and without it.
 --fit letterbox / crop (with --sar N:D, --fill R,G,B): a source that is not 4:3 on display keeps its shape -- whole, between bars of
 the fill colour, or cropped to its centred 4:3 part (frame_grabber.fit_geometry) -- instead of being stretched over the
-screen as the reference does; --preview shows it and --quality measures against the fitted frame, the one the ingest saw."""
+screen as the reference does; --preview shows it and --quality measures against the fitted frame, the one the ingest saw.
+--preview-audio FILE.wav: also write what the stream's ticks sound like on the machine, 16-bit mono PCM at 44 369 Hz: the speaker's
+pulses, ACKs included, through the default CIC decimator (csrc/iiv_speaker.hip; tools/play_a2m.py --audio gives the
+same samples from the file and takes the filter's parameters).  The .a2m bytes are the same with and without it."""
 import argparse
 import os
 import sys
@@ -108,6 +111,7 @@ def main():
     ap.add_argument("--fourth", action="store_true", help="IIV_OPT_FOURTH_OFFSET (not the reference's stream)")
     ap.add_argument("--joint", action="store_true", help="IIV_CONTENT_JOINT (not the reference's stream)")
     ap.add_argument("--preview", metavar="FILE.npy", help="also write the screen after each source frame's opcodes: uint8 (frames, 192, 560, 3)")
+    ap.add_argument("--preview-audio", metavar="FILE.wav", help="also write the PCM the stream's ticks play: 16-bit mono at 44 369 Hz")
     ap.add_argument("--quality", metavar="FILE.json",
                     help="also write, per source frame, the screen's squared error against the ingest's input frame (nine sums) and three PSNRs")
     ap.add_argument("--seed", type=int, default=1, help="random.seed / np.random.seed of the encoder's two nonce streams")
@@ -210,6 +214,9 @@ def main():
     else:
         ticks = audio_ticks[:, :ops.shape[1]]                      # opcode k carries tick k (movie.py:67-111)
     stream = a2m.emit_stream(mode, ops, ticks, addr)
+    if a.preview_audio:
+        pcm, counts = native.speaker_pcm(ticks.contiguous())
+        audio.write_wav(a.preview_audio, pcm[0, :counts[0]].cpu().numpy(), audio.speaker_rate())
     data = stream[0].cpu().numpy().tobytes()
     torch.cuda.synchronize()
     t2 = time.perf_counter()
