@@ -137,12 +137,21 @@ class ArrayFrameGrabber(FrameGrabber):
     (iiv_resize_frames_yuv420); frames that already have the target size go through the same call.
     fit, sar, fill (with resize=True; fit_geometry): "stretch" -- the default, the reference's resize and today's
     bytes -- pulls every source over the whole screen; "letterbox" keeps the whole frame and pads the screen with the colour
-    fill = (r, g, b); "crop" fills the screen with the frame's centred 4:3 part; sar = the source's pixel aspect ratio (num, den)."""
+    fill = (r, g, b); "crop" fills the screen with the frame's centred 4:3 part; sar = the source's pixel aspect ratio (num, den).
+    temporal=(lo, hi): the temporal hold (iiv_temporal_hold, include/iivision.h f14) behind the resize and in front of
+    every conversion -- a pixel within lo of its held value keeps the held bytes, one more than hi away takes the source's.
+    ingest_frames and memory_maps stay functions of their arguments: what they return is the hold run over frames 0 .. first +
+    count - 1, of which the last `count` are handed out.  The grabber keeps the held frame behind the last frame it converted and
+    goes on from it when `first` is the next frame; otherwise it runs again from frame 0, `batch` frames at a time.
+    temporal_counts() gives the pixels held, blended and passed of every frame converted so far.  None (the default) takes none
+    of these paths."""
 
     def __init__(self, frames_rgb, mode: VideoMode, palette: Palette = Palette.NTSC, dither=32,
                  input_frame_rate: float = 30, batch: int = 256, resize: bool = False, amplitude: int = 0, yuv_matrix="bt601",
-                 fit: str = "stretch", sar=(1, 1), fill=(0, 0, 0)):
+                 fit: str = "stretch", sar=(1, 1), fill=(0, 0, 0), temporal=None):
         super().__init__(mode)
+        self.temporal = None if temporal is None else native.temporal_pair(temporal)
+        self._held, self._held_next, self._held_counts = None, 0, []   # the held frame behind frame _held_next - 1, counts per call
         if fit not in FITS:
             raise ValueError("fit must be one of %s, got %r" % (", ".join(FITS), fit))
         if fit != "stretch" and not resize:
@@ -210,10 +219,37 @@ class ArrayFrameGrabber(FrameGrabber):
         self.batch = int(batch)
 
     def ingest_frames(self, first=0, count=None):
-        """CUDA uint8 (count, H, W, 3): frames first .. first + count - 1 as the conversion takes them, after any resize --
-        the reference picture screen.render_error measures a screen against."""
-        import torch
+        """CUDA uint8 (count, H, W, 3): frames first .. first + count - 1 as the conversion takes them, after any resize and
+        the temporal hold -- the reference picture screen.render_error measures a screen against."""
         count = len(self._rgb) - first if count is None else count
+        if self.temporal is None or count <= 0:
+            return self._source_frames(first, count)
+        if self._held is None or first != self._held_next:
+            # not the next frame: the hold again from frame 0, a batch at a time, up to the frame in front of `first`
+            self._held, self._held_next, self._held_counts = None, 0, []
+            while self._held_next < first:
+                self._hold(self._held_next, min(max(self.batch, 1), first - self._held_next))
+        return self._hold(first, count)
+
+    def _hold(self, first, count):
+        """frames first .. first + count - 1 through the hold, from the state behind frame first - 1"""
+        out, self._held, counts = native.temporal_hold(self._source_frames(first, count), *self.temporal, state=self._held, counts=True)
+        self._held_next = first + count
+        self._held_counts.append(counts)
+        return out
+
+    def temporal_counts(self):
+        """numpy uint32 (frames converted so far, 3): the pixels held, blended and passed of frames 0 .. n - 1 of the run of the
+        hold that the grabber's state belongs to (a call out of order starts that run again)."""
+        if self.temporal is None:
+            raise ValueError("temporal_counts() goes with temporal=(lo, hi)")
+        if not self._held_counts:
+            return np.zeros((0, 3), np.uint32)
+        return np.concatenate([c.cpu().numpy() for c in self._held_counts]).view(np.uint32)
+
+    def _source_frames(self, first, count):
+        """frames first .. first + count - 1 after any resize, in front of the hold"""
+        import torch
         if self._yuv is not None:
             y, u, v = (p[first:first + count] for p in self._yuv)
             d_u, d_v = _upload_chroma(torch, u, v)

@@ -907,6 +907,42 @@ long iiv_speaker_sample_count(long n_ops, int decim);
 int iiv_speaker_pcm(int n_streams, const uint8_t *d_ticks, size_t ticks_stride, const int64_t *d_counts, size_t counts_stride,
                     int decim, int order, int gain, int16_t *d_pcm, size_t pcm_stride, int *d_err, void *stream);
 
+/* ==== f14: temporal hold ====================================================
+ * The first front-end step along the time axis: a pixel that a viewer calls still keeps its bytes from frame to frame, so that
+ * sensor noise, compression ripple and a resampler's jitter are not priced and queued as differences.  It sits in front of every
+ * converter (f3, f6, f10) and changes none of them: where the frame carries the value of the frame before, the ordered dither,
+ * the mono dither and `direct` write the same bytes, and the error diffusions do wherever everything above and to the left is
+ * unchanged as well.  Integer arithmetic only, so every implementation agrees byte for byte (tests/temporal_model.py restates
+ * this section in numpy; csrc/iiv_temporal.hip computes it).
+ *   A clip is n_frames frames of `pixels` RGB pixels, 3 bytes each, dense within a frame.  Per clip there is one held frame h
+ *   (pixels * 3 bytes).  Per pixel, for frames t = 0, 1, ... in order, x the source pixel and y the output pixel:
+ *     if `first` is set and t == 0:  y = x, h = x; the pixel counts as passed.
+ *     otherwise  d = max(|x.r - h.r|, |x.g - h.g|, |x.b - h.b|)
+ *                w(d) = 0                                    for d <= lo     (y == h: held)
+ *                w(d) = 256                                  for d > hi      (y == x: passed)
+ *                w(d) = floor(256 (d - lo) / (hi - lo + 1))  between         (1..255: blended)
+ *                y_c = h_c + (((x_c - h_c) * w + 128) >> 8)  per channel, the shift arithmetic: floor towards minus infinity
+ *                h = y
+ *   d is taken against the HELD value, not against the previous source frame: a slow fade gets through once it has moved more
+ *   than lo -- hysteresis, not a freeze.  lo = hi = 0 is the identity, byte for byte.
+ *   Counts.  Per (clip, frame) three uint32: pixels held (d <= lo), blended (lo < d <= hi), passed (d > hi, and every pixel of a
+ *   `first` frame 0).  They sum to `pixels`.
+ * Frame t of clip k is read at d_src + k * src_clip_stride + t * src_frame_stride and written at d_out + k * out_clip_stride +
+ * t * out_frame_stride (strides in bytes).  d_state is [n_clips] held frames, clip k's at d_state + k * state_stride: with `first`
+ * they are only written, without it they are read and then written -- the h behind the call's last frame --, which is how a clip
+ * continues across calls.  d_counts is [n_clips][n_frames][3], dense, and may be NULL; every entry is written by the call, the
+ * caller clears nothing.  d_out == d_src with equal strides is allowed; any other overlap is the caller's error, and d_state
+ * overlaps nothing.
+ * IIV_ERR_INVALID before anything is launched, with nothing written: n_clips or n_frames < 0; pixels not a positive multiple of 4
+ * (or above 2^40); a pointer or a stride that is not 4-byte aligned; a frame stride below pixels * 3; with more than one clip a
+ * state_stride below pixels * 3; lo or hi outside 0..255, or lo > hi; a NULL d_src, d_out or d_state where there is work.
+ * n_clips == 0 or n_frames == 0 succeeds and touches nothing.  Asynchronous on `stream`; nothing is allocated, nothing
+ * synchronised, nothing kept between calls, no host memory is read after the call returns (w(d), 256 entries, goes to the kernel
+ * by value); the clearing of d_counts is issued on `stream` in front of the kernel. */
+int iiv_temporal_hold(int n_clips, int n_frames, long pixels, const uint8_t *d_src, size_t src_clip_stride, size_t src_frame_stride,
+                      uint8_t *d_out, size_t out_clip_stride, size_t out_frame_stride, uint8_t *d_state, size_t state_stride,
+                      int first, int lo, int hi, uint32_t *d_counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

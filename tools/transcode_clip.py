@@ -34,7 +34,11 @@ the fill colour, or cropped to its centred 4:3 part (frame_grabber.fit_geometry;
 screen as the reference does; --preview shows it and --quality measures against the fitted frame, the one the ingest saw.
 --preview-audio FILE.wav: also write what the stream's ticks sound like on the machine, 16-bit mono PCM at 44 369 Hz: the speaker's
 pulses, ACKs included, through the default CIC decimator (csrc/iiv_speaker.hip; tools/play_a2m.py --audio gives the
-same samples from the file and takes the filter's parameters).  The .a2m bytes are the same with and without it."""
+same samples from the file and takes the filter's parameters).  The .a2m bytes are the same with and without it.
+--temporal LO,HI: the temporal hold in front of the conversion (csrc/iiv_temporal.hip): a pixel within LO of the value
+held for it keeps the held bytes from frame to frame, one more than HI away takes the source's, one between moves part of the way;
+0,0 is the identity.  With --quality the JSON gains, per frame, the pixels held, blended and passed.  --synthetic-noise A adds
+uniform noise of -A..A (seeded by --seed, clamped) to the test card: the still parts of a noisy source are what the hold is for."""
 import argparse
 import os
 import sys
@@ -55,6 +59,14 @@ def test_card(n, width=280):
         out[f] = bars[((x + 3 * f) // 35) % 8]
         out[f, 128:] = ((x[128:] + y[128:] - 2 * f) % 256)[..., None]
     return out
+
+
+def add_noise(frames, amplitude, seed):
+    """uniform noise of -amplitude..amplitude on every byte, clamped; amplitude 0 returns the frames as they are"""
+    if amplitude == 0:
+        return frames
+    noise = np.random.default_rng(seed).integers(-amplitude, amplitude + 1, frames.shape)
+    return np.clip(frames.astype(np.int64) + noise, 0, 255).astype(np.uint8)
 
 
 def read_yuv(path, size, pix_fmt):
@@ -115,7 +127,20 @@ def main():
     ap.add_argument("--quality", metavar="FILE.json",
                     help="also write, per source frame, the screen's squared error against the ingest's input frame (nine sums) and three PSNRs")
     ap.add_argument("--seed", type=int, default=1, help="random.seed / np.random.seed of the encoder's two nonce streams")
+    ap.add_argument("--temporal", metavar="LO,HI", help="the temporal hold in front of the conversion: 0 <= LO <= HI <= 255 (DESIGN.md 30)")
+    ap.add_argument("--synthetic-noise", type=int, default=0, metavar="A",
+                    help="with --synthetic: uniform noise of -A..A on the test card, seeded by --seed (0: the card as it is)")
     a = ap.parse_args()
+    temporal = None
+    if a.temporal:
+        try:
+            temporal = tuple(int(v) for v in a.temporal.split(","))
+            if len(temporal) != 2 or not 0 <= temporal[0] <= temporal[1] <= 255:
+                raise ValueError
+        except ValueError:
+            ap.error("--temporal LO,HI with 0 <= LO <= HI <= 255")
+    if a.synthetic_noise < 0 or a.synthetic_noise > 255 or (a.synthetic_noise and not a.synthetic):
+        ap.error("--synthetic-noise: 0..255, with --synthetic")
     if a.tick < 4 or a.tick > 66 or a.tick % 2:
         ap.error("--tick: 4..66, even")
     if bool(a.frames) + bool(a.synthetic) + bool(a.yuv) != 1:
@@ -146,10 +171,13 @@ def main():
     mode = native.DHGR if a.mode == "DHGR" else native.HGR
     pal_id = palette.Palette[a.palette]
     rgb = read_yuv(a.yuv, a.size, a.pix_fmt) if a.yuv else np.load(a.frames) if a.frames else test_card(a.synthetic, 341 if a.fit != "stretch" else native.MONO_SIZE[mode][1] if pal_id == palette.Palette.MONO else 280)
+    if a.synthetic:
+        rgb = add_noise(rgb, a.synthetic_noise, a.seed)
     t0 = time.perf_counter()
+    hold = dict(temporal=temporal) if temporal is not None else {}
     grab = frame_grabber.ArrayFrameGrabber(rgb, video_mode.VideoMode[a.mode], pal_id,
                                            dither=int(a.dither) if a.dither.isdigit() else a.dither, resize=True,
-                                           amplitude=a.amplitude, yuv_matrix=a.yuv_matrix, fit=a.fit, sar=sar, fill=fill)
+                                           amplitude=a.amplitude, yuv_matrix=a.yuv_matrix, fit=a.fit, sar=sar, fill=fill, **hold)
     main_maps, aux_maps = grab.memory_maps()                       # (n, 32, 256) on the device
     dm = palette.diff_matrix(pal_id)                               # CIE2000 of the palette's colours; MONO: the dot distance
     table = native.build_table(mode, dm, True)
@@ -194,11 +222,16 @@ def main():
             import screen
             host = np.stack([t.cpu().numpy()[0] for t in sums])                   # (frames, 3, 3) uint64
             db = [screen.psnr(host, level)[1] for level in range(3)]
+            per_frame = [{"frame": i, "sums": [[int(v) for v in row] for row in host[i]],
+                          "psnr_db": [float(db[level][i]) for level in range(3)]} for i in range(n)]
+            report = {"mode": a.mode, "palette": a.palette, "ref_width": int(ref.shape[2]), "levels": ["dot", "quad", "unit"],
+                      "channels": ["R", "G", "B"], "frames": per_frame}
+            if temporal is not None:
+                report["temporal"] = {"lo": temporal[0], "hi": temporal[1], "counts": ["held", "blended", "passed"]}
+                for entry, c in zip(per_frame, grab.temporal_counts()):
+                    entry["temporal"] = [int(v) for v in c]
             with open(a.quality, "w") as f:
-                json.dump({"mode": a.mode, "palette": a.palette, "ref_width": int(ref.shape[2]), "levels": ["dot", "quad", "unit"],
-                           "channels": ["R", "G", "B"],
-                           "frames": [{"frame": i, "sums": [[int(v) for v in row] for row in host[i]],
-                                       "psnr_db": [float(db[level][i]) for level in range(3)]} for i in range(n)]}, f, indent=1)
+                json.dump(report, f, indent=1)
             print("screen against source, mean PSNR over %d frames: dot %.2f dB, quad %.2f dB, unit %.2f dB -> %s" % (
                 n, *(float(np.mean(d)) for d in db), a.quality))
     else:
