@@ -164,6 +164,10 @@ _SIGNATURES = {
     "iiv_speaker_pcm": (_i32, [_i32, _vp, _sz, _vp, _sz, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
     # ---- f14: temporal hold
     "iiv_temporal_hold": (_i32, [_i32, _i32, _lg, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _i32, _i32, _i32, _vp, _vp]),
+    # ---- f15: picture levels
+    "iiv_levels_histogram": (_i32, [_i32, _i32, _lg, _vp, _sz, _sz, _vp, _vp]),
+    "iiv_levels_auto": (_i32, [_vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "iiv_levels_apply": (_i32, [_i32, _i32, _lg, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp]),
 }
 SYMBOLS = list(_SIGNATURES)
 
@@ -1184,6 +1188,98 @@ def temporal_hold(frames, lo, hi, state=None, out=None, counts=False):
         check(lib().iiv_temporal_hold(c, n, H * W, dptr(frames), *strides(frames), dptr(out), *strides(out), dptr(state), frame_bytes,
                                       1 if first else 0, lo, hi, dptr(d_counts), stream_ptr()))
     return (out, state, d_counts) if counts else (out, state)
+
+
+# ---- f15: picture levels ---------------------------------------------------------------
+
+LEVELS_PPM = (5000, 5000)     # the 0.5th and 99.5th percentiles, as the reference's audio normalisation takes them (audio.py:60-78)
+LEVELS_MATRIX_RANGE = (-2048, 2047)   # Q8 entries of the 3 x 3 matrix: +-8.0 (include/iivision.h f15)
+
+
+def _clip_frames(frames, name):
+    """(c, n, H, W, clip stride, frame stride, several) of a CUDA uint8 tensor (n, H, W, 3) or (c, n, H, W, 3) with dense frames of
+    a positive multiple of 4 pixels"""
+    torch = _torch()
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() in (4, 5)):
+        raise ValueError("%s must be a CUDA uint8 tensor (n, H, W, 3) or (c, n, H, W, 3)" % name)
+    _dense_frames(frames, name)
+    several = frames.dim() == 5
+    c = int(frames.shape[0]) if several else 1
+    n, H, W = (int(v) for v in frames.shape[-4:-1])
+    if H * W <= 0 or (H * W) % 4:
+        raise ValueError("a frame must hold a positive multiple of 4 pixels, got %d x %d" % (H, W))
+    frame = _stride(frames, -4, H * W * 3)
+    return c, n, H, W, (_stride(frames, 0, n * frame) if several else n * frame), frame, several
+
+
+def levels_histogram(frames):
+    """The histograms of every frame (include/iivision.h: iiv_levels_histogram).  frames: CUDA uint8 (n, H, W, 3) for one clip or
+    (c, n, H, W, 3) for several; frame and clip strides are free (multiples of 4 bytes), a frame is dense, H * W a multiple of 4.
+    -> CUDA int32 (n, 4, 256) or (c, n, 4, 256): per frame the counts of R, G, B and Y = (77 R + 150 G + 29 B + 128) >> 8 (the
+    bits of a uint32: a frame of 2^31 equal pixels reads as negative).  Asynchronous on torch's current stream."""
+    torch = _torch()
+    c, n, H, W, clip_stride, frame_stride, several = _clip_frames(frames, "frames")
+    hist = torch.empty(((c,) if several else ()) + (n, 4, 256), dtype=torch.int32, device=frames.device)
+    with torch.cuda.device(frames.device):
+        check(lib().iiv_levels_histogram(c, n, H * W, dptr(frames), clip_stride, frame_stride, dptr(hist), stream_ptr()))
+    return hist
+
+
+def levels_auto(hist256, lo_ppm=LEVELS_PPM[0], hi_ppm=LEVELS_PPM[1]):
+    """(black, white) from one histogram of 256 counts (include/iivision.h: iiv_levels_auto): at most lo_ppm millionths of the
+    pixels lie below black and hi_ppm above white; an empty histogram, or points that meet, give (0, 255).  Host only."""
+    h = np.asarray(hist256)
+    if h.shape != (256,) or h.dtype.kind not in "iu" or (h.dtype.kind == "i" and h.size and int(h.min()) < 0):
+        raise ValueError("hist256 must be 256 non-negative integer counts")
+    if not (0 <= int(lo_ppm) <= 500000 and 0 <= int(hi_ppm) <= 500000 and int(lo_ppm) == lo_ppm and int(hi_ppm) == hi_ppm):
+        raise ValueError("lo_ppm and hi_ppm are integers in 0..500000, got (%r, %r)" % (lo_ppm, hi_ppm))
+    h = np.ascontiguousarray(h, dtype=np.uint64)
+    black, white = C.c_int(0), C.c_int(255)
+    check(lib().iiv_levels_auto(hptr(h), int(lo_ppm), int(hi_ppm), C.byref(black), C.byref(white)))
+    return black.value, white.value
+
+
+def levels_tables(lut, matrix, c):
+    """The tables of levels_apply as the C ABI takes them, on the host: (uint8 (k, 3, 256), int16 (k, 10), lut_stride,
+    matrix_stride) for c clips.  lut: uint8 (256,) -- one table for the three channels --, (3, 256), or (c, 3, 256) per clip;
+    matrix: None (256 * I), (3, 3) or (c, 3, 3) integers in -2048..2047, checked here because the library cannot.  A matrix row
+    is 18 bytes padded to 20."""
+    lut = np.asarray(lut)
+    if lut.dtype != np.uint8 or lut.shape not in ((256,), (3, 256), (c, 3, 256)):
+        raise ValueError("lut must be uint8 (256,), (3, 256) or (%d, 3, 256), got %s %s" % (c, lut.dtype, lut.shape))
+    lut_stride = 768 if lut.ndim == 3 else 0
+    lut = np.ascontiguousarray(np.broadcast_to(lut, (3, 256)) if lut.ndim < 3 else lut).reshape(-1, 3, 256)
+    m = np.asarray(256 * np.eye(3, dtype=np.int64) if matrix is None else matrix)
+    if m.dtype.kind not in "iu" or m.shape not in ((3, 3), (c, 3, 3)):
+        raise ValueError("matrix must be integers (3, 3) or (%d, 3, 3), got %s %s" % (c, m.dtype, m.shape))
+    if m.size and not (LEVELS_MATRIX_RANGE[0] <= int(m.min()) and int(m.max()) <= LEVELS_MATRIX_RANGE[1]):
+        raise ValueError("matrix entries are Q8 in %d..%d" % LEVELS_MATRIX_RANGE)
+    matrix_stride = 20 if m.ndim == 3 else 0
+    padded = np.zeros((m.size // 9, 10), np.int16)
+    padded[:, :9] = m.reshape(-1, 9)
+    return lut, padded, lut_stride, matrix_stride
+
+
+def levels_apply(frames, lut, matrix=None, out=None):
+    """A table per channel and a 3 x 3 matrix behind it, on every pixel (include/iivision.h: iiv_levels_apply): a_c = lut[c][x_c],
+    y_c = clamp((m[c] . a + 128) >> 8, 0, 255).  frames: as levels_histogram's.  lut, matrix: host arrays, see levels_tables (one
+    for all clips, or one per clip).  out: a tensor of frames' shape to write into (frames itself: in place), by default a new
+    contiguous one.  -> out.  Asynchronous on torch's current stream (the tables are uploaded on it)."""
+    torch = _torch()
+    c, n, H, W, clip_stride, frame_stride, several = _clip_frames(frames, "frames")
+    if out is None:
+        out = torch.empty(tuple(frames.shape), dtype=torch.uint8, device=frames.device)
+    else:
+        if not (isinstance(out, torch.Tensor) and tuple(out.shape) == tuple(frames.shape)):
+            raise ValueError("out must be a CUDA uint8 tensor of frames' shape %s" % (tuple(frames.shape),))
+        _clip_frames(out, "out")
+    _, _, _, _, out_clip_stride, out_frame_stride, _ = _clip_frames(out, "out")
+    lut, m, lut_stride, matrix_stride = levels_tables(lut, matrix, c)
+    with torch.cuda.device(frames.device):
+        d_lut, d_m = torch.from_numpy(lut.copy()).to(frames.device), torch.from_numpy(m).to(frames.device)
+        check(lib().iiv_levels_apply(c, n, H * W, dptr(frames), clip_stride, frame_stride, dptr(out), out_clip_stride, out_frame_stride,
+                                     dptr(d_lut), lut_stride, dptr(d_m), matrix_stride, stream_ptr()))
+    return out
 
 
 # ---- f4: the audio track ------------------------------------------------------------

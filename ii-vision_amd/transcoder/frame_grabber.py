@@ -96,6 +96,79 @@ def fit_geometry(h, w, H, W, fit, sar=(1, 1)):
     return tuple(_float32(q) for q in box), rect
 
 
+LUMA_WEIGHTS = (77, 150, 29)   # Y = (77 R + 150 G + 29 B + 128) >> 8 (include/iivision.h f15)
+
+
+def levels_lut(black=0, white=255, gamma=1.0, brightness=0, contrast=1.0):
+    """uint8 (256,): the table of one channel for native.levels_apply (include/iivision.h f15).
+    The linear part, in integers: with D = white - black >= 1, L[v] = clamp(floor((510 (v - black) + D) / (2 D)), 0, 255) --
+    255 (v - black) / D rounded half up --, so (0, 255) is the identity, L[black] = 0 and L[white] = 255.
+    The result is C[L[v]], C the float64 curve  C[u] = clamp(floor(255 (((u / 255) ** (1 / gamma) - 0.5) contrast + 0.5) +
+    brightness + 0.5), 0, 255): gamma (above 1 lifts the mid-tones), contrast about mid-grey, brightness in levels, rounded half
+    up.  At gamma = 1, brightness = 0, contrast = 1 the curve is skipped, not evaluated.  Monotone for contrast >= 0.  The curve
+    lives here alone: the C ABI takes tables."""
+    black, white = int(black), int(white)
+    if not 0 <= black < white <= 255:
+        raise ValueError("levels need 0 <= black < white <= 255, got (%d, %d)" % (black, white))
+    gamma, brightness, contrast = float(gamma), float(brightness), float(contrast)
+    if not (gamma > 0 and np.isfinite(gamma) and contrast >= 0 and np.isfinite(contrast) and -255 <= brightness <= 255):
+        raise ValueError("levels need gamma > 0, contrast >= 0 and brightness in -255..255")
+    d = white - black
+    linear = np.clip((510 * (np.arange(256, dtype=np.int64) - black) + d) // (2 * d), 0, 255)
+    if gamma == 1.0 and brightness == 0.0 and contrast == 1.0:
+        return linear.astype(np.uint8)
+    u = np.arange(256, dtype=np.float64) / 255.0
+    curve = np.clip(np.floor(255.0 * ((u ** (1.0 / gamma) - 0.5) * contrast + 0.5) + brightness + 0.5), 0, 255).astype(np.uint8)
+    return curve[linear]
+
+
+def saturation_matrix(s256):
+    """int16 (3, 3), Q8: the matrix of native.levels_apply that keeps a pixel's luma and scales its distance from grey by
+    s256 / 256 (0..1024).  With w = LUMA_WEIGHTS: o_R and o_B = ((256 - s256) w_k + 128) >> 8, o_G = (256 - s256) - o_R - o_B, and
+    m[c][k] = o_k + (c == k) s256.  Every row sums to 256, so greys are fixed points; 256 is the identity, 0 is grey."""
+    if int(s256) != s256 or not 0 <= int(s256) <= 1024:
+        raise ValueError("s256 is an integer in 0..1024, got %r" % (s256,))
+    s256 = int(s256)
+    o_r, o_b = ((256 - s256) * LUMA_WEIGHTS[0] + 128) >> 8, ((256 - s256) * LUMA_WEIGHTS[2] + 128) >> 8
+    o = np.array([o_r, (256 - s256) - o_r - o_b, o_b], np.int64)
+    return (o[None, :] + s256 * np.eye(3, dtype=np.int64)).astype(np.int16)
+
+
+class Levels:
+    """What ArrayFrameGrabber(levels=) does to a frame behind the resize and in front of the temporal hold.
+    black, white: the points pulled to 0 and 255; gamma, brightness, contrast: levels_lut's curve; saturation: 1.0 leaves the
+    colours, 0.0 is grey, up to 4.0 (saturation_matrix(round(256 saturation))).  auto=(lo_ppm, hi_ppm), or True for (5000, 5000):
+    black and white come from the clip's own histogram instead -- of Y, or with per_channel=True of R, G and B, one table each --
+    summed over frames 0 .. auto_frames - 1 (None: the whole clip)."""
+
+    def __init__(self, black=0, white=255, gamma=1.0, brightness=0, contrast=1.0, saturation=1.0, auto=None, per_channel=False,
+                 auto_frames=None):
+        levels_lut(black, white, gamma, brightness, contrast)   # (refuses bad values now)
+        self.black, self.white = int(black), int(white)
+        self.gamma, self.brightness, self.contrast, self.saturation = float(gamma), float(brightness), float(contrast), float(saturation)
+        if not 0 <= self.saturation <= 4:
+            raise ValueError("saturation is 0..4, got %r" % (saturation,))
+        self.s256 = int(np.floor(self.saturation * 256 + 0.5))
+        if auto is True:
+            auto = native.LEVELS_PPM
+        if auto is not None:
+            try:
+                lo, hi = auto
+                if int(lo) != lo or int(hi) != hi or not (0 <= lo <= 500000 and 0 <= hi <= 500000):
+                    raise ValueError
+                auto = (int(lo), int(hi))
+            except (TypeError, ValueError):
+                raise ValueError("auto is None or (lo_ppm, hi_ppm), integers in 0..500000, got %r" % (auto,)) from None
+            if (self.black, self.white) != (0, 255):
+                raise ValueError("auto finds black and white itself: give one or the other")
+        elif per_channel or auto_frames is not None:
+            raise ValueError("per_channel and auto_frames go with auto")
+        if auto_frames is not None and (int(auto_frames) != auto_frames or auto_frames < 1):
+            raise ValueError("auto_frames is None or a positive integer")
+        self.auto, self.per_channel = auto, bool(per_channel)
+        self.auto_frames = None if auto_frames is None else int(auto_frames)
+
+
 class FrameGrabber:
     """frame_grabber.py:18-24."""
 
@@ -144,12 +217,21 @@ class ArrayFrameGrabber(FrameGrabber):
     count - 1, of which the last `count` are handed out.  The grabber keeps the held frame behind the last frame it converted and
     goes on from it when `first` is the next frame; otherwise it runs again from frame 0, `batch` frames at a time.
     temporal_counts() gives the pixels held, blended and passed of every frame converted so far.  None (the default) takes none
-    of these paths."""
+    of these paths.
+    levels=Levels(...): picture levels (iiv_levels_histogram / iiv_levels_apply, include/iivision.h f15) behind the
+    resize and in front of the temporal hold: black and white points, gamma, brightness, contrast, saturation.  With Levels(auto=)
+    the points come from the clip's own histogram after the resize, computed once at first use, `batch` frames at a time, and
+    then fixed, so ingest_frames and memory_maps stay functions of their arguments; levels_report() gives the points and tables
+    in use.  None (the default) takes none of these paths and changes no byte."""
 
     def __init__(self, frames_rgb, mode: VideoMode, palette: Palette = Palette.NTSC, dither=32,
                  input_frame_rate: float = 30, batch: int = 256, resize: bool = False, amplitude: int = 0, yuv_matrix="bt601",
-                 fit: str = "stretch", sar=(1, 1), fill=(0, 0, 0), temporal=None):
+                 fit: str = "stretch", sar=(1, 1), fill=(0, 0, 0), temporal=None, levels=None):
         super().__init__(mode)
+        if levels is not None and not isinstance(levels, Levels):
+            raise ValueError("levels is None or a frame_grabber.Levels, got %r" % (levels,))
+        self.levels = levels
+        self._levels_tables = None   # (report, lut (3, 256), matrix (3, 3)) once computed
         self.temporal = None if temporal is None else native.temporal_pair(temporal)
         self._held, self._held_next, self._held_counts = None, 0, []   # the held frame behind frame _held_next - 1, counts per call
         if fit not in FITS:
@@ -219,11 +301,11 @@ class ArrayFrameGrabber(FrameGrabber):
         self.batch = int(batch)
 
     def ingest_frames(self, first=0, count=None):
-        """CUDA uint8 (count, H, W, 3): frames first .. first + count - 1 as the conversion takes them, after any resize and
-        the temporal hold -- the reference picture screen.render_error measures a screen against."""
+        """CUDA uint8 (count, H, W, 3): frames first .. first + count - 1 as the conversion takes them, after any resize, the
+        levels and the temporal hold -- the reference picture screen.render_error measures a screen against."""
         count = len(self._rgb) - first if count is None else count
         if self.temporal is None or count <= 0:
-            return self._source_frames(first, count)
+            return self._levelled_frames(first, count)
         if self._held is None or first != self._held_next:
             # not the next frame: the hold again from frame 0, a batch at a time, up to the frame in front of `first`
             self._held, self._held_next, self._held_counts = None, 0, []
@@ -233,7 +315,7 @@ class ArrayFrameGrabber(FrameGrabber):
 
     def _hold(self, first, count):
         """frames first .. first + count - 1 through the hold, from the state behind frame first - 1"""
-        out, self._held, counts = native.temporal_hold(self._source_frames(first, count), *self.temporal, state=self._held, counts=True)
+        out, self._held, counts = native.temporal_hold(self._levelled_frames(first, count), *self.temporal, state=self._held, counts=True)
         self._held_next = first + count
         self._held_counts.append(counts)
         return out
@@ -247,8 +329,46 @@ class ArrayFrameGrabber(FrameGrabber):
             return np.zeros((0, 3), np.uint32)
         return np.concatenate([c.cpu().numpy() for c in self._held_counts]).view(np.uint32)
 
+    def levels_report(self):
+        """The levels in use: {"black", "white"} -- ints, or with per_channel three each --, the parameters of the Levels, and
+        "lut" uint8 (3, 256) and "matrix" int16 (3, 3) as native.levels_apply takes them.  With Levels(auto=) the first call (or
+        the first frame asked for) reads frames 0 .. auto_frames - 1 and fixes the points."""
+        if self.levels is None:
+            raise ValueError("levels_report() goes with levels=Levels(...)")
+        if self._levels_tables is None:
+            lv = self.levels
+            points = [(lv.black, lv.white)] * 3
+            if lv.auto is not None:
+                n = len(self._rgb) if lv.auto_frames is None else min(lv.auto_frames, len(self._rgb))
+                total = np.zeros((4, 256), np.int64)
+                for first in range(0, n, max(self.batch, 1)):
+                    hist = native.levels_histogram(self._source_frames(first, min(max(self.batch, 1), n - first)))
+                    total += hist.long().sum(dim=0).cpu().numpy()   # (a count of 280x192 or 560x192 is far below 2^31)
+                if lv.per_channel:
+                    points = [native.levels_auto(total[c], *lv.auto) for c in range(3)]
+                else:
+                    points = [native.levels_auto(total[3], *lv.auto)] * 3
+            lut = np.stack([levels_lut(b, w, lv.gamma, lv.brightness, lv.contrast) for b, w in points])
+            per = lv.per_channel and lv.auto is not None
+            report = {"black": [p[0] for p in points] if per else points[0][0], "white": [p[1] for p in points] if per else points[0][1],
+                      "gamma": lv.gamma, "brightness": lv.brightness, "contrast": lv.contrast, "saturation": lv.saturation,
+                      "auto": list(lv.auto) if lv.auto is not None else None, "per_channel": lv.per_channel, "auto_frames": lv.auto_frames}
+            self._levels_tables = (report, lut, saturation_matrix(lv.s256))
+        report, lut, matrix = self._levels_tables
+        return dict(report, lut=lut.copy(), matrix=matrix.copy())
+
+    def _levelled_frames(self, first, count):
+        """frames first .. first + count - 1 after any resize and the levels, in front of the hold"""
+        frames = self._source_frames(first, count)
+        if self.levels is None or count <= 0:
+            return frames
+        if self._levels_tables is None:
+            self.levels_report()
+        _, lut, matrix = self._levels_tables
+        return native.levels_apply(frames, lut, matrix.astype(np.int64), out=frames)   # (a tensor of this call's own: in place)
+
     def _source_frames(self, first, count):
-        """frames first .. first + count - 1 after any resize, in front of the hold"""
+        """frames first .. first + count - 1 after any resize, in front of the levels and the hold"""
         import torch
         if self._yuv is not None:
             y, u, v = (p[first:first + count] for p in self._yuv)

@@ -943,6 +943,55 @@ int iiv_temporal_hold(int n_clips, int n_frames, long pixels, const uint8_t *d_s
                       uint8_t *d_out, size_t out_clip_stride, size_t out_frame_stride, uint8_t *d_state, size_t state_stride,
                       int first, int lo, int hi, uint32_t *d_counts, void *stream);
 
+/* ==== f15: picture levels ===================================================
+ * What the audio track has had since f4 (a factor from the 0.5th and 99.5th percentiles of the PCM) for the picture: a histogram
+ * per frame, black and white points from it, and a per-channel table with a 3 x 3 matrix behind it -- levels, gamma, brightness,
+ * contrast and saturation in one pass.  The stage sits behind the resize (f5, f11, f12) and in front of the temporal hold (f14),
+ * so the hold's thresholds are in the values the converters see; it changes no converter.  Integer arithmetic only, so every
+ * implementation agrees byte for byte (tests/levels_model.py restates this section in numpy; csrc/iiv_levels.hip computes it;
+ * DESIGN.md 31).  The curves themselves (gamma, contrast) are the caller's: the ABI takes tables, so no pow() has to agree across
+ * libraries (frame_grabber.levels_lut, frame_grabber.saturation_matrix).
+ *   A clip is laid out as in f14: n_frames frames of `pixels` RGB pixels, 3 bytes each, dense within a frame; frame t of clip k
+ *   is at d + k * clip_stride + t * frame_stride (strides in bytes).
+ *   Luma.  Y = (77 R + 150 G + 29 B + 128) >> 8; the weights sum to 256, so Y is 0..255. */
+
+/* The histograms of every frame: d_hist is [n_clips][n_frames][4][256] uint32, dense, channel order R, G, B, Y; entry v of a
+ * channel is the number of the frame's pixels whose channel has the value v, so each channel sums to `pixels`.  Per frame, so
+ * that the caller chooses which frames to sum.  Every entry is written by the call; the caller clears nothing.
+ * IIV_ERR_INVALID before anything is launched, with nothing written: n_clips or n_frames < 0; pixels not a positive multiple of 4,
+ * or above 2^31 (a count fits its uint32); a pointer or a stride that is not 4-byte aligned; a frame stride below pixels * 3; a
+ * NULL d_src or d_hist where there is work.  n_clips == 0 or n_frames == 0 succeeds and touches nothing.  Asynchronous on
+ * `stream`; nothing is allocated, nothing synchronised, nothing kept between calls, no host memory is read after the call
+ * returns; nothing but the one kernel is issued (no clearing, no global atomics: a frame is one workgroup's). */
+int iiv_levels_histogram(int n_clips, int n_frames, long pixels, const uint8_t *d_src, size_t src_clip_stride,
+                         size_t src_frame_stride, uint32_t *d_hist, void *stream);
+
+/* Black and white points from one histogram of 256 counts (one channel of the above, summed over the frames the caller chose):
+ * host only, a closed form.  total = sum of hist, cum(v) = sum of hist[u] for u <= v, cum(-1) = 0;
+ * k_lo = floor(total * lo_ppm / 10^6), k_hi = floor(total * hi_ppm / 10^6);
+ *   *black = the least v with cum(v) > k_lo             (at most k_lo pixels lie below it)
+ *   *white = the greatest v with total - cum(v - 1) > k_hi   (at most k_hi pixels lie above it)
+ * total == 0 or white <= black gives (0, 255), the identity range.  IIV_ERR_INVALID: lo_ppm or hi_ppm above 500000, a total
+ * above 2^43 (the products stay inside uint64), a NULL pointer. */
+int iiv_levels_auto(const uint64_t hist[256], uint32_t lo_ppm, uint32_t hi_ppm, int *black, int *white);
+
+/* The tables applied.  Clip k has a table lut[3][256] uint8 at d_lut + k * lut_stride and a matrix m[3][3] int16 (rows of 3,
+ * dense: 18 bytes) at (const uint8_t *)d_matrix + k * matrix_stride; a stride of 0 means one table or matrix for all clips, any
+ * other lut_stride is at least 768 and any other matrix_stride at least 20, and both are multiples of 4.  Per pixel x -> y:
+ *     a_c = lut[c][x_c]
+ *     y_c = clamp((m[c][0] a_0 + m[c][1] a_1 + m[c][2] a_2 + 128) >> 8, 0, 255)      the shift arithmetic
+ * The matrix is Q8: entries lie in -2048..2047 (+-8.0).  The call cannot check that without reading device memory: the Python
+ * layer checks it before upload, and for an entry outside that range the kernel computes the formula in int32 all the same
+ * (3 * 32768 * 255 + 128 < 2^31).  The identity table with 256 * I is the identity, byte for byte.  d_out == d_src with equal
+ * strides is allowed; any other overlap is the caller's error.
+ * IIV_ERR_INVALID before anything is launched, with nothing written: as for iiv_levels_histogram (pixels up to 2^40 as in f14; the
+ * frame strides of d_src and d_out both), and the stride rules above; a NULL d_src, d_out, d_lut or d_matrix where there is work.
+ * n_clips == 0 or n_frames == 0 succeeds and touches nothing.  Asynchronous on `stream`; nothing is allocated, nothing
+ * synchronised, nothing kept between calls, no host memory is read after the call returns. */
+int iiv_levels_apply(int n_clips, int n_frames, long pixels, const uint8_t *d_src, size_t src_clip_stride, size_t src_frame_stride,
+                     uint8_t *d_out, size_t out_clip_stride, size_t out_frame_stride, const uint8_t *d_lut, size_t lut_stride,
+                     const int16_t *d_matrix, size_t matrix_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

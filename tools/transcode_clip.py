@@ -38,7 +38,13 @@ same samples from the file and takes the filter's parameters).  The .a2m bytes a
 --temporal LO,HI: the temporal hold in front of the conversion (csrc/iiv_temporal.hip): a pixel within LO of the value
 held for it keeps the held bytes from frame to frame, one more than HI away takes the source's, one between moves part of the way;
 0,0 is the identity.  With --quality the JSON gains, per frame, the pixels held, blended and passed.  --synthetic-noise A adds
-uniform noise of -A..A (seeded by --seed, clamped) to the test card: the still parts of a noisy source are what the hold is for."""
+uniform noise of -A..A (seeded by --seed, clamped) to the test card: the still parts of a noisy source are what the hold is for.
+--levels auto[:LO,HI] / --levels BLACK,WHITE, --gamma G, --brightness B, --contrast C, --saturation S: picture levels behind the
+resize and in front of the hold (csrc/iiv_levels.hip; frame_grabber.Levels).  auto takes the black and white points
+from the clip's own luma histogram, at most LO and HI millionths of the pixels below and above them (5000,5000 by default: the
+0.5th and 99.5th percentiles); BLACK,WHITE gives them.  Any one of the five options turns the stage on; none of them leaves every
+byte as it was.  With --quality the JSON gains a "picture_levels" block: the points and parameters in use.  --synthetic-range LO,HI
+squeezes the test card into LO..HI: a clip graded into 16..235, or a washed-out transfer, is what --levels auto is for."""
 import argparse
 import os
 import sys
@@ -59,6 +65,13 @@ def test_card(n, width=280):
         out[f] = bars[((x + 3 * f) // 35) % 8]
         out[f, 128:] = ((x[128:] + y[128:] - 2 * f) % 256)[..., None]
     return out
+
+
+def squeeze(frames, lo, hi):
+    """the frames' 0..255 taken linearly into lo..hi, rounded half up; (0, 255) returns the frames as they are"""
+    if (lo, hi) == (0, 255):
+        return frames
+    return ((frames.astype(np.int64) * (2 * (hi - lo)) + 255) // 510 + lo).astype(np.uint8)
 
 
 def add_noise(frames, amplitude, seed):
@@ -130,7 +143,44 @@ def main():
     ap.add_argument("--temporal", metavar="LO,HI", help="the temporal hold in front of the conversion: 0 <= LO <= HI <= 255 (DESIGN.md 30)")
     ap.add_argument("--synthetic-noise", type=int, default=0, metavar="A",
                     help="with --synthetic: uniform noise of -A..A on the test card, seeded by --seed (0: the card as it is)")
+    ap.add_argument("--levels", metavar="auto[:LO,HI] | BLACK,WHITE", help="picture levels: the black and white points, found or given (DESIGN.md 31)")
+    ap.add_argument("--gamma", type=float, default=None, help="picture levels: gamma, above 1 lifts the mid-tones (1: none)")
+    ap.add_argument("--brightness", type=float, default=None, help="picture levels: added to every channel, in levels (0: none)")
+    ap.add_argument("--contrast", type=float, default=None, help="picture levels: slope about mid-grey (1: none)")
+    ap.add_argument("--saturation", type=float, default=None, help="picture levels: 0 grey, 1 none, up to 4")
+    ap.add_argument("--synthetic-range", metavar="LO,HI", help="with --synthetic: the test card squeezed into LO..HI")
     a = ap.parse_args()
+    levels_args = None
+    if a.levels is not None or any(v is not None for v in (a.gamma, a.brightness, a.contrast, a.saturation)):
+        levels_args = dict(gamma=1.0 if a.gamma is None else a.gamma, brightness=0 if a.brightness is None else a.brightness,
+                           contrast=1.0 if a.contrast is None else a.contrast, saturation=1.0 if a.saturation is None else a.saturation)
+        try:
+            if a.levels is None:
+                pass
+            elif a.levels == "auto":
+                levels_args["auto"] = (5000, 5000)
+            elif a.levels.startswith("auto:"):
+                levels_args["auto"] = tuple(int(v) for v in a.levels[5:].split(","))
+                if len(levels_args["auto"]) != 2 or not all(0 <= v <= 500000 for v in levels_args["auto"]):
+                    raise ValueError
+            else:
+                points = tuple(int(v) for v in a.levels.split(","))
+                if len(points) != 2 or not 0 <= points[0] < points[1] <= 255:
+                    raise ValueError
+                levels_args["black"], levels_args["white"] = points
+        except ValueError:
+            ap.error("--levels auto, auto:LO,HI with 0..500000 each, or BLACK,WHITE with 0 <= BLACK < WHITE <= 255")
+        if not (levels_args["gamma"] > 0 and levels_args["contrast"] >= 0 and -255 <= levels_args["brightness"] <= 255
+                and 0 <= levels_args["saturation"] <= 4):
+            ap.error("--gamma above 0, --contrast at least 0, --brightness -255..255, --saturation 0..4")
+    synthetic_range = (0, 255)
+    if a.synthetic_range:
+        try:
+            synthetic_range = tuple(int(v) for v in a.synthetic_range.split(","))
+            if len(synthetic_range) != 2 or not 0 <= synthetic_range[0] < synthetic_range[1] <= 255 or not a.synthetic:
+                raise ValueError
+        except ValueError:
+            ap.error("--synthetic-range LO,HI with 0 <= LO < HI <= 255, with --synthetic")
     temporal = None
     if a.temporal:
         try:
@@ -172,9 +222,11 @@ def main():
     pal_id = palette.Palette[a.palette]
     rgb = read_yuv(a.yuv, a.size, a.pix_fmt) if a.yuv else np.load(a.frames) if a.frames else test_card(a.synthetic, 341 if a.fit != "stretch" else native.MONO_SIZE[mode][1] if pal_id == palette.Palette.MONO else 280)
     if a.synthetic:
-        rgb = add_noise(rgb, a.synthetic_noise, a.seed)
+        rgb = add_noise(squeeze(rgb, *synthetic_range), a.synthetic_noise, a.seed)
     t0 = time.perf_counter()
     hold = dict(temporal=temporal) if temporal is not None else {}
+    if levels_args is not None:
+        hold["levels"] = frame_grabber.Levels(**levels_args)
     grab = frame_grabber.ArrayFrameGrabber(rgb, video_mode.VideoMode[a.mode], pal_id,
                                            dither=int(a.dither) if a.dither.isdigit() else a.dither, resize=True,
                                            amplitude=a.amplitude, yuv_matrix=a.yuv_matrix, fit=a.fit, sar=sar, fill=fill, **hold)
@@ -230,6 +282,9 @@ def main():
                 report["temporal"] = {"lo": temporal[0], "hi": temporal[1], "counts": ["held", "blended", "passed"]}
                 for entry, c in zip(per_frame, grab.temporal_counts()):
                     entry["temporal"] = [int(v) for v in c]
+            if levels_args is not None:
+                lv = grab.levels_report()
+                report["picture_levels"] = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in lv.items()}
             with open(a.quality, "w") as f:
                 json.dump(report, f, indent=1)
             print("screen against source, mean PSNR over %d frames: dot %.2f dB, quad %.2f dB, unit %.2f dB -> %s" % (
