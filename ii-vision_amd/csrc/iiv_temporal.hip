@@ -2,11 +2,10 @@
 // held value stays where the source is within `lo` of it, follows the source where it is more than `hi` away, and moves part of
 // the way in between.  The reference has nothing on the time axis: its frames reach bmp2dhr as the decoder delivers them.
 //
-// Shape.  The kernel only streams: every byte of the clip is read once and written once; frames are sequential per pixel and
-// independent across pixels and clips.
-//   * A lane owns four pixels: three dwords, 12 contiguous bytes per frame, so a wave reads and writes 768 contiguous bytes per
-//     frame.  Their held values live in three registers over the whole frame loop; the state is read in front of the loop
-//     (not with `first`) and written behind it.
+// Shape.  A work item is (clip, run of lanes) -- lanes of 12 bytes, runs and the capped grid are iiv_clip.h's.  The kernel only
+// streams: every byte is read once and written once; frames are sequential per pixel and independent across pixels and clips.
+//   * The held values of a lane's four pixels live in three registers over the whole frame loop; the state is read in front of
+//     the loop (not with `first`) and written behind it.
 //   * The only loop-carried dependence is the held value.  The source of frame t + kTemporalRing is loaded when frame t is
 //     taken out of a register ring of kTemporalRing frames (3 dwords each), so the chain per frame is VALU work and one LDS
 //     lookup, not a memory latency.  In place (d_out == d_src) a lane stores frame t behind its own load of frame t and of
@@ -18,47 +17,35 @@
 //   * Counts: a pixel is held where w == 0 and passed where w == 256; a wave counts each class of each of its four pixel slots
 //     with a ballot and lane 0 adds the three sums to the frame's entry: one atomic add per class per wave and frame.  Integer
 //     adds in any order give the same counts.  The entries are cleared on the caller's stream in front of the launch.
-//   * A work item is (clip, run of kTemporalThreads lanes); the items are walked with a grid stride under kTemporalGridCap
-//     workgroups.
 // Nothing is allocated, nothing synchronised, nothing kept between calls.
+#include "iiv_clip.h"
 #include "iiv_host.h"
 
 namespace iiv {
 
 namespace {
 
-constexpr int kTemporalThreads = 256;
-constexpr int kTemporalLanePixels = 4;      // pixels of a lane: 12 bytes = three dwords per frame
 constexpr int kTemporalRing = 8;            // frames whose source is in flight ahead of the one being computed
-constexpr int kTemporalGridCap = 2048;      // workgroups of a launch; the items beyond are reached by the grid stride
 
 struct TemporalWeights {
     uint16_t w[256];   // w(d) of f14: 0 for d <= lo, 256 for d > hi, 1..255 between
 };
 
-struct alignas(4) Dwords3 {
-    uint32_t v[3];
-};
-
-// byte i (0..11) of a lane's 12: channel i % 3 of pixel i / 3
-__device__ inline uint32_t temporal_byte(const Dwords3 &a, int i) { return (a.v[i >> 2] >> (8 * (i & 3))) & 0xffu; }
-
 template <bool kCount>
-__global__ __launch_bounds__(kTemporalThreads) void temporal_kernel(size_t n_items, size_t runs, size_t lanes, int n_frames,
-                                                                    const uint8_t *src, size_t src_clip_stride,
-                                                                    size_t src_frame_stride, uint8_t *out, size_t out_clip_stride,
-                                                                    size_t out_frame_stride, uint8_t *state, size_t state_stride,
-                                                                    int first, const TemporalWeights W, uint32_t *counts)
+__global__ __launch_bounds__(kClipThreads) void temporal_kernel(size_t n_items, size_t runs, size_t lanes, int n_frames, const uint8_t *src,
+                                                                size_t src_clip_stride, size_t src_frame_stride, uint8_t *out,
+                                                                size_t out_clip_stride, size_t out_frame_stride, uint8_t *state,
+                                                                size_t state_stride, int first, const TemporalWeights W, uint32_t *counts)
 {
     __shared__ uint16_t w_s[256];
     const int tid = threadIdx.x;
-    w_s[tid] = W.w[tid];   // (kTemporalThreads == 256)
+    w_s[tid] = W.w[tid];   // (kClipThreads == 256)
     __syncthreads();
     for (size_t item = blockIdx.x; item < n_items; item += gridDim.x) {
         const size_t clip = item / runs;
-        const size_t lane = (item - clip * runs) * kTemporalThreads + tid;
+        const size_t lane = (item - clip * runs) * kClipThreads + tid;
         const bool active = lane < lanes;
-        const size_t at = active ? lane * (kTemporalLanePixels * 3) : 0;   // (an idle lane computes on zeros and stores nothing)
+        const size_t at = active ? lane * (kClipLanePixels * 3) : 0;   // (an idle lane computes on zeros and stores nothing)
         const uint8_t *s = src + clip * src_clip_stride + at;
         uint8_t *o = out + clip * out_clip_stride + at;
         uint8_t *st = state + clip * state_stride + at;
@@ -79,15 +66,15 @@ __global__ __launch_bounds__(kTemporalThreads) void temporal_kernel(size_t n_ite
                 if (active && t + kTemporalRing < n_frames)
                     ring[k] = *reinterpret_cast<const Dwords3 *>(s + (size_t)(t + kTemporalRing) * src_frame_stride);
                 const bool pass_all = first && t == 0;
-                uint32_t y[kTemporalLanePixels * 3];
+                uint32_t y[kClipLanePixels * 3];
                 uint32_t n_held = 0, n_passed = 0;
 #pragma unroll
-                for (int p = 0; p < kTemporalLanePixels; p++) {
+                for (int p = 0; p < kClipLanePixels; p++) {
                     uint32_t xc[3], hc[3], d = 0;
 #pragma unroll
                     for (int c = 0; c < 3; c++) {
-                        xc[c] = temporal_byte(x, 3 * p + c);
-                        hc[c] = temporal_byte(h, 3 * p + c);
+                        xc[c] = clip_byte(x, 3 * p + c);
+                        hc[c] = clip_byte(h, 3 * p + c);
                         const uint32_t a = xc[c] > hc[c] ? xc[c] - hc[c] : hc[c] - xc[c];
                         d = a > d ? a : d;
                     }
@@ -100,11 +87,10 @@ __global__ __launch_bounds__(kTemporalThreads) void temporal_kernel(size_t n_ite
                     }
                 }
 #pragma unroll
-                for (int i = 0; i < 3; i++)
-                    h.v[i] = y[4 * i] | y[4 * i + 1] << 8 | y[4 * i + 2] << 16 | y[4 * i + 3] << 24;
+                for (int i = 0; i < 3; i++) h.v[i] = clip_pack4(y[4 * i], y[4 * i + 1], y[4 * i + 2], y[4 * i + 3]);
                 if (active) *reinterpret_cast<Dwords3 *>(o + (size_t)t * out_frame_stride) = h;
                 if (kCount) {
-                    const uint32_t n_all = kTemporalLanePixels * (uint32_t)__popcll(__ballot(active));
+                    const uint32_t n_all = kClipLanePixels * (uint32_t)__popcll(__ballot(active));
                     if ((tid & 63) == 0 && active) {   // (lanes are taken in order: a wave with an active lane has lane 0 active)
                         uint32_t *c = counts + (clip * (size_t)n_frames + (size_t)t) * 3;
                         atomicAdd(c + 0, n_held);
@@ -130,31 +116,24 @@ int iiv_temporal_hold(int n_clips, int n_frames, long pixels, const uint8_t *d_s
                       uint8_t *d_out, size_t out_clip_stride, size_t out_frame_stride, uint8_t *d_state, size_t state_stride,
                       int first, int lo, int hi, uint32_t *d_counts, void *stream)
 {
-    if (n_clips < 0 || n_frames < 0) return set_error(IIV_ERR_INVALID, "iiv_temporal_hold: n_clips or n_frames < 0");
-    if (pixels <= 0 || pixels % kTemporalLanePixels)
-        return set_error(IIV_ERR_INVALID, "iiv_temporal_hold: pixels must be a positive multiple of 4, got %ld", pixels);
-    if (pixels > (long)1 << 40) return set_error(IIV_ERR_INVALID, "iiv_temporal_hold: pixels above 2^40");
+    if (int rc = clip_refuse("iiv_temporal_hold", n_clips, n_frames, pixels, 40,
+                             (uintptr_t)d_src | (uintptr_t)d_out | (uintptr_t)d_state | (uintptr_t)d_counts | src_clip_stride |
+                                 src_frame_stride | out_clip_stride | out_frame_stride | state_stride,
+                             {src_frame_stride, out_frame_stride}))
+        return rc;
     if (lo < 0 || hi > 255 || lo > hi) return set_error(IIV_ERR_INVALID, "iiv_temporal_hold: 0 <= lo <= hi <= 255, got (%d, %d)", lo, hi);
-    if (((uintptr_t)d_src | (uintptr_t)d_out | (uintptr_t)d_state | (uintptr_t)d_counts | src_clip_stride | src_frame_stride |
-         out_clip_stride | out_frame_stride | state_stride) & 3)
-        return set_error(IIV_ERR_INVALID, "iiv_temporal_hold: every pointer and every stride must be 4-byte aligned");
-    const size_t frame_bytes = (size_t)pixels * 3;
-    if (src_frame_stride < frame_bytes || out_frame_stride < frame_bytes)
-        return set_error(IIV_ERR_INVALID, "iiv_temporal_hold: a frame stride is below the %zu bytes of a frame", frame_bytes);
-    if (n_clips > 1 && state_stride < frame_bytes)
-        return set_error(IIV_ERR_INVALID, "iiv_temporal_hold: state_stride is below the %zu bytes of a held frame", frame_bytes);
+    if (n_clips > 1 && state_stride < (size_t)pixels * 3)
+        return set_error(IIV_ERR_INVALID, "iiv_temporal_hold: state_stride is below the %zu bytes of a held frame", (size_t)pixels * 3);
     if (n_clips == 0 || n_frames == 0) return IIV_OK;
     if (!d_src || !d_out || !d_state) return set_error(IIV_ERR_INVALID, "iiv_temporal_hold: a NULL pointer");
     TemporalWeights W;
     for (int d = 0; d < 256; d++) W.w[d] = (uint16_t)(d <= lo ? 0 : d > hi ? 256 : 256 * (d - lo) / (hi - lo + 1));
-    const size_t lanes = (size_t)pixels / kTemporalLanePixels;
-    const size_t runs = (lanes + kTemporalThreads - 1) / kTemporalThreads;
+    const size_t lanes = clip_lanes(pixels), runs = clip_runs(lanes);
     const size_t n_items = (size_t)n_clips * runs;
-    const unsigned grid = (unsigned)(n_items < (size_t)kTemporalGridCap ? n_items : (size_t)kTemporalGridCap);
     hipStream_t st = (hipStream_t)stream;
     if (d_counts) IIV_HIP(hipMemsetAsync(d_counts, 0, (size_t)n_clips * (size_t)n_frames * 3 * sizeof(uint32_t), st));
-    return launch(d_counts ? temporal_kernel<true> : temporal_kernel<false>, "temporal_kernel launch", dim3(grid),
-                  dim3(kTemporalThreads), 0, st, n_items, runs, lanes, n_frames, d_src, src_clip_stride, src_frame_stride, d_out,
+    return launch(d_counts ? temporal_kernel<true> : temporal_kernel<false>, "temporal_kernel launch", dim3(clip_grid(n_items)),
+                  dim3(kClipThreads), 0, st, n_items, runs, lanes, n_frames, d_src, src_clip_stride, src_frame_stride, d_out,
                   out_clip_stride, out_frame_stride, d_state, state_stride, first ? 1 : 0, W, d_counts);
 }
 

@@ -1122,20 +1122,11 @@ def speaker_pcm(ticks, counts=None, decim=SPEAKER_DECIM, order=SPEAKER_ORDER, ga
     return out, np.array([speaker_sample_count(c, decim) for c in np.clip(host, 0, n)], dtype=np.int64)
 
 
-# ---- f14: temporal hold ---------------------------------------------------------------
+# ---- clip stages (f14, f15): the frames of a clip and the out= argument -------------------
 
-def temporal_pair(temporal):
-    """(lo, hi) of a temporal hold as two ints; ValueError unless 0 <= lo <= hi <= 255 (include/iivision.h f14)."""
-    try:
-        lo, hi = temporal
-        if int(lo) != lo or int(hi) != hi:
-            raise ValueError
-        lo, hi = int(lo), int(hi)
-    except (TypeError, ValueError):
-        raise ValueError("a temporal hold is two integers (lo, hi), got %r" % (temporal,)) from None
-    if not 0 <= lo <= hi <= 255:
-        raise ValueError("a temporal hold needs 0 <= lo <= hi <= 255, got (%d, %d)" % (lo, hi))
-    return lo, hi
+def _stride(t, dim, default):
+    """t.stride(dim) where it means something: a dimension of one element has no stride of its own"""
+    return int(t.stride(dim)) if int(t.shape[dim]) > 1 else default
 
 
 def _dense_frames(t, name):
@@ -1143,57 +1134,6 @@ def _dense_frames(t, name):
     if not (int(t.shape[-1]) == 3 and _stride(t, -1, 1) == 1 and _stride(t, -2, 3) == 3
             and _stride(t, -3, 3 * int(t.shape[-2])) == 3 * int(t.shape[-2])):
         raise ValueError("%s: a frame must be dense (H, W, 3) bytes" % name)
-
-
-def temporal_hold(frames, lo, hi, state=None, out=None, counts=False):
-    """The temporal hold along the frames of a clip (include/iivision.h: iiv_temporal_hold): a pixel within `lo` of its held value
-    keeps the held bytes, one more than `hi` away takes the source's, one between moves part of the way.  frames: CUDA uint8
-    (n, H, W, 3) for one clip or (c, n, H, W, 3) for several; frame and clip strides are free (multiples of 4 bytes), a frame is
-    dense, H * W a multiple of 4.  state: None starts the hold at frame 0 (`first`) and allocates the held frames; the state an
-    earlier call returned -- contiguous CUDA uint8 (H, W, 3) or (c, H, W, 3) -- continues that clip and is updated in place.
-    out: a tensor of frames' shape to write into (frames itself: in place), by default a new contiguous one.
-    -> (out, state), or (out, state, counts) with counts=True: CUDA int32 (n, 3) or (c, n, 3), the pixels held, blended and passed
-    of every frame.  Asynchronous on torch's current stream, like resize_frames."""
-    torch = _torch()
-    lo, hi = temporal_pair((lo, hi))
-    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() in (4, 5)):
-        raise ValueError("frames must be a CUDA uint8 tensor (n, H, W, 3) or (c, n, H, W, 3)")
-    _dense_frames(frames, "frames")
-    several = frames.dim() == 5
-    c = int(frames.shape[0]) if several else 1
-    n, H, W = (int(v) for v in frames.shape[-4:-1])
-    frame_bytes = H * W * 3
-    if H * W <= 0 or (H * W) % 4:
-        raise ValueError("a frame must hold a positive multiple of 4 pixels, got %d x %d" % (H, W))
-    if out is None:
-        out = torch.empty(tuple(frames.shape), dtype=torch.uint8, device=frames.device)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == tuple(frames.shape)):
-        raise ValueError("out must be a CUDA uint8 tensor of frames' shape %s" % (tuple(frames.shape),))
-    else:
-        _dense_frames(out, "out")
-    state_shape = ((c,) if several else ()) + (H, W, 3)
-    first = state is None
-    if first:
-        state = torch.empty(state_shape, dtype=torch.uint8, device=frames.device)
-    else:
-        _cuda_u8(state, "state")
-        if tuple(state.shape) != state_shape:
-            raise ValueError("state has shape %s, these frames need %s" % (tuple(state.shape), state_shape))
-    d_counts = torch.empty(((c,) if several else ()) + (n, 3), dtype=torch.int32, device=frames.device) if counts else None
-
-    def strides(t):
-        frame = _stride(t, -4, frame_bytes)
-        return (_stride(t, 0, n * frame) if several else n * frame), frame
-    with torch.cuda.device(frames.device):
-        check(lib().iiv_temporal_hold(c, n, H * W, dptr(frames), *strides(frames), dptr(out), *strides(out), dptr(state), frame_bytes,
-                                      1 if first else 0, lo, hi, dptr(d_counts), stream_ptr()))
-    return (out, state, d_counts) if counts else (out, state)
-
-
-# ---- f15: picture levels ---------------------------------------------------------------
-
-LEVELS_PPM = (5000, 5000)     # the 0.5th and 99.5th percentiles, as the reference's audio normalisation takes them (audio.py:60-78)
-LEVELS_MATRIX_RANGE = (-2048, 2047)   # Q8 entries of the 3 x 3 matrix: +-8.0 (include/iivision.h f15)
 
 
 def _clip_frames(frames, name):
@@ -1210,6 +1150,67 @@ def _clip_frames(frames, name):
         raise ValueError("a frame must hold a positive multiple of 4 pixels, got %d x %d" % (H, W))
     frame = _stride(frames, -4, H * W * 3)
     return c, n, H, W, (_stride(frames, 0, n * frame) if several else n * frame), frame, several
+
+
+def _clip_out(out, frames):
+    """(out, clip stride, frame stride) of a clip stage's out= argument: None is a new contiguous tensor of the checked frames' shape
+    on their device, anything else a CUDA uint8 tensor of exactly that shape with dense frames (frames itself: in place)"""
+    if out is None:
+        out = _torch().empty(tuple(frames.shape), dtype=frames.dtype, device=frames.device)
+    clip_stride, frame_stride = _clip_frames(out, "out")[4:6]
+    if tuple(out.shape) != tuple(frames.shape):
+        raise ValueError("out must be a CUDA uint8 tensor of frames' shape %s" % (tuple(frames.shape),))
+    return out, clip_stride, frame_stride
+
+
+# ---- f14: temporal hold ---------------------------------------------------------------
+
+def temporal_pair(temporal):
+    """(lo, hi) of a temporal hold as two ints; ValueError unless 0 <= lo <= hi <= 255 (include/iivision.h f14)."""
+    try:
+        lo, hi = temporal
+        if int(lo) != lo or int(hi) != hi:
+            raise ValueError
+        lo, hi = int(lo), int(hi)
+    except (TypeError, ValueError):
+        raise ValueError("a temporal hold is two integers (lo, hi), got %r" % (temporal,)) from None
+    if not 0 <= lo <= hi <= 255:
+        raise ValueError("a temporal hold needs 0 <= lo <= hi <= 255, got (%d, %d)" % (lo, hi))
+    return lo, hi
+
+
+def temporal_hold(frames, lo, hi, state=None, out=None, counts=False):
+    """The temporal hold along the frames of a clip (include/iivision.h: iiv_temporal_hold): a pixel within `lo` of its held value
+    keeps the held bytes, one more than `hi` away takes the source's, one between moves part of the way.  frames: CUDA uint8
+    (n, H, W, 3) for one clip or (c, n, H, W, 3) for several; frame and clip strides are free (multiples of 4 bytes), a frame is
+    dense, H * W a multiple of 4.  state: None starts the hold at frame 0 (`first`) and allocates the held frames; the state an
+    earlier call returned -- contiguous CUDA uint8 (H, W, 3) or (c, H, W, 3) -- continues that clip and is updated in place.
+    out: a tensor of frames' shape to write into (frames itself: in place), by default a new contiguous one.
+    -> (out, state), or (out, state, counts) with counts=True: CUDA int32 (n, 3) or (c, n, 3), the pixels held, blended and passed
+    of every frame.  Asynchronous on torch's current stream, like resize_frames."""
+    torch = _torch()
+    lo, hi = temporal_pair((lo, hi))
+    c, n, H, W, clip_stride, frame_stride, several = _clip_frames(frames, "frames")
+    out, out_clip_stride, out_frame_stride = _clip_out(out, frames)
+    state_shape = ((c,) if several else ()) + (H, W, 3)
+    first = state is None
+    if first:
+        state = torch.empty(state_shape, dtype=torch.uint8, device=frames.device)
+    else:
+        _cuda_u8(state, "state")
+        if tuple(state.shape) != state_shape:
+            raise ValueError("state has shape %s, these frames need %s" % (tuple(state.shape), state_shape))
+    d_counts = torch.empty(((c,) if several else ()) + (n, 3), dtype=torch.int32, device=frames.device) if counts else None
+    with torch.cuda.device(frames.device):
+        check(lib().iiv_temporal_hold(c, n, H * W, dptr(frames), clip_stride, frame_stride, dptr(out), out_clip_stride, out_frame_stride,
+                                      dptr(state), H * W * 3, 1 if first else 0, lo, hi, dptr(d_counts), stream_ptr()))
+    return (out, state, d_counts) if counts else (out, state)
+
+
+# ---- f15: picture levels ---------------------------------------------------------------
+
+LEVELS_PPM = (5000, 5000)     # the 0.5th and 99.5th percentiles, as the reference's audio normalisation takes them (audio.py:60-78)
+LEVELS_MATRIX_RANGE = (-2048, 2047)   # Q8 entries of the 3 x 3 matrix: +-8.0 (include/iivision.h f15)
 
 
 def levels_histogram(frames):
@@ -1267,13 +1268,7 @@ def levels_apply(frames, lut, matrix=None, out=None):
     contiguous one.  -> out.  Asynchronous on torch's current stream (the tables are uploaded on it)."""
     torch = _torch()
     c, n, H, W, clip_stride, frame_stride, several = _clip_frames(frames, "frames")
-    if out is None:
-        out = torch.empty(tuple(frames.shape), dtype=torch.uint8, device=frames.device)
-    else:
-        if not (isinstance(out, torch.Tensor) and tuple(out.shape) == tuple(frames.shape)):
-            raise ValueError("out must be a CUDA uint8 tensor of frames' shape %s" % (tuple(frames.shape),))
-        _clip_frames(out, "out")
-    _, _, _, _, out_clip_stride, out_frame_stride, _ = _clip_frames(out, "out")
+    out, out_clip_stride, out_frame_stride = _clip_out(out, frames)
     lut, m, lut_stride, matrix_stride = levels_tables(lut, matrix, c)
     with torch.cuda.device(frames.device):
         d_lut, d_m = torch.from_numpy(lut.copy()).to(frames.device), torch.from_numpy(m).to(frames.device)
@@ -1480,11 +1475,6 @@ def yuv_matrix(matrix):
     if m.shape != (6,) or not np.issubdtype(m.dtype, np.integer):
         raise ValueError("a YUV matrix is six integers (y_off, ky, rv, gu, gv, bu)")
     return np.ascontiguousarray(m, dtype=np.int32)
-
-
-def _stride(t, dim, default):
-    """t.stride(dim) where it means something: a dimension of one element has no stride of its own"""
-    return int(t.stride(dim)) if int(t.shape[dim]) > 1 else default
 
 
 def resize_frames_yuv420(y, u, v, size=RESIZE_SIZE, matrix="bt601", out=None, box=None, rect=None, fill=(0, 0, 0)):

@@ -1,6 +1,6 @@
 """What the picture-levels tests share (tests/test_gpu_levels.py, tests/test_gpu_levels_batches.py, tests/test_levels_batches_host.py,
-tests/test_levels_model.py): the case grid of the issue, the five kinds of input, the constants mirrored from csrc/iiv_levels.hip,
-the tables, and the model's output of each, computed once and shared read-only.
+tests/test_levels_model.py): the case grid of the issue, the five kinds of input, the constants mirrored from csrc/iiv_clip.h and
+csrc/iiv_levels.hip, the tables, and the model's output of each, computed once and shared read-only.
 
 Histograms are per frame and the tables are applied per pixel, so the model of the first n frames of the first c clips is the
 front of the model of the whole (CLIPS, FRAMES) block: one model run per (pixels, kind) serves every frame and clip count."""
@@ -10,11 +10,12 @@ import numpy as np
 
 import levels_model as M
 
-# mirrored from csrc/iiv_levels.hip; tests/test_levels_batches_host.py reads them from its text and fails if they moved
-THREADS = 256               # constexpr int kLevelsThreads = 256
-LANE_PIXELS = 4             # constexpr int kLevelsLanePixels = 4
-APPLY_FRAMES = 8            # constexpr int kLevelsApplyFrames = 8: frames of one apply item
-GRID_CAP = 2048             # constexpr int kLevelsGridCap = 2048: workgroups of a launch
+# mirrored from csrc/iiv_clip.h (the clip stages' shared three) and csrc/iiv_levels.hip (the frames of an apply item);
+# tests/test_levels_batches_host.py reads them from the text and fails if they moved
+THREADS = 256               # iiv_clip.h: constexpr int kClipThreads = 256
+LANE_PIXELS = 4             # iiv_clip.h: constexpr int kClipLanePixels = 4
+APPLY_FRAMES = 8            # iiv_levels.hip: constexpr int kLevelsApplyFrames = 8: frames of one apply item
+GRID_CAP = 2048             # iiv_clip.h: constexpr int kClipGridCap = 2048: workgroups of a launch
 
 # ---- the case grid ---------------------------------------------------------------------------------------------------------------
 

@@ -1,7 +1,7 @@
 """What the temporal-hold tests share (tests/test_gpu_temporal.py, tests/test_gpu_temporal_batches.py,
 tests/test_temporal_batches_host.py, tests/test_temporal_model.py, tests/test_gpu_temporal_grabber.py): the case grid of the issue,
-the four kinds of input, the constants mirrored from csrc/iiv_temporal.hip, the full-hold clip, and the model's output of each,
-computed once and shared read-only.
+the four kinds of input, the constants mirrored from csrc/iiv_clip.h and csrc/iiv_temporal.hip, the full-hold clip, and the model's
+output of each, computed once and shared read-only.
 
 The hold is causal and per pixel and per clip, so the model of the first n frames of the first c clips is the front of the model of
 the whole (CLIPS, FRAMES) block: one model run per (pixels, kind, pair) serves every frame count and clip count of the grid."""
@@ -11,11 +11,12 @@ import numpy as np
 
 import temporal_model as M
 
-# mirrored from csrc/iiv_temporal.hip; tests/test_temporal_batches_host.py reads them from its text and fails if they moved
-THREADS = 256               # constexpr int kTemporalThreads = 256
-LANE_PIXELS = 4             # constexpr int kTemporalLanePixels = 4
-RING = 8                    # constexpr int kTemporalRing = 8: source frames in flight ahead of the one computed
-GRID_CAP = 2048             # constexpr int kTemporalGridCap = 2048: workgroups of a launch
+# mirrored from csrc/iiv_clip.h (the clip stages' shared three) and csrc/iiv_temporal.hip (the ring);
+# tests/test_temporal_batches_host.py reads them from the text and fails if they moved
+THREADS = 256               # iiv_clip.h: constexpr int kClipThreads = 256
+LANE_PIXELS = 4             # iiv_clip.h: constexpr int kClipLanePixels = 4
+RING = 8                    # iiv_temporal.hip: constexpr int kTemporalRing = 8: source frames in flight ahead of the one computed
+GRID_CAP = 2048             # iiv_clip.h: constexpr int kClipGridCap = 2048: workgroups of a launch
 
 # ---- the case grid ---------------------------------------------------------------------------------------------------------------
 

@@ -1,8 +1,8 @@
 """CPU: what tests/test_gpu_levels_batches.py and the grid of tests/test_gpu_levels.py rely on without being able to see it.
 
-  the constants   kLevelsThreads, kLevelsLanePixels, kLevelsApplyFrames and kLevelsGridCap are read from the text of
-                  csrc/iiv_levels.hip and must equal what tests/levels_cases.py mirrors: a changed cap or frame range fails here,
-                  instead of passing unnoticed while the GPU tests silently stop reaching the loops' later trips
+  the constants   kClipThreads, kClipLanePixels and kClipGridCap are read from the text of csrc/iiv_clip.h, kLevelsApplyFrames
+                  from csrc/iiv_levels.hip, and must equal what tests/levels_cases.py mirrors: a changed cap or frame range fails
+                  here, instead of passing unnoticed while the GPU tests silently stop reaching the loops' later trips
   the arithmetic  2049 clips of one frame of 8 pixels are the least with a second trip of either kernel, 4097 with a third
   the pool        on the model alone: the seven clips' expected histograms and bytes are pairwise different, so "another clip's
                   result" can never equal the right one"""
@@ -23,17 +23,22 @@ def _one(pattern, text):
 def test_levels_constants_equal_the_source():
     with open(os.path.join(CSRC, "iiv_levels.hip")) as f:
         src = f.read()
-    assert int(_one(r"constexpr int kLevelsThreads = (\d+);", src)) == LC.THREADS
-    assert int(_one(r"constexpr int kLevelsLanePixels = (\d+);", src)) == LC.LANE_PIXELS
+    with open(os.path.join(CSRC, "iiv_clip.h")) as f:
+        clip = f.read()
+    assert int(_one(r"constexpr int kClipThreads = (\d+);", clip)) == LC.THREADS
+    assert int(_one(r"constexpr int kClipLanePixels = (\d+);", clip)) == LC.LANE_PIXELS
     assert int(_one(r"constexpr int kLevelsApplyFrames = (\d+);", src)) == LC.APPLY_FRAMES
-    assert int(_one(r"constexpr int kLevelsGridCap = (\d+);", src)) == LC.GRID_CAP
+    assert int(_one(r"constexpr int kClipGridCap = (\d+);", clip)) == LC.GRID_CAP
     # the histogram's items are the frames; apply's are clips times runs of lanes times ranges of frames; both grids are capped
     # and both loops stride by the grid
+    assert "size_t clip_lanes(long pixels) { return (size_t)pixels / kClipLanePixels; }" in clip
+    assert "size_t clip_runs(size_t lanes) { return (lanes + kClipThreads - 1) / kClipThreads; }" in clip
+    assert "(unsigned)(n_items < (size_t)kClipGridCap ? n_items : (size_t)kClipGridCap)" in clip
     assert "const size_t n_items = (size_t)n_clips * (size_t)n_frames;" in src
-    assert "const size_t runs = (lanes + kLevelsThreads - 1) / kLevelsThreads;" in src
+    assert "const size_t lanes = clip_lanes(pixels), runs = clip_runs(lanes);" in src
     assert "const size_t ranges = ((size_t)n_frames + kLevelsApplyFrames - 1) / kLevelsApplyFrames;" in src
     assert "const size_t n_items = (size_t)n_clips * runs * ranges;" in src
-    assert src.count("(unsigned)(n_items < (size_t)kLevelsGridCap ? n_items : (size_t)kLevelsGridCap)") == 2
+    assert " ".join(src.split()).count("dim3(clip_grid(n_items)), dim3(kClipThreads)") == 2
     assert src.count("for (size_t item = blockIdx.x; item < n_items; item += gridDim.x)") == 2
     # the grid's pixel counts sit around a wave and a workgroup, the frame counts of the apply test around a range of frames
     assert {64 * LC.LANE_PIXELS - 4, 64 * LC.LANE_PIXELS, 64 * LC.LANE_PIXELS + 4, LC.THREADS * LC.LANE_PIXELS + 4} <= set(LC.PIXELS)

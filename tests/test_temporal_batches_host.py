@@ -1,7 +1,7 @@
 """CPU: what tests/test_gpu_temporal_batches.py and the grid of tests/test_gpu_temporal.py rely on without being able to see it.
 
-  the constants   kTemporalThreads, kTemporalLanePixels, kTemporalRing and kTemporalGridCap are read from the text of
-                  csrc/iiv_temporal.hip and must equal what tests/temporal_cases.py mirrors: a changed cap or ring depth fails here,
+  the constants   kClipThreads, kClipLanePixels and kClipGridCap are read from the text of csrc/iiv_clip.h, kTemporalRing from
+                  csrc/iiv_temporal.hip, and must equal what tests/temporal_cases.py mirrors: a changed cap or ring depth fails here,
                   instead of passing unnoticed while the GPU tests silently stop reaching the loop's later trips or the ring's turn
   the arithmetic  2049 clips of 8 pixels are the least with a second trip, 4097 with a third
   the pool        on the model alone: the seven clips' expected outputs are pairwise different, so "another clip's bytes" can never
@@ -23,15 +23,19 @@ def _one(pattern, text):
 def test_temporal_constants_equal_the_source():
     with open(os.path.join(CSRC, "iiv_temporal.hip")) as f:
         src = f.read()
-    assert int(_one(r"constexpr int kTemporalThreads = (\d+);", src)) == TC.THREADS
-    assert int(_one(r"constexpr int kTemporalLanePixels = (\d+);", src)) == TC.LANE_PIXELS
+    with open(os.path.join(CSRC, "iiv_clip.h")) as f:
+        clip = f.read()
+    assert int(_one(r"constexpr int kClipThreads = (\d+);", clip)) == TC.THREADS
+    assert int(_one(r"constexpr int kClipLanePixels = (\d+);", clip)) == TC.LANE_PIXELS
     assert int(_one(r"constexpr int kTemporalRing = (\d+);", src)) == TC.RING
-    assert int(_one(r"constexpr int kTemporalGridCap = (\d+);", src)) == TC.GRID_CAP
+    assert int(_one(r"constexpr int kClipGridCap = (\d+);", clip)) == TC.GRID_CAP
     # the list of items is clips times runs of lanes, the grid is capped, and the loop strides by the grid
-    assert "const size_t lanes = (size_t)pixels / kTemporalLanePixels;" in src
-    assert "const size_t runs = (lanes + kTemporalThreads - 1) / kTemporalThreads;" in src
+    assert "size_t clip_lanes(long pixels) { return (size_t)pixels / kClipLanePixels; }" in clip
+    assert "size_t clip_runs(size_t lanes) { return (lanes + kClipThreads - 1) / kClipThreads; }" in clip
+    assert "(unsigned)(n_items < (size_t)kClipGridCap ? n_items : (size_t)kClipGridCap)" in clip
+    assert "const size_t lanes = clip_lanes(pixels), runs = clip_runs(lanes);" in src
     assert "const size_t n_items = (size_t)n_clips * runs;" in src
-    assert "(unsigned)(n_items < (size_t)kTemporalGridCap ? n_items : (size_t)kTemporalGridCap)" in src
+    assert "dim3(clip_grid(n_items)), dim3(kClipThreads)" in " ".join(src.split())
     assert "for (size_t item = blockIdx.x; item < n_items; item += gridDim.x)" in src
     # the grid's frame counts sit around the ring's depth, its pixel counts around a wave and a workgroup
     assert set(TC.N_FRAMES) == {1, 2, 3, TC.RING, TC.RING + 1, 2 * TC.RING + 1}
