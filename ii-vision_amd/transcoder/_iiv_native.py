@@ -168,6 +168,8 @@ _SIGNATURES = {
     "iiv_levels_histogram": (_i32, [_i32, _i32, _lg, _vp, _sz, _sz, _vp, _vp]),
     "iiv_levels_auto": (_i32, [_vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "iiv_levels_apply": (_i32, [_i32, _i32, _lg, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp]),
+    # ---- f16: spatial filter
+    "iiv_filter_frames": (_i32, [_i32, _i32, _i32, _i32, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
 }
 SYMBOLS = list(_SIGNATURES)
 
@@ -1274,6 +1276,56 @@ def levels_apply(frames, lut, matrix=None, out=None):
         d_lut, d_m = torch.from_numpy(lut.copy()).to(frames.device), torch.from_numpy(m).to(frames.device)
         check(lib().iiv_levels_apply(c, n, H * W, dptr(frames), clip_stride, frame_stride, dptr(out), out_clip_stride, out_frame_stride,
                                      dptr(d_lut), lut_stride, dptr(d_m), matrix_stride, stream_ptr()))
+    return out
+
+
+# ---- f16: spatial filter ---------------------------------------------------------------
+
+FILTER_GAIN_RANGE = (-256, 1024)   # Q8 entries of the gain table (include/iivision.h f16)
+FILTER_SIZE_MAX = 4096             # rows and pixels of a row
+
+
+def filter_tables(taps_x, taps_y, gain):
+    """(uint16 (5,), uint16 (5,), int16 (256,)) as the C ABI takes them; ValueError unless each tap set is five integers in 0..256
+    that sum to 256 and gain is 256 integers in -256..1024 (include/iivision.h f16)."""
+    taps = []
+    for name, t in (("taps_x", taps_x), ("taps_y", taps_y)):
+        a = np.asarray(t)
+        if a.shape != (5,) or a.dtype.kind not in "iu":
+            raise ValueError("%s must be five integers, got %r" % (name, t))
+        a = a.astype(np.int64)
+        if int(a.min()) < 0 or int(a.max()) > 256 or int(a.sum()) != 256:
+            raise ValueError("%s must be five taps in 0..256 that sum to 256, got %s" % (name, a.tolist()))
+        taps.append(np.ascontiguousarray(a, dtype=np.uint16))
+    g = np.asarray(gain)
+    if g.shape != (256,) or g.dtype.kind not in "iu":
+        raise ValueError("gain must be 256 integers, got %s %s" % (g.dtype, g.shape))
+    g = g.astype(np.int64)
+    if int(g.min()) < FILTER_GAIN_RANGE[0] or int(g.max()) > FILTER_GAIN_RANGE[1]:
+        raise ValueError("gain entries are Q8 in %d..%d" % FILTER_GAIN_RANGE)
+    return taps[0], taps[1], np.ascontiguousarray(g, dtype=np.int16)
+
+
+def filter_frames(frames, taps_x, taps_y, gain, out=None):
+    """The spatial filter on every frame (include/iivision.h: iiv_filter_frames): B the separable 5 x 5 blur of the frame under
+    taps_x and taps_y (edges replicated), d = p - B, m the largest |d| of the pixel's channels, y_c = clamp(p_c + ((gain[m] d_c +
+    128) >> 8)).  frames: CUDA uint8 (n, H, W, 3) for one clip or (c, n, H, W, 3) for several; frame and clip strides are free
+    (multiples of 4 bytes), a frame is dense, H is 1..4096 and W a multiple of 4 in 4..4096.  taps_x, taps_y, gain: see
+    filter_tables.  out: a tensor of frames' shape to write into, by default a new contiguous one; it must not share storage with
+    frames (a neighbour's source would be overwritten).  -> out.  Asynchronous on torch's current stream."""
+    torch = _torch()
+    tx, ty, g = filter_tables(taps_x, taps_y, gain)
+    c, n, H, W, clip_stride, frame_stride, several = _clip_frames(frames, "frames")
+    if not (1 <= H <= FILTER_SIZE_MAX and 4 <= W <= FILTER_SIZE_MAX and W % 4 == 0):
+        raise ValueError("a filtered frame has 1..%d rows of a multiple of 4 in 4..%d pixels, got %d x %d"
+                         % (FILTER_SIZE_MAX, FILTER_SIZE_MAX, H, W))
+    if out is not None and isinstance(out, torch.Tensor) and out.is_cuda and out.device == frames.device \
+            and out.untyped_storage().data_ptr() == frames.untyped_storage().data_ptr():
+        raise ValueError("out must not share storage with frames: the filter reads a pixel's neighbours")
+    out, out_clip_stride, out_frame_stride = _clip_out(out, frames)
+    with torch.cuda.device(frames.device):
+        check(lib().iiv_filter_frames(c, n, H, W, dptr(frames), clip_stride, frame_stride, dptr(out), out_clip_stride, out_frame_stride,
+                                      hptr(tx), hptr(ty), hptr(g), stream_ptr()))
     return out
 
 

@@ -169,6 +169,76 @@ class Levels:
         self.auto_frames = None if auto_frames is None else int(auto_frames)
 
 
+BINOMIAL_TAPS = (16, 64, 96, 64, 16)   # (1, 4, 6, 4, 1) / 16 scaled to 256 (include/iivision.h f16)
+
+
+def filter_taps(sigma):
+    """Five taps of one axis for native.filter_frames (include/iivision.h f16): the Gaussian exp(-k^2 / (2 sigma^2)),
+    k = -2..2, scaled to 256 and rounded half up, the centre taking the remainder so that the sum is exactly 256.  sigma == 0 gives
+    the identity (0, 0, 256, 0, 0).  The curve lives here alone: the C ABI takes taps."""
+    sigma = float(sigma)
+    if not (sigma >= 0 and np.isfinite(sigma)):
+        raise ValueError("a blur's sigma is a finite number >= 0, got %r" % (sigma,))
+    if sigma == 0:
+        return (0, 0, 256, 0, 0)
+    w = np.exp(-np.arange(-2, 3, dtype=np.float64) ** 2 / (2.0 * sigma * sigma))
+    side = [int(np.floor(256.0 * w[k] / w.sum() + 0.5)) for k in (0, 1)]
+    return (side[0], side[1], 256 - 2 * (side[0] + side[1]), side[1], side[0])
+
+
+def _int_pair(what, pair, hi_a, hi_b):
+    try:
+        a, b = pair
+        if int(a) != a or int(b) != b:
+            raise ValueError
+        a, b = int(a), int(b)
+    except (TypeError, ValueError):
+        raise ValueError("%s is two integers, got %r" % (what, pair)) from None
+    if not (0 <= a <= hi_a and 0 <= b <= hi_b):
+        raise ValueError("%s needs 0..%d and 0..%d, got (%d, %d)" % (what, hi_a, hi_b, a, b))
+    return a, b
+
+
+def filter_gain(denoise=None, sharpen=None):
+    """int16 (256,), Q8: the gain table of native.filter_frames over m, the largest channel difference between a pixel and its
+    blur (include/iivision.h f16).  denoise=(lo, hi), 0 <= lo <= hi <= 255: -256 for m <= lo (the pixel becomes the blur), -256 +
+    floor(256 (m - lo) / (hi - lo + 1)) for lo < m <= hi, 0 above (an edge is left alone).  sharpen=(amount256, threshold),
+    amount256 0..1024, threshold 0..255 and at least hi: amount256 for m > threshold (an unsharp mask that stays off the noise).
+    Neither: all zero, the identity."""
+    g = np.zeros(256, np.int64)
+    m = np.arange(256, dtype=np.int64)
+    hi = 0
+    if denoise is not None:
+        lo, hi = _int_pair("denoise=(lo, hi)", denoise, 255, 255)
+        if lo > hi:
+            raise ValueError("denoise needs lo <= hi, got (%d, %d)" % (lo, hi))
+        g = np.where(m <= lo, -256, np.where(m <= hi, -256 + (256 * (m - lo)) // (hi - lo + 1), 0))
+    if sharpen is not None:
+        amount, threshold = _int_pair("sharpen=(amount256, threshold)", sharpen, 1024, 255)
+        if denoise is not None and threshold < hi:
+            raise ValueError("sharpen's threshold %d lies below denoise's hi %d" % (threshold, hi))
+        g = np.where(m > threshold, amount, g)
+    return g.astype(np.int16)
+
+
+class Spatial:
+    """What ArrayFrameGrabber(spatial=) does to a frame behind the levels and in front of the temporal hold.
+    blur=(sx, sy): the Gaussian sigmas of the two axes in pixels (filter_taps); None is BINOMIAL_TAPS on both.  denoise, sharpen:
+    filter_gain's.  taps_x, taps_y and gain are what native.filter_frames takes."""
+
+    def __init__(self, blur=None, denoise=None, sharpen=None):
+        if blur is None:
+            self.taps_x = self.taps_y = BINOMIAL_TAPS
+        else:
+            try:
+                sx, sy = blur
+            except (TypeError, ValueError):
+                raise ValueError("blur is None or (sx, sy), got %r" % (blur,)) from None
+            self.taps_x, self.taps_y = filter_taps(sx), filter_taps(sy)
+        self.blur, self.denoise, self.sharpen = blur, denoise, sharpen
+        self.gain = filter_gain(denoise, sharpen)
+
+
 class FrameGrabber:
     """frame_grabber.py:18-24."""
 
@@ -222,12 +292,18 @@ class ArrayFrameGrabber(FrameGrabber):
     resize and in front of the temporal hold: black and white points, gamma, brightness, contrast, saturation.  With Levels(auto=)
     the points come from the clip's own histogram after the resize, computed once at first use, `batch` frames at a time, and
     then fixed, so ingest_frames and memory_maps stay functions of their arguments; levels_report() gives the points and tables
-    in use.  None (the default) takes none of these paths and changes no byte."""
+    in use.  None (the default) takes none of these paths and changes no byte.
+    spatial=Spatial(...): the spatial filter (iiv_filter_frames, include/iivision.h f16) behind the levels and in
+    front of the temporal hold: an edge-keeping denoise, an unsharp mask, or both.  Stateless per frame, so ingest_frames and
+    memory_maps stay functions of their arguments.  None (the default) takes none of these paths and changes no byte."""
 
     def __init__(self, frames_rgb, mode: VideoMode, palette: Palette = Palette.NTSC, dither=32,
                  input_frame_rate: float = 30, batch: int = 256, resize: bool = False, amplitude: int = 0, yuv_matrix="bt601",
-                 fit: str = "stretch", sar=(1, 1), fill=(0, 0, 0), temporal=None, levels=None):
+                 fit: str = "stretch", sar=(1, 1), fill=(0, 0, 0), temporal=None, levels=None, spatial=None):
         super().__init__(mode)
+        if spatial is not None and not isinstance(spatial, Spatial):
+            raise ValueError("spatial is None or a frame_grabber.Spatial, got %r" % (spatial,))
+        self.spatial = spatial
         if levels is not None and not isinstance(levels, Levels):
             raise ValueError("levels is None or a frame_grabber.Levels, got %r" % (levels,))
         self.levels = levels
@@ -302,10 +378,10 @@ class ArrayFrameGrabber(FrameGrabber):
 
     def ingest_frames(self, first=0, count=None):
         """CUDA uint8 (count, H, W, 3): frames first .. first + count - 1 as the conversion takes them, after any resize, the
-        levels and the temporal hold -- the reference picture screen.render_error measures a screen against."""
+        levels, the spatial filter and the temporal hold -- the reference picture screen.render_error measures a screen against."""
         count = len(self._rgb) - first if count is None else count
         if self.temporal is None or count <= 0:
-            return self._levelled_frames(first, count)
+            return self._filtered_frames(first, count)
         if self._held is None or first != self._held_next:
             # not the next frame: the hold again from frame 0, a batch at a time, up to the frame in front of `first`
             self._held, self._held_next, self._held_counts = None, 0, []
@@ -315,7 +391,7 @@ class ArrayFrameGrabber(FrameGrabber):
 
     def _hold(self, first, count):
         """frames first .. first + count - 1 through the hold, from the state behind frame first - 1"""
-        out, self._held, counts = native.temporal_hold(self._levelled_frames(first, count), *self.temporal, state=self._held, counts=True)
+        out, self._held, counts = native.temporal_hold(self._filtered_frames(first, count), *self.temporal, state=self._held, counts=True)
         self._held_next = first + count
         self._held_counts.append(counts)
         return out
@@ -357,8 +433,15 @@ class ArrayFrameGrabber(FrameGrabber):
         report, lut, matrix = self._levels_tables
         return dict(report, lut=lut.copy(), matrix=matrix.copy())
 
+    def _filtered_frames(self, first, count):
+        """frames first .. first + count - 1 after any resize, the levels and the spatial filter, in front of the hold"""
+        frames = self._levelled_frames(first, count)
+        if self.spatial is None or count <= 0:
+            return frames
+        return native.filter_frames(frames, self.spatial.taps_x, self.spatial.taps_y, self.spatial.gain)   # (out of place: a halo)
+
     def _levelled_frames(self, first, count):
-        """frames first .. first + count - 1 after any resize and the levels, in front of the hold"""
+        """frames first .. first + count - 1 after any resize and the levels, in front of the filter and the hold"""
         frames = self._source_frames(first, count)
         if self.levels is None or count <= 0:
             return frames

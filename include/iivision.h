@@ -992,6 +992,37 @@ int iiv_levels_apply(int n_clips, int n_frames, long pixels, const uint8_t *d_sr
                      uint8_t *d_out, size_t out_clip_stride, size_t out_frame_stride, const uint8_t *d_lut, size_t lut_stride,
                      const int16_t *d_matrix, size_t matrix_stride, void *stream);
 
+/* ==== f16: spatial filter ===================================================
+ * The first front-end step that looks at a pixel's neighbours: a separable 5 x 5 blur B of the frame, and per pixel a gain on the
+ * difference between the pixel and B, chosen by the size of that difference.  A negative gain where the difference is small pulls
+ * noise to the neighbourhood's mean and leaves an edge alone (denoise); a positive gain where it is large is an unsharp mask.  The
+ * stage sits behind the levels (f15) and in front of the temporal hold (f14), so both thresholds are in the values the converters
+ * see and the hold sees the denoised picture; it changes no converter.  Integer arithmetic only, so every implementation agrees
+ * byte for byte (tests/spatial_model.py restates this section in numpy; csrc/iiv_filter.hip computes it).
+ *   A clip is laid out as in f14 and f15, but the frame's geometry matters: a frame is `height` rows of `width` RGB pixels, 3 bytes
+ *   each, rows dense (width * 3 bytes); frame t of clip k is at d + k * clip_stride + t * frame_stride (strides in bytes).
+ *   Coordinates outside the frame are clamped to it: the edge is replicated.
+ *   taps_x[5] and taps_y[5] are 0..256 each and sum to exactly 256 per axis; gain[256] is Q8, each entry in -256..1024.  Per frame,
+ *   per channel c, p the source:
+ *     h_c(x, y) = sum_{k=0..4} taps_x[k] * p_c(clamp(x + k - 2, 0, width - 1), y)                        (0..65280: fits a uint16)
+ *     B_c(x, y) = (sum_{j=0..4} taps_y[j] * h_c(x, clamp(y + j - 2, 0, height - 1)) + 32768) >> 16       (0..255)
+ *     d_c = p_c - B_c
+ *     m   = max(|d_r|, |d_g|, |d_b|)                            one index per pixel, as f14 takes one d per pixel
+ *     y_c = clamp(p_c + ((gain[m] * d_c + 128) >> 8), 0, 255)   the shift arithmetic: floor towards minus infinity
+ *   gain == 0 everywhere is the identity, and so are the taps (0, 0, 256, 0, 0) on both axes whatever the gain; gain == -256
+ *   everywhere gives y == B, the plain blur; a constant frame is a fixed point.
+ * IIV_ERR_INVALID before anything is launched, with nothing written, in this order: n_clips or n_frames < 0; height * width not a
+ * positive multiple of 4, or above 2^24; d_src, d_out or a stride that is not 4-byte aligned; a frame stride below height * width *
+ * 3; then height outside 1..4096; width outside 4..4096 or not a multiple of 4; NULL taps_x, taps_y or gain; a tap above 256, or
+ * an axis whose taps do not sum to 256; a gain outside -256..1024; d_out == d_src (a neighbour's source would be overwritten: in
+ * place is not possible here; any other overlap is the caller's error); a NULL d_src or d_out where there is work.
+ * n_clips == 0 or n_frames == 0 succeeds and touches nothing.  Asynchronous on `stream`; nothing is allocated, nothing
+ * synchronised, nothing kept between calls, no host memory is read after the call returns (the taps and the gain go to the kernel
+ * by value); nothing but the one kernel is issued. */
+int iiv_filter_frames(int n_clips, int n_frames, int height, int width, const uint8_t *d_src, size_t src_clip_stride,
+                      size_t src_frame_stride, uint8_t *d_out, size_t out_clip_stride, size_t out_frame_stride,
+                      const uint16_t taps_x[5], const uint16_t taps_y[5], const int16_t gain[256], void *stream);
+
 #ifdef __cplusplus
 }
 #endif

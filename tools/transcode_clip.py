@@ -44,7 +44,13 @@ resize and in front of the hold (csrc/iiv_levels.hip; frame_grabbe
 from the clip's own luma histogram, at most LO and HI millionths of the pixels below and above them (5000,5000 by default: the
 0.5th and 99.5th percentiles); BLACK,WHITE gives them.  Any one of the five options turns the stage on; none of them leaves every
 byte as it was.  With --quality the JSON gains a "picture_levels" block: the points and parameters in use.  --synthetic-range LO,HI
-squeezes the test card into LO..HI: a clip graded into 16..235, or a washed-out transfer, is what --levels auto is for."""
+squeezes the test card into LO..HI: a clip graded into 16..235, or a washed-out transfer, is what --levels auto is for.
+--denoise LO,HI, --sharpen AMOUNT[,THRESHOLD], --blur SX[,SY]: the spatial filter behind the levels and in front of the hold
+(csrc/iiv_filter.hip; frame_grabber.Spatial).  A pixel is compared with a 5 x 5 blur of its neighbourhood -- Gaussian,
+sigmas SX and SY in pixels (SY = SX when left out); without --blur the binomial (1, 4, 6, 4, 1) / 16 on both axes --; where the
+largest channel difference is at most LO the pixel takes the blur's value, above HI it is left alone, between it moves part of the
+way (denoise); where it is above THRESHOLD (by default HI, or 0 without --denoise) the difference is amplified by AMOUNT / 256
+(sharpen, an unsharp mask; AMOUNT 0..1024).  Any one of the three turns the stage on; none of them leaves every byte as it was."""
 import argparse
 import os
 import sys
@@ -149,7 +155,35 @@ def main():
     ap.add_argument("--contrast", type=float, default=None, help="picture levels: slope about mid-grey (1: none)")
     ap.add_argument("--saturation", type=float, default=None, help="picture levels: 0 grey, 1 none, up to 4")
     ap.add_argument("--synthetic-range", metavar="LO,HI", help="with --synthetic: the test card squeezed into LO..HI")
+    ap.add_argument("--denoise", metavar="LO,HI", help="spatial filter: pull a pixel within LO of its neighbourhood's blur to it, leave one above HI (DESIGN.md 33)")
+    ap.add_argument("--sharpen", metavar="AMOUNT[,THRESHOLD]", help="spatial filter: unsharp mask, AMOUNT / 256 (0..1024) of the difference above THRESHOLD")
+    ap.add_argument("--blur", metavar="SX[,SY]", help="spatial filter: the Gaussian sigmas of the blur in pixels (default: binomial taps)")
     a = ap.parse_args()
+    spatial_args = None
+    if a.denoise is not None or a.sharpen is not None or a.blur is not None:
+        spatial_args = {}
+        try:
+            if a.denoise is not None:
+                spatial_args["denoise"] = tuple(int(v) for v in a.denoise.split(","))
+                if len(spatial_args["denoise"]) != 2 or not 0 <= spatial_args["denoise"][0] <= spatial_args["denoise"][1] <= 255:
+                    raise ValueError
+            if a.sharpen is not None:
+                sharpen = tuple(int(v) for v in a.sharpen.split(","))
+                if len(sharpen) == 1:
+                    sharpen += (spatial_args["denoise"][1] if a.denoise is not None else 0,)
+                if len(sharpen) != 2 or not 0 <= sharpen[0] <= 1024 or not spatial_args.get("denoise", (0, 0))[1] <= sharpen[1] <= 255:
+                    raise ValueError
+                spatial_args["sharpen"] = sharpen
+            if a.blur is not None:
+                blur = tuple(float(v) for v in a.blur.split(","))
+                if len(blur) == 1:
+                    blur += blur
+                if len(blur) != 2 or not all(0 <= v < float("inf") for v in blur):
+                    raise ValueError
+                spatial_args["blur"] = blur
+        except ValueError:
+            ap.error("--denoise LO,HI with 0 <= LO <= HI <= 255; --sharpen AMOUNT[,THRESHOLD] with 0..1024 and HI <= THRESHOLD <= 255; "
+                     "--blur SX[,SY] with sigmas >= 0")
     levels_args = None
     if a.levels is not None or any(v is not None for v in (a.gamma, a.brightness, a.contrast, a.saturation)):
         levels_args = dict(gamma=1.0 if a.gamma is None else a.gamma, brightness=0 if a.brightness is None else a.brightness,
@@ -227,6 +261,8 @@ def main():
     hold = dict(temporal=temporal) if temporal is not None else {}
     if levels_args is not None:
         hold["levels"] = frame_grabber.Levels(**levels_args)
+    if spatial_args is not None:
+        hold["spatial"] = frame_grabber.Spatial(**spatial_args)
     grab = frame_grabber.ArrayFrameGrabber(rgb, video_mode.VideoMode[a.mode], pal_id,
                                            dither=int(a.dither) if a.dither.isdigit() else a.dither, resize=True,
                                            amplitude=a.amplitude, yuv_matrix=a.yuv_matrix, fit=a.fit, sar=sar, fill=fill, **hold)
